@@ -2,6 +2,8 @@
 """bench.py - BASELINE metric: episodes/sec (query+support forward), SAM ViT-B 1024 px, 1-way 1-shot, on N MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                    # + roofline, kernel table, eager / CPU baselines
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR        # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one ``Lam.forward`` over a batch of ``--episodes`` synthetic 1-way 1-shot episodes (BASELINE cfg2: encoder on
@@ -9,7 +11,11 @@ query + support image, prompt encoder, mask decoder, post-processed full-resolut
 so for N > 1 every rank runs its own batch (weak scaling, no data-path collective); the timed region is bracketed by a
 barrier + device sync and the MAX over ranks is reported.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times ``--steps`` steps, writes the outputs if ``--dump-outputs`` is given and prints the line
+(``roofline``, ``kernels_ms_per_step`` and ``vs_baseline`` are null then).  Inputs and weights are seeded: the same arguments
+give the same inputs in every run.
+
+Extra objects on the line with --full:
   roofline      the dominant kernel (la_gemm: every Linear / conv of the path) timed live with HIP events on the launch
                 stream in a separate instrumented step: algorithmic FLOPs of all its launches / their summed duration,
                 against the gfx950 dense fp16/bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).  `traffic` = HBM-side
@@ -85,6 +91,30 @@ def make_inputs(episodes: int, seed: int, device, workload="cfg2"):
     batch = make_episode(batch=episodes, seed=seed, prompts=("mask",), **WORKLOADS[workload]["episode"])
     dev_keys = ("images", "embeddings", "prompt_masks")
     return {k: (v.to(device) if k in dev_keys else v) for k, v in batch.items()}
+
+
+DUMP_BYTES = 60_000_000        # data bytes of all --dump-outputs arrays together (npy headers come on top: < 64 MB in all)
+
+
+def dump_outputs(out, path: str, budget: int = DUMP_BYTES):
+    """Write every tensor the timed path handed its caller as ``path/<name>.npy`` (float64 stays float64, everything else is
+    written as float32).  Smaller arrays go first and are written whole; an array larger than its share of what is left of the
+    budget is written as a fixed sample: flat indices drawn by a generator seeded with 0, in ascending order, so that every run
+    and every build with the same arguments writes the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = sorted(((k, v.detach()) for k, v in out.items() if isinstance(v, torch.Tensor)), key=lambda kv: kv[1].numel())
+    left = budget
+    for i, (name, t) in enumerate(arrays):
+        dt = torch.float64 if t.dtype == torch.float64 or (not t.is_floating_point() and t.dtype != torch.bool) else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        n = min(t.numel(), left // (len(arrays) - i) // esz)
+        if n < t.numel():
+            print(f"dump-outputs: {name} {tuple(t.shape)}: seeded sample of {n} of {t.numel()} elements", file=sys.stderr)
+            idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(0)).to(t.device).sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), t.to(dt).cpu().numpy())
+        left -= n * esz
 
 
 class KernelTimer:
@@ -217,7 +247,8 @@ def host_cpu():
 
 def cpu_baseline(cfg, timed: int = 3):
     """Time the CPU oracle (kind "port": the checked restatement of the reference's torch path) on this box's host cores: one warm-up
-    episode + the median of ``timed`` episodes of the bench workload, torch intra-op threads = physical cores."""
+    episode + the median of ``timed`` episodes of the bench workload, torch intra-op threads = physical cores, or
+    OMP_NUM_THREADS where that is set and smaller (a host that grants this process fewer CPUs than it has)."""
     from labelanything_amd.episodes import make_episode
     from labelanything_amd.weights import init_state_dict
     from oracle import lam_oracle as O
@@ -225,7 +256,8 @@ def cpu_baseline(cfg, timed: int = 3):
     sd = init_state_dict(cfg, 2)
     geo = geometry_for(cfg)
     model, phys, logical = host_cpu()
-    torch.set_num_threads(max(1, phys))
+    granted = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    torch.set_num_threads(max(1, min(phys, int(granted)) if granted.isdigit() else phys))
     times = []
     with torch.no_grad():
         for i in range(timed + 1):
@@ -311,8 +343,8 @@ def main():
                     "freeze_backbone): forward with saved activations + encoder backward + 96 M-parameter gradient all-reduce")
     ap.add_argument("--attn-fp8", action="store_true", help="HF encoders (cfg1/3/5): QK^T of the attention on the fp8 (e4m3) MFMA, as BASELINE "
                     "configs[4] words cfg5; 3e-3 on the logits, i.e. outside the 1e-3 tolerance - never the default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-eager-baseline", action="store_true", help="skip the torch-eager-on-GPU comparator that fills vs_baseline (cfg2, 1 GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-eager-baseline", action="store_true", help="with --full: skip the torch-eager-on-GPU comparator that fills vs_baseline (cfg2, 1 GPU)")
     ap.add_argument("--no-graphs", action="store_true", help="launch every kernel eagerly instead of replaying a HIP graph")
     ap.add_argument("--no-conv-implicit", action="store_true", help="A/B: the necks' 3 x 3 convolution as im2col + GEMM instead of the implicit GEMM on "
                     "zero-bordered plane-pair maps (LamEngine.conv_implicit, round 6)")
@@ -320,8 +352,17 @@ def main():
                     "the attention epilogue's column sums (LamEngine.win_fused_cs, round 6)")
     ap.add_argument("--no-norm-fold", action="store_true", help="A/B: keep the LayerNorm kernels of the encoder blocks instead of folding them into "
                     "the neighbour GEMMs (LamEngine.norm_fold, round 6)")
-    ap.add_argument("--gemm-shapes", action="store_true", help="print a per-shape breakdown of the GEMM launches to stderr")
+    ap.add_argument("--gemm-shapes", action="store_true", help="with --full: print a per-shape breakdown of the GEMM launches to stderr")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure, after the timed steps: the finiteness check "
+                    "of the last step's logits, the instrumented per-kernel steps (roofline, kernels_ms_per_step, --gemm-shapes) and the "
+                    "torch-eager / CPU baselines (vs_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy "
+                    "(float32 / float64, under 64 MB in all; a larger output as a fixed seeded sample of its elements)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.gemm_shapes and not a.full:
+        ap.error("--gemm-shapes runs in the instrumented step of --full")
     if a.episodes is None:
         a.episodes = WORKLOADS[a.workload]["default_episodes"]
 
@@ -355,6 +396,7 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group(backend)
+    torch.manual_seed(1234 + rank)                   # host draws of the forward (RandomMatrixEncoder rows, cfg3 / cfg5): the same every run
     dtype = torch.float16 if a.dtype == "f16" else torch.bfloat16
     precise = None if a.precise == "default" else (() if a.precise == "none" else tuple(a.precise.split(",")))
     lam, cfg = build_model(dtype, {"f32": torch.float32, "f16x2": "f16x2", "same": None}[a.decoder], a.workload, precise)
@@ -395,12 +437,15 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    assert torch.isfinite(out["logits"][out["logits"] > float("-inf")]).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
+    if a.full:
+        assert torch.isfinite(out["logits"][out["logits"] > float("-inf")]).all()
 
     # instrumented step: per-kernel HIP-event timing (outside the timed region)
     roof = None
     kernels = None
-    if rank == 0:
+    if rank == 0 and a.full:
         if not train:
             lam.use_graphs = False      # per-kernel events need eager launches
         with KernelTimer() as kt:
@@ -487,7 +532,7 @@ def main():
                        "launch": "eager" if (a.no_graphs or train) else "hipGraph replay"},
             "roofline": roof, "kernels_ms_per_step": kernels,
         }
-        if world == 1 and not a.no_eager_baseline and a.workload == "cfg2":
+        if a.full and world == 1 and not a.no_eager_baseline and a.workload == "cfg2":
             # BASELINE.md publishes no number; north_star's target is stated against the reference's eager path on the same GPU
             eb = eager_baseline(cfg, dev)
             line["vs_baseline"] = round(eps / eb["value"], 2)
@@ -495,7 +540,7 @@ def main():
                 line["vs_eager_autocast16"] = round(eps / eb["autocast16"]["value"], 2)
             line["baseline_kind"] = eb["kind"]
             line["eager_baseline"] = eb
-        if world == 1 and not a.no_cpu_baseline and a.workload == "cfg2":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "cfg2":
             line["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(line), flush=True)
     if dist is not None:

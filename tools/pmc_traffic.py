@@ -46,7 +46,7 @@ def main():
     out = {
         "workload": workload, "encoder_split_precision": precise,      # bench.py only attaches this file to a matching run
         "episodes_per_step": episodes,
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --no-graphs --no-cpu-baseline`",
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --no-graphs --no-cpu-baseline`",
         "kernels": names,
         "launches_counted": launches,
         "fetch_kib_per_launch_raw": round(fkib / max(launches, 1), 1),
