@@ -535,6 +535,23 @@ int la_norm_finalize(const float* part, int M, int nslots, int E, float eps, flo
  * (HF ViT: CLS row + patch embedding through a row map). */
 int la_norm_stats(const float* x, int ldx, int M, int E, float eps, void* x16, float* mr, int dt, void* stream);
 
+/* ---- query substitution (experiment/substitution.py:17-97 + data/transforms.py:176-191) ------------------------------------------------
+ * Per pixel p = argmax_c logits (first maximal index), g = gt with ignore_index (and values outside [0, C)) read as 0; a pixel with p != g
+ * is an error of class g (label +1) and of class p (label -1).  Images are cut into tiles of 4096 pixels in raster order; C <= 64,
+ * H * W <= 4096 tiles.
+ * la_error_count: logits fp32 [B, C, H, W], gt int64 [B, H, W] -> counts u32 [B, C, tiles] (error pixels of each class per tile) and,
+ *   when preds != NULL, the argmax int64 [B, H, W].
+ * la_error_points: one wave per (b, c) scans its tile counts and, for each of num_points draws, finds the rank-th error pixel in raster
+ *   (y, x) order - torch.nonzero's.  rank = ranks[b, c, k] (int32, clamped into [0, count)) or, with ranks == NULL,
+ *   min(floor(u[b, c, k] * count), count - 1).  points fp32 [B, C, n, 2] = (x, y), scaled as torch_apply_coords with the original size
+ *   (dims[b * dims_stride], dims[b * dims_stride + 1]) = (h, w) when dims != NULL; labels fp32 [B, C, n] = +1 / -1, 0 for class 0.  A
+ *   (b, c) without errors gets zero points and label 0.  counts must come from la_error_count on the same logits / gt. */
+int la_error_count(const float* logits, const long long* gt, int B, int C, int H, int W, int ignore_index, unsigned* counts,
+                   long long* preds, void* stream);
+int la_error_points(const float* logits, const long long* gt, int B, int C, int H, int W, int ignore_index, const unsigned* counts,
+                    int num_points, const int* ranks, const float* u, const long long* dims, long dims_stride, int long_side,
+                    int custom_preprocess, float* points, float* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

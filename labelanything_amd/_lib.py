@@ -66,6 +66,7 @@ EXPORTS = [
     "la_classify_bwd", "la_row_broadcast", "la_twoway_t2i", "la_twoway_i2t", "la_gemm_variant", "la_attn_fwd_lse", "la_head_transpose", "la_attn_bwd", "la_cast", "la_gelu_bwd16", "la_axpy", "la_transpose16", "la_qk_fp8", "la_attn_fwd_fp8", "la_colmean16", "la_layernorm_g", "la_add_rowvec", "la_add_rowvec_split", "la_attn_fwd_cs", "la_attn_fwd_rows", "la_colsum_fold", "la_gelu_fwd16", "la_gemm_tn_db",
     "la_attn_fwd_relpos_lse", "la_attn_bwd_relpos", "la_relpos_bwd", "la_twoway_pe_layout",
     "la_norm_finalize", "la_norm_stats", "la_conv3x3_split", "la_conv3x3_split_ok",
+    "la_error_count", "la_error_points",
 ]
 
 
@@ -324,6 +325,18 @@ def bilinear(x, n: int, h: int, w: int, oh: int, ow: int, out) -> None:
     _dev(x)
     _check(lib().la_bilinear(_ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(oh), C.c_int(ow), _ptr(out), _stream()),
            "la_bilinear")
+
+
+def error_count(logits, gt, b: int, c: int, h: int, w: int, ignore_index: int, counts, preds=None) -> None:
+    _check(lib().la_error_count(_ptr(logits), _ptr(gt), C.c_int(b), C.c_int(c), C.c_int(h), C.c_int(w), C.c_int(ignore_index), _ptr(counts),
+                                _ptr(preds), _stream()), "la_error_count")
+
+
+def error_points(logits, gt, b: int, c: int, h: int, w: int, ignore_index: int, counts, num_points: int, ranks, u, dims, dims_stride: int,
+                 long_side: int, custom_preprocess: bool, points, labels) -> None:
+    _check(lib().la_error_points(_ptr(logits), _ptr(gt), C.c_int(b), C.c_int(c), C.c_int(h), C.c_int(w), C.c_int(ignore_index), _ptr(counts),
+                                 C.c_int(num_points), _ptr(ranks), _ptr(u), _ptr(dims), C.c_long(dims_stride), C.c_int(long_side),
+                                 C.c_int(1 if custom_preprocess else 0), _ptr(points), _ptr(labels), _stream()), "la_error_points")
 
 
 def post_final(big, b: int, c: int, s: int, sizes_i32, flag_gts_u8, hmax: int, wmax: int, logits, argmax) -> None:

@@ -535,3 +535,60 @@ class LamTrainer:
         res = self.forward_backward(batch, gt, loss_normalizer, sync=True)
         self.apply_update()
         return res
+
+    def embed_batch(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        """The batch with ``images`` [B, N, 3, S, S] replaced by the frozen encoder's ``embeddings`` [B, N, C, g, g] (NCHW, as the
+        reference's encoder returns them), encoded once through the engine.  The embeddings path of ``forward_backward`` feeds the
+        decoder graph the same rows as the images path, so training on the result is bit-identical - and a substitution batch
+        (M+2 steps over the same M+1 images) encodes them once instead of M+2 times.  A batch without ``images`` is returned as is."""
+        if self.train_encoder:
+            raise ValueError("embed_batch needs a frozen encoder: with train_encoder=True every step must run the encoder's forward")
+        if "images" not in batch:
+            return batch
+        lam = self.lam
+        self._sync_version()
+        with torch.cuda.device(lam._device()), torch.no_grad():
+            im = self.engine.h2d(batch["images"], torch.float32)
+            b, n = im.shape[:2]
+            e32, _, c, g = self.engine.encode_images(im.flatten(0, 1))
+            emb = torch.empty(b * n, c, g * g, device=im.device)
+            L.nhwc_to_nchw(e32, b * n, c, g * g, emb)
+        out = {k: v for k, v in batch.items() if k != "images"}
+        out["embeddings"] = emb.view(b, n, c, g, g)
+        return out
+
+    def substitution_steps(self, batch: Dict[str, Any], gts: Tensor, substitutor, accumulate: bool = False,
+                           loss_normalizer: Optional[float] = None):
+        """One batch of ``Run.train_epoch`` with query substitution (experiment/run.py:500-560): ``substitutor.reset((batch, gts))``,
+        then for every substitution step a training step and ``substitutor.generate_new_points(logits, gt)``.  batch / gts: the
+        dataset's layout (prompts for all M+1 images, ground truths [B, M+1, H, W]).
+        accumulate=False (the canonical configs): ``step`` per substitution step.  accumulate=True (``accumulate_substitution``):
+        ``forward_backward`` on every step, synchronising on the last, then one ``apply_update``.  loss_normalizer defaults to M+2
+        with accumulate=True and 1 otherwise, as run.py:503-507 computes it.
+        Yields per step a dict: ``step``, ``input`` (the model input), ``gt`` (query ground truth), ``preds`` (argmax of the logits,
+        int64 [B, H, W]) and the step's ``loss`` / ``logits`` / ``class_examples_embeddings``.
+        The batch's tensors and ``gts`` are moved to the model's device first, so that the rotations and the growing point prompts stay
+        there: with a host batch every step would copy its new points back (a host sync).  The model step's own prompt-type
+        decisions on device flags (``Lam._prepare``) read a few flags on the host, as the reference's forward does."""
+        dev = self.lam._device()
+        batch = {k: (v.to(dev, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        gts = gts.to(dev, non_blocking=True)
+        substitutor.reset(batch=(batch, gts))
+        n_steps = substitutor.num_steps
+        if loss_normalizer is None:
+            loss_normalizer = float(gts.shape[1] + 1) if accumulate else 1.0
+        if accumulate:
+            self.zero_grad()
+        for i, (inp, gt) in enumerate(substitutor):
+            last = i == n_steps - 1
+            if accumulate:
+                res = self.forward_backward(inp, gt, loss_normalizer, sync=last)
+                if last:
+                    self.apply_update()
+            else:
+                res = self.step(inp, gt, loss_normalizer)
+            logits = res["logits"]
+            preds = torch.empty(logits.shape[0], *logits.shape[2:], dtype=torch.int64, device=logits.device)
+            with torch.cuda.device(logits.device):
+                substitutor.generate_new_points(logits, gt.to(logits.device), preds_out=preds)
+            yield {"step": i, "input": inp, "gt": gt, "preds": preds, **res}
