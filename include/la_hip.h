@@ -296,6 +296,27 @@ int la_focal_loss(const float* logits, const long long* target, int B, int C, lo
                   long long ignore_index, float* loss, float* dlogits, float* class_weights, void* scratch, long scratch_bytes,
                   void* stream);
 
+/* Logits objective of LabelAnythingLoss: focal, dice and false positive, any subset (mask bits 1 focal, 2 dice, 4 fp), fused with
+ * the gradient (loss/__init__.py:67-89, loss/focal.py:17-26, loss/dice.py:54-113 with average "macro" / reduction "mean",
+ * loss/fp.py:10-34, loss/utils.py:17-43).  logits fp32 [B, C, HW] (C <= 64, -inf padding allowed), target int64 [B, HW].
+ * Each component k enters value fp32 [1] as w_k^2 L_k and components fp32 [3] (focal, dice, fp; 0 when off) as w_k L_k.
+ * dlogits fp32 [B, C, HW] = d value / d logits, or NULL.  class_weights fp32 [C] or NULL: the batch's weights (focal and dice).
+ * workspace: la_logits_objective_workspace_bytes; its first B * (C + 2) 64-bit words are the per-image label histogram (word
+ * b * (C + 2) + C + 1 counts targets outside [0, C) other than ignore_index: they contribute nothing).  No host synchronisation. */
+int la_logits_objective_workspace_bytes(int B, int C, long HW, long* bytes);
+int la_logits_objective(const float* logits, const long long* target, int B, int C, long HW, long long ignore_index, int mask,
+                        float w_focal, float gamma, float w_dice, float w_fp, int class_weighting, float* value, float* components,
+                        float* dlogits, float* class_weights, void* workspace, long workspace_bytes, void* stream);
+
+/* PromptContrastiveLoss (loss/prompt.py:10-48): emb fp32 [B, n, D] (class_examples_embeddings [B, M, C, D], n = M * C rows in (m, c)
+ * order, n <= 1024, D <= 1024), flags uint8 [B, n] (flag_examples).  t_prime, bias: device fp32 [1] (the loss's parameters, read on
+ * the device).  loss fp32 [1] = sum over images and flagged pairs i < j of softplus(-y_ij z_ij) / (valid_b * B) with
+ * z = normalize(e_i) . normalize(e_j) * exp(t') + bias, y = +1 for the same class index, -1 otherwise; demb fp32 [B, n, D],
+ * dt_prime, dbias fp32 [1] (or NULL): its gradients.  workspace: la_prompt_contrastive_workspace_bytes. */
+int la_prompt_contrastive_workspace_bytes(int B, int n, int D, long* bytes);
+int la_prompt_contrastive(const float* emb, const unsigned char* flags, int B, int n, int C, int D, const float* t_prime, const float* bias,
+                          float* loss, float* demb, float* dt_prime, float* dbias, void* workspace, long workspace_bytes, void* stream);
+
 /* One torch.optim.AdamW step on flat fp32 buffers of n elements (experiment/utils.py:53-76; decoupled weight decay, bias
  * correction with the 1-based `step`), gradients scaled by grad_scale first (1 / world size after the data-parallel SUM
  * all-reduce). */

@@ -67,6 +67,7 @@ EXPORTS = [
     "la_attn_fwd_relpos_lse", "la_attn_bwd_relpos", "la_relpos_bwd", "la_twoway_pe_layout",
     "la_norm_finalize", "la_norm_stats", "la_conv3x3_split", "la_conv3x3_split_ok",
     "la_error_count", "la_error_points",
+    "la_logits_objective_workspace_bytes", "la_logits_objective", "la_prompt_contrastive_workspace_bytes", "la_prompt_contrastive",
 ]
 
 
@@ -383,6 +384,37 @@ def focal_loss(logits, target_i64, gamma: float, class_weighting: bool, scale: f
     _check(lib().la_focal_loss(_ptr(logits), _ptr(target_i64), C.c_int(b), C.c_int(c), C.c_long(hw), C.c_float(gamma), C.c_int(int(class_weighting)),
                                C.c_float(scale), C.c_longlong(ignore_index), _ptr(loss), _ptr(dlogits), _ptr(class_weights), _ptr(scratch),
                                C.c_long(scratch.numel() * scratch.element_size()), _stream()), "la_focal_loss")
+
+
+def logits_objective_workspace_bytes(b: int, c: int, hw: int) -> int:
+    n = C.c_long(0)
+    _check(lib().la_logits_objective_workspace_bytes(C.c_int(b), C.c_int(c), C.c_long(hw), C.byref(n)), "la_logits_objective_workspace_bytes")
+    return int(n.value)
+
+
+def logits_objective(logits, target_i64, ignore_index: int, mask: int, w_focal: float, gamma: float, w_dice: float, w_fp: float,
+                     class_weighting: bool, value, components, dlogits, class_weights, workspace) -> None:
+    _dev(logits)
+    b, c = logits.shape[0], logits.shape[1]
+    hw = logits.numel() // (b * c)
+    _check(lib().la_logits_objective(_ptr(logits), _ptr(target_i64), C.c_int(b), C.c_int(c), C.c_long(hw), C.c_longlong(ignore_index),
+                                     C.c_int(mask), C.c_float(w_focal), C.c_float(gamma), C.c_float(w_dice), C.c_float(w_fp),
+                                     C.c_int(int(class_weighting)), _ptr(value), _ptr(components), _ptr(dlogits), _ptr(class_weights),
+                                     _ptr(workspace), C.c_long(workspace.numel() * workspace.element_size()), _stream()), "la_logits_objective")
+
+
+def prompt_contrastive_workspace_bytes(b: int, n: int, d: int) -> int:
+    k = C.c_long(0)
+    _check(lib().la_prompt_contrastive_workspace_bytes(C.c_int(b), C.c_int(n), C.c_int(d), C.byref(k)), "la_prompt_contrastive_workspace_bytes")
+    return int(k.value)
+
+
+def prompt_contrastive(emb, flags_u8, c: int, t_prime, bias, loss, demb, dt_prime, dbias, workspace) -> None:
+    _dev(emb)
+    b, n, d = emb.shape
+    _check(lib().la_prompt_contrastive(_ptr(emb), _ptr(flags_u8), C.c_int(b), C.c_int(n), C.c_int(c), C.c_int(d), _ptr(t_prime), _ptr(bias),
+                                       _ptr(loss), _ptr(demb), _ptr(dt_prime), _ptr(dbias), _ptr(workspace),
+                                       C.c_long(workspace.numel() * workspace.element_size()), _stream()), "la_prompt_contrastive")
 
 
 def adamw_step(params, grads, exp_avg, exp_avg_sq, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,

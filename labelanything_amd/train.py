@@ -24,7 +24,7 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import autograd_ops as A
-from .loss import FocalLossDevice
+from .loss import FocalLossDevice, LabelAnythingLoss
 from .models import Lam
 from .optim import FlatAdamW
 from .parallel import any_over_ranks
@@ -45,6 +45,18 @@ class _FocalObjective(Function):
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
         return dl * g, None, None
+
+
+def _objective(crit, out: Dict[str, Tensor], gt: Tensor, inp: Dict[str, Tensor]) -> Tuple[Tensor, Dict[str, Tensor]]:
+    """The step's loss and its reported components: FocalLossDevice, or LabelAnythingLoss on the decoder graph's logits and
+    class-example embeddings (prompt_contrastive's gradient flows back through the class / example attention blocks into the prompt
+    encoder) with the batch's flag_examples, as compose_loss_input hands them to the reference's loss (experiment/utils.py:114)."""
+    if isinstance(crit, LabelAnythingLoss):
+        res = crit({"logits": out["logits"], "class_examples_embeddings": out["class_examples_embeddings"],
+                    "flag_examples": inp["flag_examples"]}, gt)
+        return res["value"], {k: v.detach() for k, v in res["components"].items()}
+    loss = _FocalObjective.apply(out["logits"], gt, crit)
+    return loss, {"focal": loss.detach()}
 
 
 class _PointEmbed(Function):
@@ -335,7 +347,7 @@ class LamTrainer:
     ``Lam.get_learnable_params({'freeze_backbone': True})``."""
 
     def __init__(self, lam: Lam, lr: float = 5e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
-                 num_warmup_steps: int = 0, loss: Optional[FocalLossDevice] = None, train_encoder: bool = False,
+                 num_warmup_steps: int = 0, loss=None, train_encoder: bool = False,
                  backbone_lr: Optional[float] = None, encoder_buckets: int = 4):
         """backbone_lr: learning rate of the ``image_encoder.*`` tensors (the reference's ``backbone_lr`` parameter group,
         models/lam.py:340-346; needs train_encoder=True - with a frozen backbone the reference raises as well).
@@ -344,7 +356,10 @@ class LamTrainer:
         pieces, each followed by its AdamW launch (``parallel.BucketedGradReducer``); the decoder-side gradients (40 MB) are one more
         bucket, launched from inside the backward pass - they are final when the encoder backward starts.
         train_encoder=True: every parameter trains, as with parameters/trainval/coco20i/mae_noembs.yaml (no
-        ``freeze_backbone``: models/lam.py:347 returns ``self.parameters()``); needs an HF ViT encoder (train_encoder.py)."""
+        ``freeze_backbone``: models/lam.py:347 returns ``self.parameters()``); needs an HF ViT encoder (train_encoder.py).
+        loss: ``FocalLossDevice`` (default: focal, weight 1, class weighting) or a ``loss.LabelAnythingLoss``; the latter is moved to the
+        model's device and its parameters (prompt_contrastive's t_prime / bias) train with the decoder's learning rate and weight
+        decay, as ``WrapperModule.get_learnable_params`` appends them to the optimizer (experiment/utils.py:290-295)."""
         if float(getattr(lam.cfg, "dropout", 0.0) or 0.0) != 0.0:
             # the reference trains with nn.Dropout(p) inside MLPBlock / AttentionMLPBlock when it is set (models/common.py:25-32,68-75,
             # build_lam.py:128); the training graph here has no dropout node, so training such a model would silently be a different model
@@ -368,7 +383,15 @@ class LamTrainer:
         # tensors the forward never reaches (dead in the reference too, prompt_encoder.py:683) go to the tail of the flat buffer so
         # that the per-step "received a gradient" spans of FlatAdamW.step stay one contiguous run
         dead = ("prompt_encoder.transformer.final_attn_token_to_image.", "prompt_encoder.transformer.norm_final_attn.")
-        named = [kp for kp in named if not kp[0].startswith(dead)] + [kp for kp in named if kp[0].startswith(dead)]
+        if isinstance(loss, LabelAnythingLoss):
+            loss.to(lam._device())
+            loss_named = [("loss." + k, p) for k, p in loss.named_parameters()]
+        elif loss is None or isinstance(loss, FocalLossDevice):
+            loss_named = []
+        else:
+            raise TypeError(f"loss must be a FocalLossDevice or a LabelAnythingLoss, got {type(loss).__name__}")
+        # the loss's parameters sit between the live decoder tensors and the dead tail: in the decoder bucket, inside the active span
+        named = ([kp for kp in named if not kp[0].startswith(dead)] + loss_named + [kp for kp in named if kp[0].startswith(dead)])
         for _, p in lam.named_parameters():
             p.requires_grad_(False)
         for _, p in named:
@@ -491,13 +514,14 @@ class LamTrainer:
                 # gradient that does arrive later invalidates it and the bucket is reduced in place at the end)
                 self.enc_graph.before_backward = (lambda: self.reducer.launch(self._dec_bucket, staged=True)) if sync else None
             out = self.graph.forward(e_rows, b, n, g, inp, batch["dims"], neck_input=True)
-            loss = _FocalObjective.apply(out["logits"], gt.to(lam._device()), self.crit)
+            loss, components = _objective(self.crit, out, gt.to(lam._device()), inp)
             (loss / loss_normalizer).backward()
             if sync:                                  # everything is final now: the remaining buckets leave in buffer order
                 for i in range(len(self.reducer.bounds)):
                     if not self.reducer.launched(i):
                         self.reducer.launch(i)
-        return {"loss": loss.detach(), "logits": out["logits"].detach(), "class_examples_embeddings": out["class_examples_embeddings"].detach()}
+        return {"loss": loss.detach(), "loss_components": components, "logits": out["logits"].detach(),
+                "class_examples_embeddings": out["class_examples_embeddings"].detach()}
 
     def zero_grad(self) -> None:
         self.opt.zero_grad()
@@ -566,7 +590,7 @@ class LamTrainer:
         ``forward_backward`` on every step, synchronising on the last, then one ``apply_update``.  loss_normalizer defaults to M+2
         with accumulate=True and 1 otherwise, as run.py:503-507 computes it.
         Yields per step a dict: ``step``, ``input`` (the model input), ``gt`` (query ground truth), ``preds`` (argmax of the logits,
-        int64 [B, H, W]) and the step's ``loss`` / ``logits`` / ``class_examples_embeddings``.
+        int64 [B, H, W]) and the step's ``loss`` / ``loss_components`` / ``logits`` / ``class_examples_embeddings``.
         The batch's tensors and ``gts`` are moved to the model's device first, so that the rotations and the growing point prompts stay
         there: with a host batch every step would copy its new points back (a host sync).  The model step's own prompt-type
         decisions on device flags (``Lam._prepare``) read a few flags on the host, as the reference's forward does."""
