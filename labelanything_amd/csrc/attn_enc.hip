@@ -261,6 +261,13 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
   long qrow = (long)b * T_ + qc;                       // row of this lane's query in qkv / out
   if (img_order) qrow = img_row(qy5, qx5);
   const T* padrow = reinterpret_cast<const T*>(a.padrow);
+  // A query block that starts in a window row beyond the image holds padded queries only (the second block of a bottom-edge window: a
+  // 64-row grid leaves G = 14 windows 8 rows = 112 queries).  A padded KEY is needed, a padded QUERY is not: nothing of the block is
+  // stored and its column sums are zeros, so the workgroup is done before its first load (5 of an image-head's 50 on the SAM grid).
+  if (img_order && a.lse == nullptr && wy0 + udiv_magic(qblk * 128, a.G, a.mg_G) >= a.imgH) {
+    if (a.cspart != nullptr && tid < HDT) a.cspart[((size_t)b * ((T_ + 127) / 128) + qblk) * a.E + h * HDT + tid] = 0.f;
+    return;
+  }
 
   // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[q][ks*16 + fh*8 .. +8] -----------------
   uint4 qf[KS];

@@ -2129,6 +2129,9 @@ extern "C" int la_gemm(const void* A, int lda, const void* W, int ldw, int M, in
                        void* stream) {
   LA_CHECK_ARG(A && W && epi, "la_gemm: null pointer");
   LA_CHECK_ARG(M > 0 && N > 0 && K > 0, "la_gemm: bad shape M=%d N=%d K=%d", M, N, K);
+  // (the four-wave epilogue reaches the 128 rows of a wave's block with 32-bit byte offsets from the tile's base: 128 x ld x 4 B < 2^31)
+  LA_CHECK_ARG(epi->ld16 < (1 << 22) && epi->ldaux < (1 << 22) && epi->ld32 < (1 << 22) && epi->ldr < (1 << 22) && N < (1 << 22),
+               "la_gemm: output / residual leading dimensions must be below %d elements", 1 << 22);
   const int kq = (dt == LA_F32) ? 4 : 8;
   LA_CHECK_ARG((K % kq) == 0 && (lda % kq) == 0 && (ldw % kq) == 0, "la_gemm: K, lda, ldw must be multiples of %d (K=%d lda=%d ldw=%d)", kq, K,
                lda, ldw);

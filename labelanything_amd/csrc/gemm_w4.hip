@@ -73,6 +73,20 @@ constexpr int LA_W4_NSTAMP = 128;
 __device__ unsigned long long g_w4_stamps[4 * LA_W4_NSTAMP];      // [wave][i] = s_memtime << 8 | tag (workgroup 0 of the last stamped launch)
 #endif
 
+// global memory at an address formed as an integer (a wave-uniform base + a 32-bit lane offset): the address space is stated, a generic
+// pointer would make these flat accesses, which count on lgkmcnt as well
+template <int BYTES> struct GWords;      // (the HIP vector classes have no members for a qualified address space: moved as native vectors)
+template <> struct GWords<16> { typedef unsigned type __attribute__((ext_vector_type(4))); };
+template <> struct GWords<8> { typedef unsigned type __attribute__((ext_vector_type(2))); };
+template <typename V> __device__ __forceinline__ V gld(uintptr_t a) {
+  typedef typename GWords<sizeof(V)>::type W;
+  return __builtin_bit_cast(V, *reinterpret_cast<const __attribute__((address_space(1))) W*>(a));
+}
+template <typename V> __device__ __forceinline__ void gst(uintptr_t a, const V& v) {
+  typedef typename GWords<sizeof(V)>::type W;
+  *reinterpret_cast<__attribute__((address_space(1))) W*>(a) = __builtin_bit_cast(W, v);
+}
+
 template <int N> __device__ __forceinline__ void wait_vm_lgkm0() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 
 // ---- the k-tile body is written out slot by slot: one MFMA, at most one memory instruction, pinned by sched_barrier(0) ----------------
@@ -112,8 +126,18 @@ template <int N> __device__ __forceinline__ void wait_vm_lgkm0() { asm volatile(
 //   write: lane (fr, fh), register quad g of tile jj -> q = 2 g + fh, c = 32 jj + fr          (8 stores per round, conflict-free)
 //   read:  lane -> q = lane >> 3, column group cg = lane & 7: columns 8 cg + t, t = 0..7      (8 loads per round, conflict-free)
 // The LDS queue of a wave is in order: round r + 1 is written right behind the read instructions of round r.
-template <typename T, int EPI>
+// RAGGED: the tile reaches beyond row M (the last row tile of an M % 256 != 0 call): every row's loads and stores are predicated.  The
+// interior form has no row predicate at all - on a wave that is alone on its SIMD each predicated row is a basic block of its own
+// (zero fill, saveexec, branch, exec restore), and the loads of a round can neither be clustered nor hoisted across them.
+// Addresses: one wave-uniform 64-bit base per matrix and tile (an SGPR pair) + ONE 32-bit byte offset per lane and matrix; the rows of a
+// round add the uniform row stride to it and the column half is a constant - no 64-bit multiply-add per access.
+template <typename T, int EPI, bool RAGGED>
 __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], int row0, int col0, const LaGemmEpilogue& e, int lane, int M, int N) {
+  row0 = __builtin_amdgcn_readfirstlane(row0);
+  col0 = __builtin_amdgcn_readfirstlane(col0);
+  // (everything derived from the lane is a tile-loop invariant that hipcc would hoist into the main loop's registers and then spill: an
+  // opaque copy keeps it local to the epilogue, ~40 instructions per tile)
+  asm volatile("" : "+v"(lane));
   const int fr = lane & 31, fh = lane >> 5;
   const int rq = lane >> 3, cg = lane & 7;
   const unsigned sl = lds_addr_of(slab);
@@ -176,9 +200,9 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
     mrv[i & 1][0] = mrv[i & 1][1] = make_float4(0.f, 1.f, 0.f, 1.f);
     return;
 #endif
-    const float4* mp = reinterpret_cast<const float4*>(e.nstat_in + (size_t)(row0 + i * 32 + rq * 4) * 2);
-    mrv[i & 1][0] = mp[0];
-    mrv[i & 1][1] = mp[1];
+    const uintptr_t mp = reinterpret_cast<uintptr_t>(e.nstat_in + (size_t)(row0 + i * 32) * 2) + (size_t)(unsigned)(rq * 32);
+    mrv[i & 1][0] = gld<float4>(mp);
+    mrv[i & 1][1] = gld<float4>(mp + 16);
   };
   if (NORM) {
     ldmr(0);
@@ -208,23 +232,49 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
   // EPI 3: the residual rows of round (i, jp) - requested RING rounds ahead of their use (HBM round trips, nothing else to hide them)
   // (res_mod: the residual repeats every res_mod rows; the host sends such a call here only when res_mod % 256 == 0 - a tile is inside one period)
   const int rrow0 = e.res_mod > 0 ? row0 % e.res_mod : row0;
+  // (p, ld, es: matrix, leading dimension, element size) -> the tile's uniform base at row r0 / the lane's byte offset inside the wave's block
+  auto tbase = [&](const void* p, int r0, int ld, int es) { return reinterpret_cast<uintptr_t>(p) + ((size_t)r0 * ld + col0) * es; };
+  auto loff = [&](int ld, int es) { return (unsigned)((rq * 4 * ld + cg * 8) * es); };
+  // row r (0 .. 127, uniform) of the wave's block + cb constant bytes (the column half): the row stride joins the SCALAR base, the lane's
+  // offset stays one register for all rows of the tile.  RAGGED keeps the per-lane 64-bit form (r0: the block's first row in the matrix).
+  auto addr = [&](const void* p, uintptr_t base, unsigned lo, int r0, int r, int ld, int es, int cb) {
+    if constexpr (RAGGED) return reinterpret_cast<uintptr_t>(p) + ((size_t)(r0 + rq * 4 + r) * ld + col0 + cg * 8) * es + cb;
+    else return (base + (size_t)(unsigned)(r * ld * es)) + (size_t)lo + cb;
+  };
+  const uintptr_t b16 = tbase(e.out16, row0, e.ld16, 2), bax = tbase(e.aux16, row0, e.ldaux, 2), b32 = tbase(e.out32, row0, e.ld32, 4);
+  const uintptr_t br16 = tbase(e.out16, rrow0, e.ld16, 2), brax = tbase(e.aux16, rrow0, e.ldaux, 2), brs = tbase(e.res, rrow0, e.ldr, 4);
+  const unsigned l16 = loff(e.ld16, 2), lax = loff(e.ldaux, 2), l32 = loff(e.ld32, 4), lrs = loff(e.ldr, 4);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   auto ldres = [&](int i, int jp, float4 (&res)[4][2]) {
-    const int row = rrow0 + i * 32 + rq * 4, col = col0 + jp * 64 + cg * 8;
     if constexpr (RESP) {      // res[s][0] = the 8 hi halves, res[s][1] = the 8 lo halves of the row segment (16 bytes each, as raw bits)
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_) {
-        const bool ok = row0 + i * 32 + rq * 4 + s_ < M;
-        res[s_][0] = ok ? *reinterpret_cast<const float4*>(reinterpret_cast<const T*>(e.out16) + (size_t)(row + s_) * e.ld16 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        res[s_][1] = ok ? *reinterpret_cast<const float4*>(reinterpret_cast<const T*>(e.aux16) + (size_t)(row + s_) * e.ldaux + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const uintptr_t ph = addr(e.out16, br16, l16, rrow0, i * 32 + s_, e.ld16, 2, jp * 128);
+        const uintptr_t pl = addr(e.aux16, brax, lax, rrow0, i * 32 + s_, e.ldaux, 2, jp * 128);
+        if constexpr (RAGGED) {
+          const bool ok = row0 + i * 32 + rq * 4 + s_ < M;
+          res[s_][0] = ok ? gld<float4>(ph) : zero4;
+          res[s_][1] = ok ? gld<float4>(pl) : zero4;
+        } else {
+          res[s_][0] = gld<float4>(ph);
+          res[s_][1] = gld<float4>(pl);
+        }
       }
+      return;
+    }
+    if (!e.res) {
+#pragma unroll
+      for (int s_ = 0; s_ < 4; ++s_) res[s_][0] = res[s_][1] = zero4;
       return;
     }
 #pragma unroll
     for (int s_ = 0; s_ < 4; ++s_)
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        res[s_][h] = (e.res && row0 + i * 32 + rq * 4 + s_ < M) ? *reinterpret_cast<const float4*>(e.res + (size_t)(row + s_) * e.ldr + col + 4 * h)
-                                                                  : make_float4(0.f, 0.f, 0.f, 0.f);      // (rows beyond M: the last, ragged row tile)
+      for (int h = 0; h < 2; ++h) {
+        const uintptr_t pr = addr(e.res, brs, lrs, rrow0, i * 32 + s_, e.ldr, 4, jp * 256 + 16 * h);
+        if constexpr (RAGGED) res[s_][h] = row0 + i * 32 + rq * 4 + s_ < M ? gld<float4>(pr) : zero4;      // (rows beyond M: the last, ragged row tile)
+        else res[s_][h] = gld<float4>(pr);
+      }
   };
   // EPI 5 / 6 (training): aux16 = a second 16-bit matrix of the output's shape.  5: the pre-activation (bias added, before the GELU) is
   // written there beside out16 = GELU - the forward that keeps what gelu' needs.  6: it is READ - out16 = acc * gelu'(aux16), the data
@@ -232,14 +282,82 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
   // its row segments are requested a round ahead like the residual's
   T* aux16 = reinterpret_cast<T*>(e.aux16);
   auto ldaux = [&](int i, int jp, uint4 (&ax)[4]) {
-    const int row = row0 + i * 32 + rq * 4, col = col0 + jp * 64 + cg * 8;
+    const int row = row0 + i * 32 + rq * 4;
 #pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_)
-      ax[s_] = row + s_ < M ? *reinterpret_cast<const uint4*>(aux16 + (size_t)(row + s_) * e.ldaux + col) : make_uint4(0u, 0u, 0u, 0u);
+    for (int s_ = 0; s_ < 4; ++s_) {
+      const uintptr_t pa = addr(e.aux16, bax, lax, row0, i * 32 + s_, e.ldaux, 2, jp * 128);
+      if constexpr (RAGGED) ax[s_] = row + s_ < M ? gld<uint4>(pa) : make_uint4(0u, 0u, 0u, 0u);
+      else ax[s_] = gld<uint4>(pa);
+    }
   };
+  const uintptr_t bns = PROD ? reinterpret_cast<uintptr_t>(e.nstat_out) + ((size_t)row0 * nslots + (col0 >> 6)) * 8 : 0;
+  const unsigned lns = (unsigned)(rq * 4 * nslots * 8);
   auto out = [&](int i, int jp, const f32x4 (&r)[8], const float4 (&res)[4][2], const uint4 (&ax)[4]) {
-    const int row = row0 + i * 32 + rq * 4, col = col0 + jp * 64 + cg * 8;
+    const int row = row0 + i * 32 + rq * 4;
     if (RES) {
+      if constexpr (RESP && !TWOG && !RAGGED) {
+        // the plane-pair producer on ROW PAIRS (2 sp, 2 sp + 1) of one column, as the consumer side does: the slab hands a lane four rows
+        // of a column in adjacent registers = packed-fp32 operands.  Every value comes from the same operations in the same order as in
+        // the row-by-row form below (which the ragged instance keeps): r + bias + (hi + lo); the in-lane trees of the sums; x^2 + y^2 as
+        // rn(x x) + rn(y y), never contracted; the DPP folds; clamp; hi, lo = rn(x - hi).
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+          const int s0 = 2 * sp, s1 = 2 * sp + 1;
+          const uint32_t h0[4] = {__builtin_bit_cast(uint32_t, res[s0][0].x), __builtin_bit_cast(uint32_t, res[s0][0].y),
+                                  __builtin_bit_cast(uint32_t, res[s0][0].z), __builtin_bit_cast(uint32_t, res[s0][0].w)};
+          const uint32_t h1[4] = {__builtin_bit_cast(uint32_t, res[s1][0].x), __builtin_bit_cast(uint32_t, res[s1][0].y),
+                                  __builtin_bit_cast(uint32_t, res[s1][0].z), __builtin_bit_cast(uint32_t, res[s1][0].w)};
+          const uint32_t l0[4] = {__builtin_bit_cast(uint32_t, res[s0][1].x), __builtin_bit_cast(uint32_t, res[s0][1].y),
+                                  __builtin_bit_cast(uint32_t, res[s0][1].z), __builtin_bit_cast(uint32_t, res[s0][1].w)};
+          const uint32_t l1[4] = {__builtin_bit_cast(uint32_t, res[s1][1].x), __builtin_bit_cast(uint32_t, res[s1][1].y),
+                                  __builtin_bit_cast(uint32_t, res[s1][1].z), __builtin_bit_cast(uint32_t, res[s1][1].w)};
+          f32x2 c[8];
+#pragma unroll
+          for (int t = 0; t < 8; ++t) {
+            const f32x2 hv = (t & 1) ? f32x2{unpack_hi<T>(h0[t >> 1]), unpack_hi<T>(h1[t >> 1])} : f32x2{unpack_lo<T>(h0[t >> 1]), unpack_lo<T>(h1[t >> 1])};
+            const f32x2 lv = (t & 1) ? f32x2{unpack_hi<T>(l0[t >> 1]), unpack_hi<T>(l1[t >> 1])} : f32x2{unpack_lo<T>(l0[t >> 1]), unpack_lo<T>(l1[t >> 1])};
+            c[t] = f32x2{r[t][s0], r[t][s1]} + f32x2{bias[jp][t], bias[jp][t]} + (hv + lv);
+          }
+          const f32x2 a2 = ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
+          f32x2 b2;
+          {
+#pragma clang fp contract(off)      // (squares and sums are separate roundings in every form of this epilogue)
+            b2 = ((c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3])) + ((c[4] * c[4] + c[5] * c[5]) + (c[6] * c[6] + c[7] * c[7]));
+          }
+          float a[2] = {a2.x, a2.y}, b[2] = {b2.x, b2.y};
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            a[hh] += dpp_mov<0xB1>(a[hh]); b[hh] += dpp_mov<0xB1>(b[hh]);
+            a[hh] += dpp_mov<0x4E>(a[hh]); b[hh] += dpp_mov<0x4E>(b[hh]);
+            a[hh] += dpp_mov<0x141>(a[hh]); b[hh] += dpp_mov<0x141>(b[hh]);
+            if (cg == 0) gst((bns + (size_t)(unsigned)((i * 32 + s0 + hh) * nslots * 8)) + (size_t)lns + jp * 8, make_float2(a[hh], b[hh]));
+          }
+          constexpr float HMAX = 65504.0f;
+#pragma unroll
+          for (int t = 0; t < 8; ++t) c[t] = f32x2{__builtin_amdgcn_fmed3f(c[t].x, -HMAX, HMAX), __builtin_amdgcn_fmed3f(c[t].y, -HMAX, HMAX)};
+          uint32_t pk[2][4];
+#pragma unroll
+          for (int w_ = 0; w_ < 4; ++w_) {
+            pk[0][w_] = pack2<T>(c[2 * w_].x, c[2 * w_ + 1].x);
+            pk[1][w_] = pack2<T>(c[2 * w_].y, c[2 * w_ + 1].y);
+          }
+          gst(addr(e.out16, b16, l16, row0, i * 32 + s0, e.ld16, 2, jp * 128), make_uint4(pk[0][0], pk[0][1], pk[0][2], pk[0][3]));
+          gst(addr(e.out16, b16, l16, row0, i * 32 + s1, e.ld16, 2, jp * 128), make_uint4(pk[1][0], pk[1][1], pk[1][2], pk[1][3]));
+          if (aux16) {
+            uint32_t lo[2][4];
+#pragma unroll
+            for (int w_ = 0; w_ < 4; ++w_) {
+              const f32x2 d0 = c[2 * w_] - f32x2{unpack_lo<T>(pk[0][w_]), unpack_lo<T>(pk[1][w_])};
+              const f32x2 d1 = c[2 * w_ + 1] - f32x2{unpack_hi<T>(pk[0][w_]), unpack_hi<T>(pk[1][w_])};
+              lo[0][w_] = pack2<T>(d0.x, d1.x);
+              lo[1][w_] = pack2<T>(d0.y, d1.y);
+            }
+            gst(addr(e.aux16, bax, lax, row0, i * 32 + s0, e.ldaux, 2, jp * 128), make_uint4(lo[0][0], lo[0][1], lo[0][2], lo[0][3]));
+            gst(addr(e.aux16, bax, lax, row0, i * 32 + s1, e.ldaux, 2, jp * 128), make_uint4(lo[1][0], lo[1][1], lo[1][2], lo[1][3]));
+          }
+        }
+        return;
+      }
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_) {
         float4 o0, o1;
@@ -273,17 +391,24 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
         }
         if (PROD) {      // sum x, sum x^2 over the round's 64 columns of this row: the 8 lanes of a row quad folded by DPP, lane cg == 0 stores
           float a = ((o0.x + o0.y) + (o0.z + o0.w)) + ((o1.x + o1.y) + (o1.z + o1.w));
-          float b = ((o0.x * o0.x + o0.y * o0.y) + (o0.z * o0.z + o0.w * o0.w)) + ((o1.x * o1.x + o1.y * o1.y) + (o1.z * o1.z + o1.w * o1.w));
+          float b;
+          {
+#pragma clang fp contract(off)      // (whether hipcc fuses x x + y y depends on how it packs the surrounding code: pinned, as it always came out)
+            b = ((o0.x * o0.x + o0.y * o0.y) + (o0.z * o0.z + o0.w * o0.w)) + ((o1.x * o1.x + o1.y * o1.y) + (o1.z * o1.z + o1.w * o1.w));
+          }
           a += dpp_mov<0xB1>(a); b += dpp_mov<0xB1>(b);         // quad_perm [1,0,3,2]
           a += dpp_mov<0x4E>(a); b += dpp_mov<0x4E>(b);         // quad_perm [2,3,0,1]
           a += dpp_mov<0x141>(a); b += dpp_mov<0x141>(b);       // row_half_mirror: the other quad of the 8-lane group
-          if (cg == 0 && row + s_ < M) *reinterpret_cast<float2*>(e.nstat_out + ((size_t)(row + s_) * nslots + (col >> 6)) * 2) = make_float2(a, b);
+          if (cg == 0 && (!RAGGED || row + s_ < M))
+            gst(RAGGED ? reinterpret_cast<uintptr_t>(e.nstat_out + ((size_t)(row + s_) * nslots + (col0 >> 6) + jp) * 2)
+                       : (bns + (size_t)(unsigned)((i * 32 + s_) * nslots * 8)) + (size_t)lns + jp * 8,
+                make_float2(a, b));
         }
-        if (row + s_ >= M) continue;
+        if (RAGGED && row + s_ >= M) continue;
         if (!RESP && (!PROD || e.out32 != nullptr)) {      // (a producer that leaves plane pairs may skip the fp32 matrix: the patch embedding)
-          float* op = e.out32 + (size_t)(row + s_) * e.ld32 + col;
-          *reinterpret_cast<float4*>(op) = o0;
-          *reinterpret_cast<float4*>(op + 4) = o1;
+          const uintptr_t op = addr(e.out32, b32, l32, row0, i * 32 + s_, e.ld32, 4, jp * 256);
+          gst(op, o0);
+          gst(op + 16, o1);
         }
         if (PROD) {
           // the 16-bit copy is an MFMA operand of the next GEMM: it SATURATES at the fp16 range instead of turning into inf (an un-normalised
@@ -295,17 +420,17 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
           for (int t = 0; t < 8; ++t) c[t] = __builtin_amdgcn_fmed3f(c[t], -HMAX, HMAX);
           uint4 pk;
           pk.x = pack2<T>(c[0], c[1]); pk.y = pack2<T>(c[2], c[3]); pk.z = pack2<T>(c[4], c[5]); pk.w = pack2<T>(c[6], c[7]);
-          *reinterpret_cast<uint4*>(out16 + (size_t)(row + s_) * e.ld16 + col) = pk;
+          gst(addr(e.out16, b16, l16, row0, i * 32 + s_, e.ld16, 2, jp * 128), pk);
           if (aux16) {
             uint4 lo;
             lo.x = pack2<T>(c[0] - unpack_lo<T>(pk.x), c[1] - unpack_hi<T>(pk.x)); lo.y = pack2<T>(c[2] - unpack_lo<T>(pk.y), c[3] - unpack_hi<T>(pk.y));
             lo.z = pack2<T>(c[4] - unpack_lo<T>(pk.z), c[5] - unpack_hi<T>(pk.z)); lo.w = pack2<T>(c[6] - unpack_lo<T>(pk.w), c[7] - unpack_hi<T>(pk.w));
-            *reinterpret_cast<uint4*>(aux16 + (size_t)(row + s_) * e.ldaux + col) = lo;
+            gst(addr(e.aux16, bax, lax, row0, i * 32 + s_, e.ldaux, 2, jp * 128), lo);
           }
         } else if (out16) {
           uint4 pk;
           pk.x = pack2<T>(o0.x, o0.y); pk.y = pack2<T>(o0.z, o0.w); pk.z = pack2<T>(o1.x, o1.y); pk.w = pack2<T>(o1.z, o1.w);
-          *reinterpret_cast<uint4*>(out16 + (size_t)(row + s_) * e.ld16 + col) = pk;
+          gst(addr(e.out16, b16, l16, row0, i * 32 + s_, e.ld16, 2, jp * 128), pk);
         }
       }
     } else {
@@ -342,7 +467,7 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
             pk.y = pack2<T>(v[2][sp][h], v[3][sp][h]);
             pk.z = pack2<T>(v[4][sp][h], v[5][sp][h]);
             pk.w = pack2<T>(v[6][sp][h], v[7][sp][h]);
-            if (row + 2 * sp + h < M) *reinterpret_cast<uint4*>(aux16 + (size_t)(row + 2 * sp + h) * e.ldaux + col) = pk;
+            if (!RAGGED || row + 2 * sp + h < M) gst(addr(e.aux16, bax, lax, row0, i * 32 + 2 * sp + h, e.ldaux, 2, jp * 128), pk);
           }
         }
         if (EPI == 6) {                        // v *= gelu'(x), x = the saved pre-activation: 0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)
@@ -407,7 +532,7 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
         pk.y = pack2<T>(v[2][s_ >> 1][s_ & 1], v[3][s_ >> 1][s_ & 1]);
         pk.z = pack2<T>(v[4][s_ >> 1][s_ & 1], v[5][s_ >> 1][s_ & 1]);
         pk.w = pack2<T>(v[6][s_ >> 1][s_ & 1], v[7][s_ >> 1][s_ & 1]);
-        if (row + s_ < M) *reinterpret_cast<uint4*>(out16 + (size_t)(row + s_) * e.ld16 + col) = pk;
+        if (!RAGGED || row + s_ < M) gst(addr(e.out16, b16, l16, row0, i * 32 + s_, e.ld16, 2, jp * 128), pk);
       }
     }
   };
@@ -485,8 +610,9 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
 }
 
 // DIRECT: every tile is interior and unmapped (M % 256 == 0, no output row map, no V^T columns): epilogue_w4 only.  The two epilogues
-// do not share a kernel: with both behind a branch hipcc spills 128 accumulator registers to scratch in front of it.
-template <typename T, int EPI, int ABL, bool DIRECT>
+// do not share a kernel: with both behind a branch hipcc spills 128 accumulator registers to scratch in front of it.  For the same reason
+// the two forms of epilogue_w4 are two kernels: RAGGED (DIRECT only) is the launch with M % 256 != 0, whose last row tile is partial.
+template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false>
 __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict__ A, int lda, const T* __restrict__ Wt, int ldw, int M, int N,
                                                              int K, LaGemmEpilogue e, int gm, int stg) {
   constexpr int BK_ = 64;
@@ -677,7 +803,7 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(acc[1][i][j]));
-      epilogue_w4<T, EPI>(slab, acc, m0 + wr * 128, n0 + wc * 128, e, lane, M, N);
+      epilogue_w4<T, EPI, RAGGED>(slab, acc, m0 + wr * 128, n0 + wc * 128, e, lane, M, N);
     } else {
       epilogue_wave<T, EPI>(slab, rtab, acc[0], m0 + wr * 128, n0 + wc * 128, n0, M, e, lane, nostore);
 #pragma unroll
@@ -728,11 +854,11 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail's surplus requests must have landed before the LDS is released
 }
 
-template <typename T, int EPI, int ABL, bool DIRECT>
+template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false>
 static void launch_t256w_abl(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st) {
   constexpr int LDS = 4 * 32768 + 4 * 8192;      // two k-tile buffers + 8 KiB slab per wave: all 160 KiB
   static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256w_kernel<T, EPI, ABL, DIRECT>), LDS, attr_mask);
+  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>), LDS, attr_mask);
   static int ncu_of[64] = {0};                        // per device: a process may drive several GPUs
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -748,7 +874,7 @@ static void launch_t256w_abl(const void* A, int lda, const void* W, int ldw, int
   if (genv && atoi(genv) > 0 && atoi(genv) < grid) grid = atoi(genv);
   static const char* senv = la_dbg_env("LA_W4_STAGGER");     // debugging: "P,D" = P start classes, D x 1024 cycles apart
   if (senv) stg = (atoi(senv) << 16) | (strchr(senv, ',') ? atoi(strchr(senv, ',') + 1) : 0);
-  hipLaunchKernelGGL((gemm_t256w_kernel<T, EPI, ABL, DIRECT>), dim3(grid), dim3(256), LDS, st, reinterpret_cast<const T*>(A), lda,
+  hipLaunchKernelGGL((gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>), dim3(grid), dim3(256), LDS, st, reinterpret_cast<const T*>(A), lda,
                      reinterpret_cast<const T*>(W), ldw, M, N, K, e, gm & 0x5ff, stg);
 }
 
@@ -773,14 +899,16 @@ void launch_t256w(const void* A, int lda, const void* W, int ldw, int M, int N, 
   // (a ragged last row tile - M % 256 != 0: the HF encoders' 57664 = 225.25 tiles - stays on the direct epilogue: its loads and stores are
   // predicated on the row; a residual modulo res_mod needs whole tiles inside a period and is only sent here with M % 256 == 0)
   const bool direct = e.map == LA_MAP_NONE && !e.vt && !((gm >> 8) & 1);
-  if (direct) launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm, st);
+  if (direct && (M & 255) == 0) launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm, st);
+  else if (direct) launch_t256w_abl<T, EPI, 0, true, true>(A, lda, W, ldw, M, N, K, e, gm, st);
   else launch_t256w_abl<T, EPI, 0, false>(A, lda, W, ldw, M, N, K, e, gm, st);
 }
 
 // EPI 5 / 6 (GELU forward that also keeps the pre-activation; data gradient times gelu' - training only) exist on the direct epilogue alone
 template <typename T, int EPI>
 void launch_t256w_fused(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st) {
-  launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm & ~0x100, st);
+  if ((M & 255) == 0) launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm & ~0x100, st);
+  else launch_t256w_abl<T, EPI, 0, true, true>(A, lda, W, ldw, M, N, K, e, gm & ~0x100, st);
 }
 template void launch_t256w_fused<f16_t, 5>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
 template void launch_t256w_fused<f16_t, 6>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
