@@ -573,6 +573,35 @@ int la_error_points(const float* logits, const long long* gt, int B, int C, int 
                     int num_points, const int* ranks, const float* u, const long long* dims, long dims_stride, int long_side,
                     int custom_preprocess, float* points, float* labels, void* stream);
 
+/* ---- episode prompts and ground truths from COCO run-length annotations ---------------------------------------------------------------
+ * Replaces the host side of data/coco.py:397-477 (_get_prompts), :514-544 (compute_ground_truths) and data/transforms.py:123-157
+ * (convert_mask = pycocotools decode into a dense H x W array, sample_point) and feeds :203-224 (apply_masks) from the runs directly.
+ * An annotation is a record of 8 ints in `meta` [K, 8]: run offset, run count n, h, w, image, class slot, order within the image,
+ * reserved.  Its n counts (column-major, alternating 0 / 1, starting with a 0-run, summing to h * w < 2^31, at least one set pixel) sit
+ * at runs[offset ..]; la_rle_scan turns them into inclusive ends; pixel (x, y) is set when #{ends <= x * h + y} is odd.  All pointers are
+ * device pointers; no call synchronises or allocates.
+ * la_rle_scan: counts -> ends (int32, same layout as runs) and area[K] = set pixels (mask_utils.decode(...).sum()); one wave per annotation.
+ * la_rle_decode: out u8 [k, H, W] = dense masks of the annotations sel[0..k), all of size H x W (transforms.py:134-135).
+ * la_rle_prompt_masks: apply_masks + the mask branch of annotations_to_tensor (data/utils.py:219-223) for all N * C (image, class slot)
+ *   pairs in one launch: pair p ORs the annotations index[first[p] .. first[p] + count[p]) of image p / C; geometry as la_prompt_masks
+ *   with (h, w) = img_hw[img], (nh, nw) = new_hw[img]; custom == 0 skips the first resize + pad.  out fp32 [N, C, Mo, Mo] in {0, 1};
+ *   flags u8 [N, C] (zeroed by the caller) = 1 where the result has a set pixel.
+ * la_rle_ground_truth: out int64 [N, Hmax, Wmax] = compute_ground_truths + collate_gts: image i's annotations
+ *   index[first[i] .. first[i] + count[i]) are listed in file order and the LAST one covering a pixel gives its class slot (< 256); 0 where
+ *   nothing covers and beyond the image's own img_hw[i].
+ * la_rle_points: draws int32 [D, 3] = (annotation, rank, destination): the rank-th (clamped into [0, area)) set pixel in row-major
+ *   order (np.argwhere's, transforms.py:152-157) -> points[2 * destination ..] = (x * (nw / w), y * (nh / h)) with the ratio and the
+ *   product in fp64 rounded to fp32 once (apply_coords, transforms.py:159-174; (nh, nw) = new_hw[image]), flags[destination] = 1.  One
+ *   wave per draw. */
+int la_rle_scan(const int* runs, const int* meta, int K, int* ends, int* area, void* stream);
+int la_rle_decode(const int* ends, const int* meta, const int* sel, int k, int H, int W, unsigned char* out, void* stream);
+int la_rle_prompt_masks(const int* ends, const int* meta, const int* first, const int* count, const int* index, const int* img_hw,
+                        const int* new_hw, int N, int C, int custom, int S, int Mo, float* out, unsigned char* flags, void* stream);
+int la_rle_ground_truth(const int* ends, const int* meta, const int* first, const int* count, const int* index, const int* img_hw, int N,
+                        int Hmax, int Wmax, long long* out, void* stream);
+int la_rle_points(const int* ends, const int* meta, const int* area, const int* new_hw, const int* draws, int D, float* points,
+                  unsigned char* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

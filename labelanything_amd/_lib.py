@@ -68,6 +68,7 @@ EXPORTS = [
     "la_norm_finalize", "la_norm_stats", "la_conv3x3_split", "la_conv3x3_split_ok",
     "la_error_count", "la_error_points",
     "la_logits_objective_workspace_bytes", "la_logits_objective", "la_prompt_contrastive_workspace_bytes", "la_prompt_contrastive",
+    "la_rle_scan", "la_rle_decode", "la_rle_prompt_masks", "la_rle_ground_truth", "la_rle_points",
 ]
 
 
@@ -374,6 +375,38 @@ def prompt_masks(masks_u8, first_i32, count_i32, index_i32, p: int, h: int, w: i
     _dev(masks_u8)
     _check(lib().la_prompt_masks(_ptr(masks_u8), _ptr(first_i32), _ptr(count_i32), _ptr(index_i32), C.c_int(p), C.c_int(h), C.c_int(w),
                                  C.c_int(nh), C.c_int(nw), C.c_int(s), C.c_int(mo), _ptr(out), _ptr(flags_u8), _stream()), "la_prompt_masks")
+
+
+# ---- run-length annotations (rle.hip): all int32 device tensors, laid out by labelanything_amd.annotations.pack_rles -------------------
+def rle_scan(runs_i32, meta_i32, k: int, ends_i32, area_i32) -> None:
+    _dev(runs_i32)
+    _check(lib().la_rle_scan(_ptr(runs_i32), _ptr(meta_i32), C.c_int(k), _ptr(ends_i32), _ptr(area_i32), _stream()), "la_rle_scan")
+
+
+def rle_decode(ends_i32, meta_i32, sel_i32, k: int, h: int, w: int, out_u8) -> None:
+    _dev(ends_i32)
+    _check(lib().la_rle_decode(_ptr(ends_i32), _ptr(meta_i32), _ptr(sel_i32), C.c_int(k), C.c_int(h), C.c_int(w), _ptr(out_u8), _stream()),
+           "la_rle_decode")
+
+
+def rle_prompt_masks(ends_i32, meta_i32, first_i32, count_i32, index_i32, img_hw_i32, new_hw_i32, n: int, c: int, custom: bool, s: int, mo: int,
+                     out, flags_u8) -> None:
+    _dev(ends_i32)
+    _check(lib().la_rle_prompt_masks(_ptr(ends_i32), _ptr(meta_i32), _ptr(first_i32), _ptr(count_i32), _ptr(index_i32), _ptr(img_hw_i32),
+                                     _ptr(new_hw_i32), C.c_int(n), C.c_int(c), C.c_int(1 if custom else 0), C.c_int(s), C.c_int(mo), _ptr(out),
+                                     _ptr(flags_u8), _stream()), "la_rle_prompt_masks")
+
+
+def rle_ground_truth(ends_i32, meta_i32, first_i32, count_i32, index_i32, img_hw_i32, n: int, hmax: int, wmax: int, out_i64) -> None:
+    _dev(ends_i32)
+    _check(lib().la_rle_ground_truth(_ptr(ends_i32), _ptr(meta_i32), _ptr(first_i32), _ptr(count_i32), _ptr(index_i32), _ptr(img_hw_i32),
+                                     C.c_int(n), C.c_int(hmax), C.c_int(wmax), _ptr(out_i64), _stream()), "la_rle_ground_truth")
+
+
+def rle_points(ends_i32, meta_i32, area_i32, new_hw_i32, draws_i32, d: int, points, flags_u8) -> None:
+    _dev(ends_i32)
+    _check(lib().la_rle_points(_ptr(ends_i32), _ptr(meta_i32), _ptr(area_i32), _ptr(new_hw_i32), _ptr(draws_i32), C.c_int(d), _ptr(points),
+                               _ptr(flags_u8), _stream()), "la_rle_points")
 
 
 def focal_loss(logits, target_i64, gamma: float, class_weighting: bool, scale: float, ignore_index: int, loss, dlogits, class_weights,

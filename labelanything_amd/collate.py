@@ -26,10 +26,15 @@ def max_annotations(annotations: Sequence[Dict[Any, np.ndarray]]) -> int:
     return max((np.asarray(v).shape[0] for img in annotations for v in img.values()), default=0)
 
 
+def _is_rle_list(v: Any) -> bool:
+    return isinstance(v, (list, tuple)) and len(v) > 0 and all(isinstance(r, dict) and "counts" in r for r in v)
+
+
 def annotations_to_tensor(annotations: Sequence[Dict[Any, Any]], img_sizes: Sequence[Tuple[int, int]], prompt_type: str, side: int = 1024,
                           mask_side: int = 256, custom_preprocess: bool = True, device: Optional[torch.device] = None):
     """annotations[i][cat_id]: boxes float [m, 4] (x1, y1, x2, y2) / points [m, 2] (x, y) in ORIGINAL pixels, or - for masks - a
-    uint8 array [k, H, W] of instance masks whose union is the prompt.  Returns (tensor, flag) shaped like the reference's:
+    uint8 array [k, H, W] of instance masks whose union is the prompt, or a list of COCO RLE dicts (labelanything_amd.annotations), which
+    is rasterised from its runs without a dense mask.  Returns (tensor, flag) shaped like the reference's:
     boxes (N, C, A, 4) + (N, C, A) uint8; points (N, C, A, 2) + (N, C, A) uint8; masks (N, C, 256, 256) fp32 + (N, C) uint8.
     Classes follow the dict order of every image (all images carry the same class ids)."""
     n, c = len(annotations), len(annotations[0])
@@ -39,9 +44,13 @@ def annotations_to_tensor(annotations: Sequence[Dict[Any, Any]], img_sizes: Sequ
             raise RuntimeError("mask prompts are rasterised on the device: pass device='cuda'")
         out = torch.zeros(n, c, mask_side, mask_side, device=device)
         flag = torch.zeros(n, c, dtype=torch.uint8, device=device)
+        rles = [(i, j, r) for i, ann in enumerate(annotations) for j, v in enumerate(ann.values()) if _is_rle_list(v) for r in v]
         for i, ann in enumerate(annotations):
             stacks, slots = [], []
             for m in ann.values():
+                if _is_rle_list(m):                      # this class comes from its runs, below
+                    slots.append([])
+                    continue
                 m = np.asarray(m, dtype=np.uint8)
                 m = m[None] if m.ndim == 2 else m
                 slots.append(list(range(len(stacks), len(stacks) + m.shape[0])))
@@ -50,6 +59,12 @@ def annotations_to_tensor(annotations: Sequence[Dict[Any, Any]], img_sizes: Sequ
                 continue
             inst = torch.from_numpy(np.stack(stacks)).to(device)
             out[i], flag[i] = prompt_masks_from_instances(inst, slots, side, mask_side, custom_preprocess)
+        if rles:
+            from .annotations import RleBatch, pack_rles
+            packed = pack_rles([r for _, _, r in rles], [i for i, _, _ in rles], [j for _, j, _ in rles], list(img_sizes), n_classes=c)
+            rm, rf = RleBatch(packed, device).prompt_masks(None, side, mask_side, custom_preprocess)
+            for i, j in sorted({(i, j) for i, j, _ in rles}):
+                out[i, j], flag[i, j] = rm[i, j], rf[i, j]
         return out, flag
     width = 4 if prompt_type == BBOX else 2
     a = max_annotations(annotations)

@@ -157,6 +157,17 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
          __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
 }
 
+// ---- nearest resize ---------------------------------------------------------------------------
+// torch "nearest" source index (ATen UpSampleKernel nearest_idx): identity / exact halving shortcuts, else
+// min(floorf(dst * (float)in / out), in - 1) in fp32 (one multiply: nothing to contract).  Shared by the dense (prep.hip) and the
+// run-length (rle.hip) mask-prompt kernels.
+__device__ __forceinline__ int nearest_src(int dst, int in_size, int out_size) {
+  if (out_size == in_size) return dst;
+  if (out_size == 2 * in_size) return dst >> 1;
+  const float scale = (float)in_size / (float)out_size;
+  return min((int)floorf((float)dst * scale), in_size - 1);
+}
+
 // ---- LDS tile swizzle -----------------------------------------------------------------------
 // Tiles are [rows][64 halfs] = 128 B per row = 8 chunks of 16 B.  ds_read_b128 is serviced in 16-lane
 // groups over a 256-B bank row (MI355X_MICROARCH LDS table); XOR-ing the chunk with (row>>1)&7 makes

@@ -50,15 +50,6 @@ __global__ __launch_bounds__(256) void u8_to_chw_norm_kernel(const unsigned char
   }
 }
 
-// torch "nearest" source index (ATen UpSampleKernel nearest_idx): identity / exact halving shortcuts, else
-// min(floorf(dst * (float)in / out), in - 1) in fp32
-__device__ __forceinline__ int nearest_src(int dst, int in_size, int out_size) {
-  if (out_size == in_size) return dst;
-  if (out_size == 2 * in_size) return dst >> 1;
-  const float scale = (float)in_size / (float)out_size;
-  return min((int)floorf((float)dst * scale), in_size - 1);
-}
-
 // PromptsProcessor.apply_masks (data/transforms.py:203-224) for P prompt slots at once: OR of the slot's instance masks
 // (u8 [H, W] each, listed by [first, first + count) in `index`), nearest resize to (nh, nw), zero pad to S x S, nearest resize
 // to Mo x Mo - composed per output pixel.  nh == 0: no custom preprocessing (one resize (H, W) -> (Mo, Mo)).
