@@ -247,6 +247,15 @@ struct SmallAttnArgs {
   int split;            // LA_F16X2: out16 rows are [hi | lo] plane pairs of ldo halves each (row stride 2 ldo)
 };
 
+// a * b as an fp32 value of its own.  The plane pair of a product must be split from the value out32 holds (hi = rn16(v), lo = rn16(v - hi),
+// la_common.h), but hipcc folds a visible product into both halves: v - hi becomes a fused multiply-add on the unrounded product, and
+// the conversion becomes v_fma_mixlo_f16, which rounds the exact product to 16 bit once.  The empty asm makes the product opaque.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+  float o = a * b;
+  asm("" : "+v"(o));
+  return o;
+}
+
 // few keys, many queries: one thread per (b, q, head), two passes over the keys (max, then exp-sum).
 template <typename T, int HDIM>
 __global__ __launch_bounds__(256) void attn_fewkeys_kernel(SmallAttnArgs a) {
@@ -292,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_fewkeys_kernel(SmallAttnArgs a) {
     if (a.out16 && a.split) {
       T* op = reinterpret_cast<T*>(a.out16) + bq * 2 * a.ldo;
 #pragma unroll
-      for (int d = 0; d < HDIM; ++d) store_split<T>(op, a.ldo, h * HDIM + d, acc[d] * inv);
+      for (int d = 0; d < HDIM; ++d) store_split<T>(op, a.ldo, h * HDIM + d, mul_rn(acc[d], inv));
     } else if (a.out16) {
       T* op = reinterpret_cast<T*>(a.out16) + bq * a.ldo + h * HDIM;
 #pragma unroll

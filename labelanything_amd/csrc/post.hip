@@ -1,6 +1,7 @@
 // Logit post-processing (lam.py:383-453, 92-93) and the caller's argmax (experiment/run.py:697).
 // fp32 throughout; index arithmetic follows F.interpolate(mode="bilinear", align_corners=False) exactly
-// (source = scale*(dst+0.5)-0.5 clamped at 0, scale = in/out as float).  Compiled with -ffp-contract=off so the
+// (source = fma(scale, dst+0.5, -0.5) clamped at 0, scale = in/out as float: torch's CPU and GPU kernels are built with
+// contraction on, so the product is not rounded on its own).  Contraction is off in this file so that the
 // blend is evaluated as written: t = w0*a + w1*b per row, out = wy0*t0 + wy1*t1.
 #include "la_common.h"
 #include "../../include/la_hip.h"
@@ -10,7 +11,9 @@
 namespace la {
 
 __device__ __forceinline__ void tap(int dst, float scale, int in, int& i0, int& i1, float& w0, float& w1) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
+  // one fused multiply-add, stated (fp contract is off here): rounding the product first moves a tap weight by up to half an ulp of the
+  // source coordinate (4e-6 at 64) away from torch, from la_mask_embed's resample and from the backward kernels, which all fuse it
+  float s = fmaf(scale, (float)dst + 0.5f, -0.5f);
   if (s < 0.f) s = 0.f;
   i0 = (int)s;
   if (i0 > in - 1) i0 = in - 1;

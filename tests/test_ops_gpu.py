@@ -1,4 +1,7 @@
-"""GPU: every C-ABI kernel against a plain torch fp32 reference of the same op.
+"""GPU: the encoder-side and training C-ABI kernels (GEMM paths, attention, LayerNorm, convolutions, resampling, backward kernels), each
+against a plain torch fp32 reference of the same op.  The prompt-encoder / mask-decoder kernels (positional encodings, sparse and dense
+prompts, pooling, prototypes, classification, layout, casts, post-processing) are in tests/test_decoder_ops_gpu.py against fp64;
+tests/test_abi_coverage_cpu.py keeps the ledger of which test reaches which entry point.
 
 Inputs are rounded to the 16-bit operand type first, so the only differences left are the
 accumulation order and the 16-bit rounding of outputs: tolerances are 2e-3 (f16) / 1.6e-2 (bf16)
