@@ -230,6 +230,21 @@ int la_colmean(const float* x, int P, int hw, int D, float* out, float* scratch,
  * emb fp32 [B,M,C,D], flags u8 [B,M,C] -> out fp32 [B,C,D]. */
 int la_class_mean(const float* emb, const unsigned char* flags, int B, int M, int C, int D, float* out, void* stream);
 
+/* k x k region means of every [g*g, D] slab - nn.functional.adaptive_avg_pool2d(src, (k, k)) followed by
+ * rearrange "(b m c) d h w -> b (m h w) c d" (prompt_encoder.py:726-731, embeddings_per_example > 1).
+ * x fp32 [P, g*g, D] with P = B*M*C (class = p % C, support = p / C, as in la_mask_embed) -> out fp32 [B, M*k*k, C, D], example index
+ * m*k*k + i*k + j.  Bin i covers floor(i g / k) .. ceil((i + 1) g / k) - 1 (bins overlap when k does not divide g).  One workgroup per
+ * output row, fixed summation order, no atomics: a row depends on its own slab only.  D % 4 == 0, D <= 1024, 1 <= k <= g. */
+int la_region_mean(const float* x, int B, int M, int C, int g, int k, int D, float* out, void* stream);
+
+/* Per-example classification with the maximum over the examples of a class, fused (mask_decoder.py:309-313 with
+ * segment_example_logits): seg[b][c][pix] = max over n with flags[b][n][c] != 0 of protos[b][n][c] . feat[b][pix]; the N*C planes of
+ * per-example logits are never written.  feat fp32 NHWC [B,Npix,Cf], protos fp32 [B,N,C,Cf], flags u8 [B,N,C], seg fp32 [B,C,Npix];
+ * win (optional, int32 [B,C,Npix]) = the winning n, the lowest among equal scores.  A (b, c) without a valid example gives -inf and
+ * win = -1.  Cf in {8,16,32,64}, C <= 32, N*C*Cf <= 8192. */
+int la_classify_max(const float* feat, const float* protos, const unsigned char* flags, int B, int Npix, int N, int C, int Cf, float* seg,
+                    int* win, void* stream);
+
 /* seg[b][c][pix] = protos[b][c] . feat[b][pix]; feat fp32 NHWC [B,Npix,Cf], protos fp32 [B,C,Cf], seg fp32 [B,C,Npix]
  * (mask_decoder.py:299-314). Cf in {8,16,32,64}. */
 int la_classify(const float* feat, const float* protos, int B, int Npix, int C, int Cf, float* seg, void* stream);
@@ -379,6 +394,16 @@ int la_bilinear_bwd_set(const float* dy, int n, int oh, int ow, long dy_plane, i
  * are those of la_bilinear per channel.  la_bilinear_rows_bwd_set WRITES dx [n, ih * iw, C] from dy [n, oh * ow, C]. */
 int la_bilinear_rows(const float* in, int N, int h, int w, int C, float* out, int H, int W, void* stream);
 int la_bilinear_rows_bwd_set(const float* dy, int n, int oh, int ow, int C, float* dx, int ih, int iw, void* stream);
+
+/* Backward of la_region_mean (autograd of adaptive_avg_pool2d, prompt_encoder.py:728): dx[p, pix, :] = sum over the bins that contain pix
+ * of dy[b, m*k*k + bin, c, :] / |bin|, gathered and WRITTEN once (no atomics).  dy fp32 [B, M*k*k, C, D] -> dx fp32 [B*M*C, g*g, D]. */
+int la_region_mean_bwd(const float* dy, int B, int M, int C, int g, int k, int D, float* dx, void* stream);
+
+/* Backward of la_classify_max with the winners `win` of the forward pass (autograd of seg.max(dim=1), mask_decoder.py:309-313):
+ * dfeat[b, pix, :] = sum_c dseg[b, c, pix] protos[b, win, c, :] (written), dprotos[b, n, c, :] += sum over {pix : win = n} of
+ * dseg[b, c, pix] feat[b, pix, :] (ACCUMULATED); pixels with win = -1 contribute nothing.  Same limits as la_classify_max. */
+int la_classify_max_bwd(const float* dseg, const float* feat, const float* protos, const int* win, int B, int Npix, int N, int C, int Cf,
+                        float* dfeat, float* dprotos, void* stream);
 
 /* Backward of la_classify: dfeat[b, pix, f] (written), dprotos[b, c, f] (ACCUMULATED).  C <= 32, cf in {8, 16, 32, 64}. */
 int la_classify_bwd(const float* dseg, const float* feat, const float* protos, int B, int npix, int C, int cf, float* dfeat, float* dprotos,

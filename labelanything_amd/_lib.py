@@ -69,6 +69,7 @@ EXPORTS = [
     "la_error_count", "la_error_points",
     "la_logits_objective_workspace_bytes", "la_logits_objective", "la_prompt_contrastive_workspace_bytes", "la_prompt_contrastive",
     "la_rle_scan", "la_rle_decode", "la_rle_prompt_masks", "la_rle_ground_truth", "la_rle_points",
+    "la_region_mean", "la_classify_max", "la_region_mean_bwd", "la_classify_max_bwd",
 ]
 
 
@@ -303,6 +304,39 @@ def class_mean(emb, flags_u8, b: int, m: int, c: int, d: int, out) -> None:
 def classify(feat, protos, b: int, npix: int, c: int, cf: int, seg) -> None:
     _check(lib().la_classify(_ptr(feat), _ptr(protos), C.c_int(b), C.c_int(npix), C.c_int(c), C.c_int(cf), _ptr(seg), _stream()),
            "la_classify")
+
+
+def region_mean(x, b: int, m: int, c: int, g: int, k: int, d: int, out) -> None:
+    """x fp32 [b*m*c, g*g, d] -> out fp32 [b, m*k*k, c, d]: adaptive k x k average pooling of every slab, example index m*k*k + i*k + j."""
+    _f32c(x, out)
+    if x.numel() != b * m * c * g * g * d or out.numel() != b * m * k * k * c * d:
+        raise ValueError(f"region_mean: x must hold [{b * m * c}, {g * g}, {d}] and out [{b}, {m * k * k}, {c}, {d}] elements "
+                         f"(got {x.numel()} and {out.numel()})")
+    _check(lib().la_region_mean(_ptr(x), C.c_int(b), C.c_int(m), C.c_int(c), C.c_int(g), C.c_int(k), C.c_int(d), _ptr(out), _stream()),
+           "la_region_mean")
+
+
+def _classify_max_args(feat, protos, b: int, npix: int, n: int, c: int, cf: int, planes) -> None:
+    _f32c(feat, protos)
+    if feat.numel() != b * npix * cf or protos.numel() != b * n * c * cf:
+        raise ValueError(f"classify_max: feat must hold [{b}, {npix}, {cf}] and protos [{b}, {n}, {c}, {cf}] elements")
+    for t, dtype in planes:
+        if t is None:
+            continue
+        _dev(t)
+        if t.dtype != dtype or not t.is_contiguous() or t.numel() != b * c * npix:
+            raise ValueError(f"classify_max: contiguous {dtype} [{b}, {c}, {npix}] planes expected")
+
+
+def classify_max(feat, protos, flags_u8, b: int, npix: int, n: int, c: int, cf: int, seg, win=None) -> None:
+    """seg[b, c, pix] = max over the examples n with flags_u8[b, n, c] != 0 of protos[b, n, c] . feat[b, pix]; win (int32, optional): the
+    winning n (the lowest among equals), -1 where seg is -inf because no example is valid."""
+    _classify_max_args(feat, protos, b, npix, n, c, cf, ((seg, torch.float32), (win, torch.int32)))
+    _dev(flags_u8)
+    if flags_u8.dtype != torch.uint8 or not flags_u8.is_contiguous() or flags_u8.numel() != b * n * c:
+        raise ValueError(f"classify_max: flags must be contiguous uint8 [{b}, {n}, {c}]")
+    _check(lib().la_classify_max(_ptr(feat), _ptr(protos), _ptr(flags_u8), C.c_int(b), C.c_int(npix), C.c_int(n), C.c_int(c), C.c_int(cf),
+                                 _ptr(seg), _ptr(win), _stream()), "la_classify_max")
 
 
 def add_cast(x, y=None, ymod: int = 0, *, out32=None, out16=None, dt: int = LA_F16) -> None:
@@ -639,6 +673,26 @@ def classify_bwd(dseg, feat, protos, b: int, npix: int, c: int, cf: int, dfeat, 
     _f32c(dseg, feat, protos, dfeat, dprotos)
     _check(lib().la_classify_bwd(_ptr(dseg), _ptr(feat), _ptr(protos), C.c_int(b), C.c_int(npix), C.c_int(c), C.c_int(cf), _ptr(dfeat),
                                  _ptr(dprotos), _stream()), "la_classify_bwd")
+
+
+def region_mean_bwd(dy, b: int, m: int, c: int, g: int, k: int, d: int, dx) -> None:
+    """dy fp32 [b, m*k*k, c, d] -> dx fp32 [b*m*c, g*g, d] (written): every pixel gathers dy / |bin| of the bins that contain it."""
+    _f32c(dy, dx)
+    if dx.numel() != b * m * c * g * g * d or dy.numel() != b * m * k * k * c * d:
+        raise ValueError(f"region_mean_bwd: dy must hold [{b}, {m * k * k}, {c}, {d}] and dx [{b * m * c}, {g * g}, {d}] elements "
+                         f"(got {dy.numel()} and {dx.numel()})")
+    _check(lib().la_region_mean_bwd(_ptr(dy), C.c_int(b), C.c_int(m), C.c_int(c), C.c_int(g), C.c_int(k), C.c_int(d), _ptr(dx), _stream()),
+           "la_region_mean_bwd")
+
+
+def classify_max_bwd(dseg, feat, protos, win, b: int, npix: int, n: int, c: int, cf: int, dfeat, dprotos) -> None:
+    """dfeat [b*npix, cf] is written, dprotos [b, n, c, cf] ACCUMULATED; win: the int32 winners classify_max returned."""
+    _classify_max_args(feat, protos, b, npix, n, c, cf, ((dseg, torch.float32), (win, torch.int32)))
+    _f32c(dfeat, dprotos)
+    if dfeat.numel() != feat.numel() or dprotos.numel() != protos.numel():
+        raise ValueError("classify_max_bwd: dfeat / dprotos must have the sizes of feat / protos")
+    _check(lib().la_classify_max_bwd(_ptr(dseg), _ptr(feat), _ptr(protos), _ptr(win), C.c_int(b), C.c_int(npix), C.c_int(n), C.c_int(c),
+                                     C.c_int(cf), _ptr(dfeat), _ptr(dprotos), _stream()), "la_classify_max_bwd")
 
 
 def row_broadcast(src, groups: int, rep: int, d: int, scale: float, out) -> None:

@@ -11,6 +11,8 @@ index_select, expand); every arithmetic node of the prompt encoder / mask decode
     mean_rows     la_colmean                           bwd: la_row_broadcast
     conv3x3       la_conv3x3_f32 (implicit GEMM)       bwd: la_conv3x3_f32 with the transposed taps (dX), la_im2col_3x3 + la_gemm_tn (dW)
     classify      la_classify                          bwd: la_classify_bwd
+    region_mean   la_region_mean                       bwd: la_region_mean_bwd
+    classify_max  la_classify_max                      bwd: la_classify_max_bwd
     bilinear      la_bilinear                          bwd: la_bilinear_bwd
 
 All tensors are fp32, contiguous, on the device; 2-D activations are [rows, channels] (NHWC rows), as in the inference engine.
@@ -439,6 +441,57 @@ class _Classify(Function):
 
 def classify(feat: Tensor, protos: Tensor, bsz: int, npix: int, c: int) -> Tensor:
     return _Classify.apply(feat, protos, bsz, npix, c)
+
+
+class _RegionMean(Function):
+    """[B*M*C * g*g, D] -> [B, M*k*k, C, D]: k x k adaptive average pooling of every (support, class) slab (la_region_mean)."""
+
+    @staticmethod
+    def forward(ctx, x, b, m, c, g, k):
+        x = _c(x)
+        d = x.shape[-1]
+        out = x.new_empty(b, m * k * k, c, d)
+        L.region_mean(x, b, m, c, g, k, d, out)
+        ctx.dims = (b, m, c, g, k, d)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        b, m, c, g, k, d = ctx.dims
+        dx = dy.new_empty(b * m * c * g * g, d)
+        L.region_mean_bwd(_c(dy), b, m, c, g, k, d, dx)
+        return dx, None, None, None, None, None
+
+
+def region_mean(x: Tensor, b: int, m: int, c: int, g: int, k: int) -> Tensor:
+    return _RegionMean.apply(x, b, m, c, g, k)
+
+
+class _ClassifyMax(Function):
+    """seg[b, c, pix] = max over the valid examples n of protos[b, n, c, :] . feat[b, pix, :]; the gradient goes to the winner."""
+
+    @staticmethod
+    def forward(ctx, feat, protos, flags_u8, bsz, npix, n, c):
+        feat, protos = _c(feat), _c(protos)
+        cf = feat.shape[1]
+        seg = feat.new_empty(bsz, c, npix)
+        win = torch.empty(bsz, c, npix, device=feat.device, dtype=torch.int32)
+        L.classify_max(feat, protos, flags_u8, bsz, npix, n, c, cf, seg, win)
+        ctx.save_for_backward(feat, protos, win)
+        ctx.dims = (bsz, npix, n, c, cf)
+        return seg
+
+    @staticmethod
+    def backward(ctx, dseg):
+        feat, protos, win = ctx.saved_tensors
+        bsz, npix, n, c, cf = ctx.dims
+        dfeat, dprotos = torch.empty_like(feat), torch.zeros_like(protos)
+        L.classify_max_bwd(_c(dseg), feat, protos, win, bsz, npix, n, c, cf, dfeat, dprotos)
+        return dfeat, dprotos, None, None, None, None, None
+
+
+def classify_max(feat: Tensor, protos: Tensor, flags_u8: Tensor, bsz: int, npix: int, n: int, c: int) -> Tensor:
+    return _ClassifyMax.apply(feat, protos, flags_u8, bsz, npix, n, c)
 
 
 class _Bilinear(Function):

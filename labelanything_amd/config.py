@@ -8,6 +8,7 @@ device code.
 from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
+import math
 from typing import Dict, Optional, Tuple
 
 
@@ -65,7 +66,7 @@ class LamConfig:
     """Keyword surface of ``LabelAnything.__init__`` (build_lam.py:470-498), on-path subset.
 
     Off-path switches (few_type=Affinity, OneWay/Identity fusion, binary, pyramids,
-    segment_example_logits, conv_classification, class_embedding_dim, TokenPool) are
+    conv_classification, class_embedding_dim, TokenPool, embedding_extraction) are
     accepted only at their default value; anything else raises NotImplementedError.
     """
 
@@ -85,6 +86,12 @@ class LamConfig:
     # Dropout probability of the decoder-side MLP / attention blocks (models/common.py:25-32,68-75, build_lam.py:128).  An inference
     # no-op (eval mode); remembered so that LamTrainer can refuse to train a configuration whose reference applies it.
     dropout: float = 0.0
+    # Per-example family (build_lam.py:126,145-148): k x k pooled embeddings per (support, class) go through the mask decoder as tokens and
+    # every pixel takes the maximum over the valid examples of a class (prompt_encoder.py:726-731, mask_decoder.py:279-287,299-314).
+    # Stored RESOLVED (resolve_examples): segment_example_logits alone means one embedding per example, any truthy
+    # embeddings_per_example turns segment_example_logits on.  Adds no parameters.
+    segment_example_logits: bool = False
+    embeddings_per_example: Optional[int] = None
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -105,6 +112,12 @@ class LamConfig:
         return ENCODER_SPECS[self.encoder]
 
     @property
+    def pool_side(self) -> int:
+        """k of the k x k adaptive average pool: floor(sqrt(embeddings_per_example)) (prompt_encoder.py:727); 1 = the plain mean."""
+        e = self.embeddings_per_example
+        return math.isqrt(int(e)) if e and int(e) > 1 else 1
+
+    @property
     def bank_size(self) -> int:
         return int(self.class_encoder["bank_size"]) if self.class_encoder else 0
 
@@ -115,8 +128,22 @@ _OFF_PATH_DEFAULTS = dict(
     classification_layer_downsample_rate=8, use_support_features_in_prompt_encoder=True,
     fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
-    segment_example_logits=False, dropout=0.0, binary=False,
+    dropout=0.0, binary=False,
+    conv_classification=False, classification_levels=1, prompt_encoder=None, embedding_extraction=None,
 )
+
+
+def resolve_examples(segment_example_logits, embeddings_per_example):
+    """build_lam.py:145-148 -> (segment_example_logits, embeddings_per_example) as the reference's builder resolves them."""
+    seg = bool(segment_example_logits)
+    epe = None if embeddings_per_example is None else int(embeddings_per_example)
+    if epe is not None and epe < 0:
+        raise ValueError(f"embeddings_per_example={epe} must not be negative")
+    if seg and epe is None:
+        epe = 1
+    if epe and not seg:
+        seg = True
+    return seg, epe
 
 
 def config_from_kwargs(**kw) -> LamConfig:
@@ -134,7 +161,12 @@ def config_from_kwargs(**kw) -> LamConfig:
     unknown = [k for k in kw if k not in fields]
     if unknown:
         raise TypeError(f"unexpected LabelAnything arguments: {unknown}")
+    kw["segment_example_logits"], kw["embeddings_per_example"] = resolve_examples(kw.get("segment_example_logits", False),
+                                                                                  kw.get("embeddings_per_example"))
     cfg = LamConfig(**kw)
+    if cfg.pool_side > cfg.grid:
+        raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools {cfg.pool_side} x {cfg.pool_side} bins from a "
+                         f"{cfg.grid} x {cfg.grid} grid")
     if cfg.class_encoder is not None and cfg.class_encoder.get("name") != "RandomMatrixEncoder":
         raise NotImplementedError("only RandomMatrixEncoder is built as class_encoder")
     return cfg

@@ -462,6 +462,99 @@ __global__ __launch_bounds__(256) void classify_kernel(const float* __restrict__
   }
 }
 
+// adaptive_avg_pool2d bin i of k over g positions (prompt_encoder.py:728): [floor(i g / k), ceil((i + 1) g / k)); neighbours overlap by one
+// position when k does not divide g
+__device__ __forceinline__ void pool_bin(int i, int g, int k, int& lo, int& hi) {
+  lo = (i * g) / k;
+  hi = ((i + 1) * g + k - 1) / k;
+}
+
+// k x k region means of every [g*g, D] slab (embeddings_per_example > 1, prompt_encoder.py:726-731): out[b, m k k + i k + j, c, :] =
+// mean of x[p] over bin (i, j), p = (b M + m) C + c - the reference's "(b m c) d h w -> b (m h w) c d".  One workgroup per (bin, p): the
+// row groups walk the bin's pixels in row-major order and are folded in index order, so an output depends on its own slab only.
+__global__ __launch_bounds__(256) void region_mean_kernel(const float* __restrict__ x, int M, int C, int g, int k, int D, float* __restrict__ out) {
+  __shared__ float4 red[256];
+  const int p = blockIdx.x, bin = blockIdx.y;
+  const int nv = D >> 2;
+  const int lanes = min(nv, 256), groups = 256 / lanes;
+  const int c4 = threadIdx.x % lanes, gi = threadIdx.x / lanes;
+  int y0, y1, x0, x1;
+  pool_bin(bin / k, g, k, y0, y1);
+  pool_bin(bin % k, g, k, x0, x1);
+  const int bw = x1 - x0, cnt = (y1 - y0) * bw;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (gi < groups)
+    for (int r = gi; r < cnt; r += groups) {
+      const int pix = (y0 + r / bw) * g + x0 + r % bw;
+      const float4 v = reinterpret_cast<const float4*>(x + ((size_t)p * g * g + pix) * D)[c4];
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (gi == 0) {
+    for (int i = 1; i < groups; ++i) {
+      const float4 v = red[i * lanes + c4];
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    const float n = (float)cnt;
+    const int c = p % C, bm = p / C;              // bm = b M + m: (b, m k k + bin) is row bm k k + bin of [B, M k k]
+    reinterpret_cast<float4*>(out + (((size_t)bm * k * k + bin) * C + c) * D)[c4] = make_float4(s.x / n, s.y / n, s.z / n, s.w / n);
+  }
+}
+
+// seg[b, c, pix] = max over the examples n with flags[b, n, c] != 0 of protos[b, n, c, :] . feat[b, pix, :] (mask_decoder.py:309-313): the
+// N C planes of per-example logits are never written.  Prototypes and flags of image b sit in LDS (every read a broadcast), the pixel's
+// features in registers; c outer, n inner, one running maximum.  Strict > keeps the lowest n among equal scores; win (optional) = that n,
+// -1 and -inf where no example is valid.
+template <int CF>
+__global__ __launch_bounds__(256) void classify_max_kernel(const float* __restrict__ feat, const float* __restrict__ protos,
+                                                           const uint8_t* __restrict__ flags, int Npix, int N, int C, float* __restrict__ seg,
+                                                           int* __restrict__ win) {
+  extern __shared__ float4 cm_lds[];
+  float* pr = reinterpret_cast<float*>(cm_lds);
+  const int b = blockIdx.y;
+  const int nt = N * C;
+  uint8_t* fl = reinterpret_cast<uint8_t*>(pr + nt * CF);
+  for (int i = threadIdx.x; i < nt * (CF / 4); i += 256)
+    reinterpret_cast<float4*>(pr)[i] = reinterpret_cast<const float4*>(protos + (size_t)b * nt * CF)[i];
+  for (int i = threadIdx.x; i < nt; i += 256) fl[i] = flags[(size_t)b * nt + i];
+  __syncthreads();
+  for (int pix = blockIdx.x * 256 + threadIdx.x; pix < Npix; pix += gridDim.x * 256) {
+    float f[CF];
+    const float4* fp = reinterpret_cast<const float4*>(feat + ((size_t)b * Npix + pix) * CF);
+#pragma unroll
+    for (int d = 0; d < CF / 4; ++d) {
+      const float4 t = fp[d];
+      f[4 * d] = t.x; f[4 * d + 1] = t.y; f[4 * d + 2] = t.z; f[4 * d + 3] = t.w;
+    }
+    for (int c = 0; c < C; ++c) {
+      float best = -__builtin_inff();
+      int bi = -1;
+      for (int n = 0; n < N; ++n) {
+        if (!fl[n * C + c]) continue;                       // the same for every lane
+        const float4* pp = reinterpret_cast<const float4*>(pr + (n * C + c) * CF);
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+        for (int d = 0; d < CF / 4; ++d) {
+          const float4 w = pp[d];
+          a0 = fmaf(f[4 * d], w.x, a0);
+          a1 = fmaf(f[4 * d + 1], w.y, a1);
+          a2 = fmaf(f[4 * d + 2], w.z, a2);
+          a3 = fmaf(f[4 * d + 3], w.w, a3);
+        }
+        const float sc = (a0 + a1) + (a2 + a3);
+        if (sc > best) {
+          best = sc;
+          bi = n;
+        }
+      }
+      const size_t o = ((size_t)b * C + c) * Npix + pix;
+      seg[o] = best;
+      if (win) win[o] = bi;
+    }
+  }
+}
+
 // out = x (+ y[row % ymod]) as fp32 and/or 16 bit; contiguous [rows, D]
 template <typename T>
 __global__ void add_cast_kernel(const float* __restrict__ x, const float* __restrict__ y, int ymod, long rows, int D, float* __restrict__ out32,
@@ -654,6 +747,38 @@ extern "C" int la_classify(const float* feat, const float* protos, int B, int Np
     default: LA_CHECK_ARG(false, "la_classify: unsupported feature width %d (8, 16, 32, 64)", Cf);
   }
   LA_CHECK_LAUNCH("la_classify");
+  return 0;
+}
+
+extern "C" int la_region_mean(const float* x, int B, int M, int C, int g, int k, int D, float* out, void* stream) {
+  LA_CHECK_ARG(x && out && B > 0 && M > 0 && C > 0 && g > 0, "la_region_mean: bad arguments");
+  LA_CHECK_ARG(D > 0 && (D % 4) == 0 && D <= 1024, "la_region_mean: D=%d must be a multiple of 4, <= 1024", D);
+  LA_CHECK_ARG(k >= 1 && k <= g, "la_region_mean: pool side %d outside 1..g=%d", k, g);
+  LA_CHECK_ARG(k * k <= 65535 && (long)B * M * C <= 0x7fffffffl, "la_region_mean: %d bins / %ld slabs exceed the grid", k * k, (long)B * M * C);
+  hipLaunchKernelGGL(region_mean_kernel, dim3(B * M * C, k * k), dim3(256), 0, (hipStream_t)stream, x, M, C, g, k, D, out);
+  LA_CHECK_LAUNCH("la_region_mean");
+  return 0;
+}
+
+extern "C" int la_classify_max(const float* feat, const float* protos, const unsigned char* flags, int B, int Npix, int N, int C, int Cf,
+                               float* seg, int* win, void* stream) {
+  LA_CHECK_ARG(feat && protos && flags && seg && B > 0 && B <= 65535 && Npix > 0 && N > 0, "la_classify_max: bad arguments");
+  LA_CHECK_ARG(C > 0 && C <= 32, "la_classify_max: C=%d out of range (1..32)", C);
+  LA_CHECK_ARG(Cf == 8 || Cf == 16 || Cf == 32 || Cf == 64, "la_classify_max: unsupported feature width %d (8, 16, 32, 64)", Cf);
+  LA_CHECK_ARG((long)N * C * Cf <= 8192, "la_classify_max: N * C * Cf = %ld prototypes values exceed the 8192 that fit the LDS tile", (long)N * C * Cf);
+  // a workgroup stages the image's prototypes once and walks several 256-pixel tiles when there are enough workgroups to fill the chip
+  const int tiles = (Npix + 255) / 256;
+  const int cap = 4096 / B > 0 ? 4096 / B : 1;
+  dim3 grid(tiles < cap ? tiles : cap, B);
+  const size_t lds = (size_t)N * C * Cf * sizeof(float) + (((size_t)N * C + 15) & ~(size_t)15);
+  hipStream_t st = (hipStream_t)stream;
+  switch (Cf) {
+    case 8: hipLaunchKernelGGL(classify_max_kernel<8>, grid, dim3(256), lds, st, feat, protos, flags, Npix, N, C, seg, win); break;
+    case 16: hipLaunchKernelGGL(classify_max_kernel<16>, grid, dim3(256), lds, st, feat, protos, flags, Npix, N, C, seg, win); break;
+    case 32: hipLaunchKernelGGL(classify_max_kernel<32>, grid, dim3(256), lds, st, feat, protos, flags, Npix, N, C, seg, win); break;
+    default: hipLaunchKernelGGL(classify_max_kernel<64>, grid, dim3(256), lds, st, feat, protos, flags, Npix, N, C, seg, win); break;
+  }
+  LA_CHECK_LAUNCH("la_classify_max");
   return 0;
 }
 

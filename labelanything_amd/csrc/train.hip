@@ -1027,6 +1027,124 @@ __global__ __launch_bounds__(256) void row_broadcast_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// la_region_mean backward: dx[p, pix, :] = sum over the bins that contain pix of dy[b, m k k + bin, c, :] / |bin| - a gather, written once.
+// Along one axis position y lies in bin floor(y k / g) and at most in its two neighbours (bins are at least one position wide), taken in
+// ascending order.
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pool_bin_of(int i, int g, int k, int& lo, int& hi) {
+  lo = (i * g) / k;
+  hi = ((i + 1) * g + k - 1) / k;
+}
+
+__global__ __launch_bounds__(256) void region_mean_bwd_kernel(const float* __restrict__ dy, long P, int C, int g, int k, int D, float* __restrict__ dx) {
+  const int nv = D >> 2;
+  const long total = P * g * g * nv;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int c4 = (int)(e % nv);
+    const long pp = e / nv;
+    const int pix = (int)(pp % (g * g));
+    const long p = pp / (g * g);
+    const int y = pix / g, x = pix % g;
+    const int c = (int)(p % C);
+    const long bm = p / C;
+    const int iy = (y * k) / g, ix = (x * k) / g;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = max(iy - 1, 0); i <= min(iy + 1, k - 1); ++i) {
+      int y0, y1;
+      pool_bin_of(i, g, k, y0, y1);
+      if (y < y0 || y >= y1) continue;
+      for (int j = max(ix - 1, 0); j <= min(ix + 1, k - 1); ++j) {
+        int x0, x1;
+        pool_bin_of(j, g, k, x0, x1);
+        if (x < x0 || x >= x1) continue;
+        const float n = (float)((y1 - y0) * (x1 - x0));
+        const float4 v = reinterpret_cast<const float4*>(dy + ((bm * k * k + i * k + j) * C + c) * D)[c4];
+        acc.x += v.x / n; acc.y += v.y / n; acc.z += v.z / n; acc.w += v.w / n;
+      }
+    }
+    reinterpret_cast<float4*>(dx)[e] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// la_classify_max backward.  win[b, c, pix] = the example whose logit the forward pass kept (-1: none).
+//   dfeat[b, pix, :] = sum_c dseg[b, c, pix] protos[b, win, c, :]                      (written; the winner's row is gathered from L2)
+//   dprotos[b, n, c, :] += sum over {pix : win = n} of dseg[b, c, pix] feat[b, pix, :]   (accumulated)
+// A wave folds the pixels that share a winner with DPP sums - one round per DISTINCT winner among its 64 pixels, few on real masks - into
+// the workgroup's LDS copy of dprotos[b]; the workgroup walks several pixel tiles and ends with one global atomic per (token, channel)
+// it touched.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int CF>
+__global__ __launch_bounds__(256) void classify_max_bwd_kernel(const float* __restrict__ dseg, const float* __restrict__ feat,
+                                                               const float* __restrict__ protos, const int* __restrict__ win, int Npix, int N, int C,
+                                                               float* __restrict__ dfeat, float* __restrict__ dprotos) {
+  extern __shared__ float cmb_acc[];
+  const int b = blockIdx.y;
+  const int nt = N * C;
+  const int lane = threadIdx.x & 63;
+  for (int i = threadIdx.x; i < nt * CF; i += 256) cmb_acc[i] = 0.f;
+  __syncthreads();
+  const float* pb = protos + (size_t)b * nt * CF;
+  const int tiles = (Npix + 255) / 256;
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {           // whole tiles: every lane of a wave takes part in the wave sums
+    const int pix = t * 256 + threadIdx.x;
+    const bool live = pix < Npix;
+    const int pc = live ? pix : 0;
+    float f[CF], df[CF];
+    const float4* fp = reinterpret_cast<const float4*>(feat + ((size_t)b * Npix + pc) * CF);
+#pragma unroll
+    for (int d = 0; d < CF / 4; ++d) {
+      const float4 v = fp[d];
+      f[4 * d] = v.x; f[4 * d + 1] = v.y; f[4 * d + 2] = v.z; f[4 * d + 3] = v.w;
+    }
+#pragma unroll
+    for (int d = 0; d < CF; ++d) df[d] = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const size_t o = ((size_t)b * C + c) * Npix + pc;
+      int w = live ? win[o] : -1;
+      if (w >= N) w = -1;                                           // never index beyond the prototypes
+      const float gq = w >= 0 ? dseg[o] : 0.f;
+      if (w >= 0) {
+        const float4* pp = reinterpret_cast<const float4*>(pb + ((size_t)w * C + c) * CF);
+#pragma unroll
+        for (int d = 0; d < CF / 4; ++d) {
+          const float4 v = pp[d];
+          df[4 * d] = fmaf(gq, v.x, df[4 * d]);
+          df[4 * d + 1] = fmaf(gq, v.y, df[4 * d + 1]);
+          df[4 * d + 2] = fmaf(gq, v.z, df[4 * d + 2]);
+          df[4 * d + 3] = fmaf(gq, v.w, df[4 * d + 3]);
+        }
+      }
+      unsigned long long todo = __ballot(w >= 0);
+      while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int n = __builtin_amdgcn_readlane(w, __builtin_amdgcn_readfirstlane(src));
+        const bool mine = w == n;
+        const float gm = mine ? gq : 0.f;
+        float keep = 0.f;
+#pragma unroll
+        for (int d = 0; d < CF; ++d) {
+          const float sd = wave_sum_dpp(gm * f[d]);
+          if (lane == d) keep = sd;
+        }
+        if (lane < CF) atomicAdd(&cmb_acc[(n * C + c) * CF + lane], keep);
+        todo &= ~__ballot(mine);
+      }
+    }
+    if (live) {
+      float4* op = reinterpret_cast<float4*>(dfeat + ((size_t)b * Npix + pix) * CF);
+#pragma unroll
+      for (int d = 0; d < CF / 4; ++d) op[d] = make_float4(df[4 * d], df[4 * d + 1], df[4 * d + 2], df[4 * d + 3]);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nt * CF; i += 256) {
+    const float v = cmb_acc[i];
+    if (v != 0.f) atomicAdd(&dprotos[(size_t)b * nt * CF + i], v);
+  }
+}
+
 static int grid_for_n(long n) {
   long g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
@@ -1432,6 +1550,38 @@ extern "C" int la_bilinear_rows_bwd_set(const float* dy, int n, int oh, int ow, 
   hipLaunchKernelGGL(la::bilinear_rows_bwd_gather_kernel, dim3((unsigned)((long)n * ih)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, oh,
                      ow, C, dx, ih, iw);
   LA_CHECK_LAUNCH("la_bilinear_rows_bwd_set");
+  return 0;
+}
+
+extern "C" int la_region_mean_bwd(const float* dy, int B, int M, int C, int g, int k, int D, float* dx, void* stream) {
+  LA_CHECK_ARG(dy && dx && B > 0 && M > 0 && C > 0 && g > 0, "la_region_mean_bwd: bad arguments");
+  LA_CHECK_ARG(D > 0 && (D % 4) == 0 && D <= 1024, "la_region_mean_bwd: D=%d must be a multiple of 4, <= 1024", D);
+  LA_CHECK_ARG(k >= 1 && k <= g && g <= 4096, "la_region_mean_bwd: pool side %d outside 1..g=%d", k, g);
+  const long P = (long)B * M * C;
+  hipLaunchKernelGGL(la::region_mean_bwd_kernel, dim3(la::grid_for_n(P * g * g * (D / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, P,
+                     C, g, k, D, dx);
+  LA_CHECK_LAUNCH("la_region_mean_bwd");
+  return 0;
+}
+
+extern "C" int la_classify_max_bwd(const float* dseg, const float* feat, const float* protos, const int* win, int B, int Npix, int N, int C, int Cf,
+                                   float* dfeat, float* dprotos, void* stream) {
+  LA_CHECK_ARG(dseg && feat && protos && win && dfeat && dprotos, "la_classify_max_bwd: null pointer");
+  LA_CHECK_ARG(B > 0 && B <= 65535 && Npix > 0 && N > 0 && C > 0 && C <= 32, "la_classify_max_bwd: bad shape (C=%d must be 1..32)", C);
+  LA_CHECK_ARG(Cf == 8 || Cf == 16 || Cf == 32 || Cf == 64, "la_classify_max_bwd: unsupported feature width %d (8, 16, 32, 64)", Cf);
+  LA_CHECK_ARG((long)N * C * Cf <= 8192, "la_classify_max_bwd: N * C * Cf = %ld exceeds 8192", (long)N * C * Cf);
+  const int tiles = (Npix + 255) / 256;
+  const int cap = 2048 / B > 0 ? 2048 / B : 1;
+  const dim3 grid(tiles < cap ? tiles : cap, B), block(256);
+  const size_t lds = (size_t)N * C * Cf * sizeof(float);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  switch (Cf) {
+    case 8: hipLaunchKernelGGL(la::classify_max_bwd_kernel<8>, grid, block, lds, st, dseg, feat, protos, win, Npix, N, C, dfeat, dprotos); break;
+    case 16: hipLaunchKernelGGL(la::classify_max_bwd_kernel<16>, grid, block, lds, st, dseg, feat, protos, win, Npix, N, C, dfeat, dprotos); break;
+    case 32: hipLaunchKernelGGL(la::classify_max_bwd_kernel<32>, grid, block, lds, st, dseg, feat, protos, win, Npix, N, C, dfeat, dprotos); break;
+    default: hipLaunchKernelGGL(la::classify_max_bwd_kernel<64>, grid, block, lds, st, dseg, feat, protos, win, Npix, N, C, dfeat, dprotos); break;
+  }
+  LA_CHECK_LAUNCH("la_classify_max_bwd");
   return 0;
 }
 

@@ -1248,7 +1248,8 @@ class LamEngine:
     def prompt_encoder(self, support32: Tensor, b: int, m: int, g: int, points, boxes, masks, flag_examples: Tensor,
                        selected_rows: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """support32: [B*M*hw, D] NHWC fp32.  Returns class_embeddings (B,C,D), class_examples_embeddings (B,M,C,D),
-        class_examples_src (P, hw, D) NHWC."""
+        class_examples_src (P, hw, D) NHWC.  With cfg.pool_side = k > 1 the examples are the M k k region means and ``flag_examples``
+        comes back repeated to (B, M k k, C), as the reference's result dictionary carries it."""
         cfg, w, p = self.cfg, self.w32, self.p
         pe_ = "prompt_encoder"
         d = cfg.embed_dim
@@ -1291,17 +1292,27 @@ class LamEngine:
             L.mask_embed(None, None, pcount, c, 0, g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16, srcpe16,
                          self.idti)
         self.two_way(pe_ + ".transformer", sp, pcount, ns, src32, src16, srcpe16, hw, pe32, "pe.tw", want_tokens=False)
-        emb = self.f32("pe.emb", (pcount, d))
-        L.colmean(src32, pcount, hw, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
+        k = cfg.pool_side
+        fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
+        if k > 1:
+            # embeddings_per_example > 1 (prompt_encoder.py:726-731): k x k region means per (support, class) instead of the slab mean; every
+            # bin is an example of its own from here on - M k k of them, flagged like the support they come from
+            m = m * k * k
+            emb = self.f32("pe.emb", (b * m * c, d))
+            L.region_mean(src32, b, m // (k * k), c, g, k, d, emb)
+            fe = fe.repeat_interleave(k * k, dim=1).contiguous()
+            flag_examples = fe
+        else:
+            emb = self.f32("pe.emb", (pcount, d))
+            L.colmean(src32, pcount, hw, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
         if cfg.class_attention:
             emb = self.attention_mlp_block(pe_ + ".class_attention", emb, b * m, c, "pe.ca")
         if cfg.example_attention:
             e2 = emb.view(b, m, c, d).permute(0, 2, 1, 3).contiguous().view(b * c * m, d)
             e2 = self.attention_mlp_block(pe_ + ".example_attention", e2, b * c, m, "pe.ea")
-            emb = e2.view(b, c, m, d).permute(0, 2, 1, 3).contiguous().view(pcount, d)
+            emb = e2.view(b, c, m, d).permute(0, 2, 1, 3).contiguous().view(b * m * c, d)
         if cfg.example_class_attention:
             emb = self.attention_mlp_block(pe_ + ".class_example_attention", emb, b, m * c, "pe.cea")
-        fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
         cls = torch.empty(b, c, d, device=self.dev, dtype=torch.float32)
         L.class_mean(emb, fe, b, m, c, d, cls)
         return {"flag_examples": flag_examples, "class_embeddings": cls,
@@ -1310,12 +1321,29 @@ class LamEngine:
     # ------------------------------------------------------------------------------------------------
     # mask decoder (mask_decoder.py:316-363)
     # ------------------------------------------------------------------------------------------------
-    def mask_decoder(self, query32: Tensor, b: int, g: int, class_emb: Tensor) -> Tensor:
-        """query32 [B*hw, D] NHWC fp32, class_emb (B,C,D) fp32 -> low-res logits (B, C, 4g, 4g) fp32."""
+    def example_valid(self, flag_examples: Tensor) -> Tensor:
+        """(B, N, C) example flags -> u8 (B, C): classes with at least one valid example.  The others' low-res planes are -inf (a maximum
+        over nothing); their full-resolution planes are forced to -inf as well (la_post_final's class mask) where resampling -inf
+        planes would give the reference's NaN."""
+        return (self.h2d(flag_examples) != 0).any(dim=1).to(torch.uint8).contiguous()
+
+    def mask_decoder(self, query32: Tensor, b: int, g: int, class_emb: Tensor, examples: Optional[Tensor] = None,
+                     flag_examples: Optional[Tensor] = None) -> Tensor:
+        """query32 [B*hw, D] NHWC fp32, class_emb (B,C,D) fp32 -> low-res logits (B, C, 4g, 4g) fp32.  segment_example_logits
+        (mask_decoder.py:279-287,309-313): the tokens are the N C per-example embeddings ``examples`` (B,N,C,D) in (n, c) order and every
+        pixel keeps the maximum over the examples that ``flag_examples`` (B,N,C) marks valid."""
         cfg, w, p = self.cfg, self.w32, self.p
         md = "mask_decoder"
         d = cfg.embed_dim
         hw = g * g
+        nex = 0
+        if cfg.segment_example_logits:
+            if examples is None or flag_examples is None:
+                raise ValueError("segment_example_logits needs the per-example embeddings and their flags (class_examples_embeddings, "
+                                 "flag_examples of the prompt encoder's result)")
+            nex, ncls = examples.shape[1], examples.shape[2]
+            fex = self.h2d(flag_examples, torch.uint8).reshape(b, nex, ncls).contiguous()
+            class_emb = examples.reshape(b, nex * ncls, d)
         c = class_emb.shape[1]
         pe32 = self.dense_pe(g)
         img32 = self.f32("md.img32", (b * hw, d))
@@ -1370,6 +1398,10 @@ class LamEngine:
                     L.gemm(col, p[f"{md}.sc{i}.w"], bias=w[f"{md}.spatial_convs.{3 * i}.bias"], out32=feat32)
                 if i < cfg.spatial_convs - 1:
                     self.dln(feat32, f"{md}.spatial_convs.{3 * i + 1}", 1e-6, gelu=True, out16=feat16)
+        if nex:
+            seg = torch.empty(b, ncls, 4 * g, 4 * g, device=self.dev, dtype=torch.float32)
+            L.classify_max(feat32, protos, fex, b, npix, nex, ncls, cf, seg)
+            return seg
         seg = torch.empty(b, c, 4 * g, 4 * g, device=self.dev, dtype=torch.float32)
         L.classify(feat32, protos, b, npix, c, cf, seg)
         return seg

@@ -12,6 +12,7 @@ inference path; training (forward + backward + AdamW on the same kernels) goes t
 """
 from __future__ import annotations
 
+import dataclasses
 import inspect
 import json
 import os
@@ -20,7 +21,7 @@ from typing import Any, Dict, Optional
 import torch
 from torch import nn
 
-from .config import LamConfig, ENCODER_SPECS, config_from_kwargs
+from .config import LamConfig, ENCODER_SPECS, config_from_kwargs, resolve_examples
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
 from . import _lib as L
@@ -80,8 +81,17 @@ class Lam(nn.Module):
     image_format: str = "RGB"
 
     def __init__(self, cfg: LamConfig, seed: Optional[int] = None, compute_dtype: torch.dtype = torch.float16,
-                 decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT):
+                 decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT,
+                 segment_example_logits: Optional[bool] = None, embeddings_per_example: Optional[int] = None):
+        """segment_example_logits / embeddings_per_example: the per-example family on top of ``cfg`` (resolved as build_lam.py:145-148
+        does); left at None they keep what ``cfg`` says."""
         super().__init__()
+        if segment_example_logits is not None or embeddings_per_example is not None:
+            seg, epe = resolve_examples(cfg.segment_example_logits if segment_example_logits is None else segment_example_logits,
+                                        cfg.embeddings_per_example if embeddings_per_example is None else embeddings_per_example)
+            cfg = dataclasses.replace(cfg, segment_example_logits=seg, embeddings_per_example=epe)
+        if cfg.pool_side > cfg.grid:
+            raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools more bins than the {cfg.grid} x {cfg.grid} grid has")
         self.cfg = cfg
         self.image_size = cfg.image_size
         self.custom_preprocess = cfg.custom_preprocess
@@ -298,11 +308,17 @@ class Lam(nn.Module):
         support = ev[:, 1:].contiguous().view(b * (n - 1) * hw, d)
         points, boxes, masks = self._prompts_of(inp)
         pe_result = eng.prompt_encoder(support, b, n - 1, g, points, boxes, masks, inp["flag_examples"], inp.get("selected_rows"))
-        seg = eng.mask_decoder(query, b, g, pe_result["class_embeddings"])
+        seg = eng.mask_decoder(query, b, g, pe_result["class_embeddings"], pe_result["class_examples_embeddings"], pe_result["flag_examples"])
         out = {"low_res_logits": seg, "class_embeddings": pe_result["class_embeddings"],
                "class_examples_embeddings": pe_result["class_examples_embeddings"]}
+        if self.cfg.segment_example_logits:      # the flags that go with the (B, M k k, C, D) example embeddings, as the reference's pe_result
+            out["flag_examples"] = pe_result["flag_examples"]
         if want_post:
-            logits, am = eng.postprocess_dev(seg, inp["sizes"], plan[2], plan[3], inp.get("flag_gts"), want_argmax)
+            fg = inp.get("flag_gts")
+            if self.cfg.segment_example_logits:
+                valid = eng.example_valid(pe_result["flag_examples"])
+                fg = valid if fg is None else (fg != 0).to(torch.uint8) & valid
+            logits, am = eng.postprocess_dev(seg, inp["sizes"], plan[2], plan[3], fg, want_argmax)
             out["logits"] = logits
             if want_argmax:
                 out["argmax"] = am
@@ -382,6 +398,11 @@ class Lam(nn.Module):
         d = self.cfg.embed_dim
         e32, b, n, g = self._embeddings_nhwc(batched_input, apply_neck_to_embeddings=False)
         query = e32.view(b, n, g * g, d)[:, 0].contiguous().view(b * g * g, d)
+        if self.cfg.segment_example_logits:
+            # the per-example family serves from the cached per-example embeddings and their flags (mask_decoder.py:279-287)
+            seg = eng.mask_decoder(query, b, g, class_embeddings["class_embeddings"], class_embeddings["class_examples_embeddings"],
+                                   class_embeddings["flag_examples"])
+            return eng.postprocess(seg, batched_input["dims"].unsqueeze(1), eng.example_valid(class_embeddings["flag_examples"]))
         seg = eng.mask_decoder(query, b, g, class_embeddings["class_embeddings"])
         return eng.postprocess(seg, batched_input["dims"].unsqueeze(1))
 

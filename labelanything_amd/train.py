@@ -253,7 +253,15 @@ class DecoderGraph:
             src = _AddPerGroup.apply(src, ce.repeat(b * m, 1), p, hw)
         pos = self.dense_pe(g)
         _, keys = self.two_way(pe_ + ".transformer", src, pos, sp, p, ns, hw, want_tokens=False)
-        emb = A.mean_rows(keys, p, hw)
+        k = cfg.pool_side
+        if k > 1:
+            # embeddings_per_example > 1 (prompt_encoder.py:726-731): the M k k region means are examples of their own from here on
+            emb = A.region_mean(keys, b, m, c, g, k).reshape(p * k * k, d)
+            m = m * k * k
+            p = b * m * c
+            flag_examples = flag_examples.reshape(b, m // (k * k), c).repeat_interleave(k * k, dim=1)
+        else:
+            emb = A.mean_rows(keys, p, hw)
         if cfg.class_attention:
             emb = self.attention_mlp_block(pe_ + ".class_attention", emb, b * m, c)
         if cfg.example_attention:
@@ -267,7 +275,8 @@ class DecoderGraph:
         denom = fe.sum(dim=1)
         denom = torch.where(denom == 0, torch.ones_like(denom), denom)
         cls = (emb.view(b, m, c, d) * fe).sum(dim=1) / denom
-        return {"class_embeddings": cls, "class_examples_embeddings": emb.view(b, m, c, d), "class_examples_src": keys}
+        return {"class_embeddings": cls, "class_examples_embeddings": emb.view(b, m, c, d), "class_examples_src": keys,
+                "flag_examples": flag_examples.reshape(b, m, c)}
 
     # ---- mask decoder (mask_decoder.py:316-363) --------------------------------------------------------------------------------
     def conv_transpose_2x2(self, name: str, x: Tensor, bsz: int, h: int, wd: int) -> Tensor:
@@ -277,10 +286,15 @@ class DecoderGraph:
         y = A.linear(x, w.permute(2, 3, 1, 0).reshape(4 * cout, w.shape[0]), self.w[name + ".bias"].repeat(4))
         return y.view(bsz, h, wd, 2, 2, cout).permute(0, 1, 3, 2, 4, 5).reshape(bsz * 4 * h * wd, cout)
 
-    def mask_decoder(self, query: Tensor, b: int, g: int, class_emb: Tensor) -> Tensor:
+    def mask_decoder(self, query: Tensor, b: int, g: int, class_emb: Tensor, examples: Optional[Tensor] = None,
+                     flag_examples: Optional[Tensor] = None) -> Tensor:
         cfg = self.cfg
         md = "mask_decoder"
         d, hw = cfg.embed_dim, g * g
+        nex = 0
+        if cfg.segment_example_logits:       # tokens = the N C per-example embeddings in (n, c) order (mask_decoder.py:279-287)
+            nex, ncls = examples.shape[1], examples.shape[2]
+            class_emb = examples.reshape(b, nex * ncls, d)
         c = class_emb.shape[1]
         toks, keys = self.two_way(md + ".transformer", query, self.dense_pe(g), class_emb.reshape(b * c, d), b, c, hw, want_tokens=True)
         pr = A.relu(self.lin(md + ".class_mlp.layers.0", toks))
@@ -294,6 +308,10 @@ class DecoderGraph:
                 feat = A.conv3x3(feat, self.w[f"{md}.spatial_convs.{3 * i}.weight"], self.w[f"{md}.spatial_convs.{3 * i}.bias"], b, 4 * g, 4 * g)
                 if i < cfg.spatial_convs - 1:
                     feat = self.ln(f"{md}.spatial_convs.{3 * i + 1}", feat, 1e-6, gelu=True)
+        if nex:                               # maximum over the valid examples of each class (mask_decoder.py:309-313)
+            fex = flag_examples.reshape(b, nex, ncls).to(device=feat.device, dtype=torch.uint8).contiguous()
+            seg = A.classify_max(feat, pr.reshape(b, nex, ncls, -1), fex, b, 16 * hw, nex, ncls)
+            return seg.view(b, ncls, 4 * g, 4 * g)
         seg = A.classify(feat, pr.reshape(b, c, -1), b, 16 * hw, c)
         return seg.view(b, c, 4 * g, 4 * g)
 
@@ -336,8 +354,12 @@ class DecoderGraph:
         support = ev[:, 1:].reshape(b * (n - 1) * hw, d)
         points, boxes, masks = Lam._prompts_of(inp)
         pe = self.prompt_encoder(support, b, n - 1, g, points, boxes, masks, inp["flag_examples"], inp.get("selected_rows"))
-        seg = self.mask_decoder(query.contiguous(), b, g, pe["class_embeddings"])
-        logits = self.postprocess(seg, dims, inp.get("flag_gts"))
+        seg = self.mask_decoder(query.contiguous(), b, g, pe["class_embeddings"], pe["class_examples_embeddings"], pe["flag_examples"])
+        fg = inp.get("flag_gts")
+        if cfg.segment_example_logits:       # classes without a valid example: -inf at full resolution too (LamEngine.example_valid)
+            valid = (pe["flag_examples"] != 0).any(dim=1)
+            fg = valid if fg is None else (fg.to(valid.device) != 0) & valid
+        logits = self.postprocess(seg, dims, fg)
         return {"logits": logits, "low_res_logits": seg, **pe}
 
 
@@ -365,6 +387,12 @@ class LamTrainer:
             # build_lam.py:128); the training graph here has no dropout node, so training such a model would silently be a different model
             raise NotImplementedError(f"dropout={lam.cfg.dropout} is not built into the training graph (every canonical parameters/*.yaml "
                                       f"leaves it at 0); build the model with dropout=0.0 to train it here")
+        if lam.cfg.pool_side > 1 and isinstance(loss, LabelAnythingLoss) and len(loss.prompt_components):
+            # the contrastive term pairs the examples of a class across supports; with k x k region embeddings per support the reference's
+            # pairing treats the bins of ONE support as independent positives, which nobody has checked here
+            raise NotImplementedError(f"the prompt_contrastive loss component is not built for embeddings_per_example="
+                                      f"{lam.cfg.embeddings_per_example} (more than one embedding per example); train it without that "
+                                      f"component")
         if lam._device().type != "cuda":
             raise RuntimeError("LamTrainer needs the model on an MI355X (there is no CPU path)")
         self.lam = lam
