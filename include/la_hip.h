@@ -627,6 +627,28 @@ int la_rle_ground_truth(const int* ends, const int* meta, const int* first, cons
 int la_rle_points(const int* ends, const int* meta, const int* area, const int* new_hw, const int* draws, int D, float* points,
                   unsigned char* flags, void* stream);
 
+/* ---- the two-level classification head (classification_levels = 2) ---------------------------------------------------------------------
+ * Coarse level (mask_decoder.py:345-346 through _classify :309, on the transformer's output tokens BEFORE class_mlp and the D-channel image
+ * stream BEFORE the upscaler): seg[b][c][pix] = tok[b][c][:] . img[b][pix][:].  tok fp32 [B,C,D], img fp32 NHWC [B,Npix,D], seg fp32
+ * [B,C,Npix]; fp32 multiply-add in channel order.  D % 64 == 0, D <= 1024, C <= 32; anything else is refused with a message.
+ * Backward: dimg [B,Npix,D] is WRITTEN, dtok [B,C,D] ACCUMULATED (as la_classify_bwd does with dprotos). */
+int la_classify_wide(const float* tok, const float* img, int B, int Npix, int C, int D, float* seg, void* stream);
+int la_classify_wide_bwd(const float* dseg, const float* tok, const float* img, int B, int Npix, int C, int D, float* dimg, float* dtok,
+                         void* stream);
+
+/* level_reducer = Conv2d(2, 1, 3x3, padding "same") over stack([cls0, resize(cls1)]) per (b, c) plane (mask_decoder.py:204,358-362):
+ * seg[b][c][y][x] = bias + sum over l, ky, kx of w[l][ky][kx] * level_l[y + ky - 1][x + kx - 1], level_0 = cls0 [B,C,4gh,4gw], level_1 = the
+ * x4 bilinear enlargement (align_corners = False, phase weights 1/8 3/8 5/8 7/8) of cls1 [B,C,gh,gw], evaluated per tile and never
+ * written.  Source indices of the enlargement clamp to the coarse plane; taps of the 3x3 outside the 4gh x 4gw plane are zero for both
+ * levels; no plane reads another.  w: 18 floats [level][3][3], bias: 1 float (device pointers).  Per output: bias, the nine level-0 taps,
+ * the nine level-1 taps, one fmaf each.
+ * Backward from dseg, cls0, cls1, w: dcls0 [B,C,4gh,4gw] and dcls1 [B,C,gh,gw] (through the enlargement's adjoint, as a gather) are both
+ * WRITTEN - no zero-filled destination is needed; dw[18] and dbias[1] are ACCUMULATED into the caller's gradient slots. */
+int la_level_reduce(const float* cls0, const float* cls1, const float* w, const float* bias, int B, int C, int gh, int gw, float* seg,
+                    void* stream);
+int la_level_reduce_bwd(const float* dseg, const float* cls0, const float* cls1, const float* w, int B, int C, int gh, int gw, float* dcls0,
+                        float* dcls1, float* dw, float* dbias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,7 @@ EXPORTS = [
     "la_logits_objective_workspace_bytes", "la_logits_objective", "la_prompt_contrastive_workspace_bytes", "la_prompt_contrastive",
     "la_rle_scan", "la_rle_decode", "la_rle_prompt_masks", "la_rle_ground_truth", "la_rle_points",
     "la_region_mean", "la_classify_max", "la_region_mean_bwd", "la_classify_max_bwd",
+    "la_classify_wide", "la_classify_wide_bwd", "la_level_reduce", "la_level_reduce_bwd",
 ]
 
 
@@ -919,3 +920,47 @@ def colsum_fold(part, groups: int, chunks: int, d: int, inv: float, out) -> None
 def add_rowvec(x, v, rows_per_group: int) -> None:
     _f32c(x, v)
     _check(lib().la_add_rowvec(_ptr(x), _ptr(v), C.c_long(x.shape[0]), C.c_int(rows_per_group), C.c_int(x.shape[1]), _stream()), "la_add_rowvec")
+
+
+# ---- the two-level classification head (classification_levels = 2, csrc/levels.hip) ----------------------------------------------------
+def _numel(what: str, **named) -> None:
+    for name, (t, n) in named.items():
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} must hold {n} elements (got {t.numel()})")
+
+
+def classify_wide(tok, img, b: int, npix: int, c: int, d: int, seg) -> None:
+    """seg[b, c, pix] = tok[b, c, :] . img[b, pix, :] over the transformer width d (d % 64 == 0, d <= 1024, c <= 32: the library refuses
+    anything else)."""
+    _f32c(tok, img, seg)
+    _numel("classify_wide", tok=(tok, b * c * d), img=(img, b * npix * d), seg=(seg, b * c * npix))
+    _check(lib().la_classify_wide(_ptr(tok), _ptr(img), C.c_int(b), C.c_int(npix), C.c_int(c), C.c_int(d), _ptr(seg), _stream()),
+           "la_classify_wide")
+
+
+def classify_wide_bwd(dseg, tok, img, b: int, npix: int, c: int, d: int, dimg, dtok) -> None:
+    """dimg [b, npix, d] is written, dtok [b, c, d] ACCUMULATED."""
+    _f32c(dseg, tok, img, dimg, dtok)
+    _numel("classify_wide_bwd", dseg=(dseg, b * c * npix), tok=(tok, b * c * d), img=(img, b * npix * d), dimg=(dimg, b * npix * d),
+           dtok=(dtok, b * c * d))
+    _check(lib().la_classify_wide_bwd(_ptr(dseg), _ptr(tok), _ptr(img), C.c_int(b), C.c_int(npix), C.c_int(c), C.c_int(d), _ptr(dimg),
+                                      _ptr(dtok), _stream()), "la_classify_wide_bwd")
+
+
+def level_reduce(cls0, cls1, w, bias, b: int, c: int, gh: int, gw: int, seg) -> None:
+    """seg [b, c, 4gh, 4gw] = bias + conv3x3 (zero padding) of [cls0, x4 bilinear enlargement of cls1 [b, c, gh, gw]] with w [2][3][3]."""
+    _f32c(cls0, cls1, w, bias, seg)
+    _numel("level_reduce", cls0=(cls0, b * c * 16 * gh * gw), cls1=(cls1, b * c * gh * gw), w=(w, 18), bias=(bias, 1),
+           seg=(seg, b * c * 16 * gh * gw))
+    _check(lib().la_level_reduce(_ptr(cls0), _ptr(cls1), _ptr(w), _ptr(bias), C.c_int(b), C.c_int(c), C.c_int(gh), C.c_int(gw), _ptr(seg),
+                                 _stream()), "la_level_reduce")
+
+
+def level_reduce_bwd(dseg, cls0, cls1, w, b: int, c: int, gh: int, gw: int, dcls0, dcls1, dw, dbias) -> None:
+    """dcls0 [b, c, 4gh, 4gw] and dcls1 [b, c, gh, gw] are written; dw [18] and dbias [1] ACCUMULATED."""
+    _f32c(dseg, cls0, cls1, w, dcls0, dcls1, dw, dbias)
+    n0, n1 = b * c * 16 * gh * gw, b * c * gh * gw
+    _numel("level_reduce_bwd", dseg=(dseg, n0), cls0=(cls0, n0), cls1=(cls1, n1), w=(w, 18), dcls0=(dcls0, n0), dcls1=(dcls1, n1),
+           dw=(dw, 18), dbias=(dbias, 1))
+    _check(lib().la_level_reduce_bwd(_ptr(dseg), _ptr(cls0), _ptr(cls1), _ptr(w), C.c_int(b), C.c_int(c), C.c_int(gh), C.c_int(gw),
+                                     _ptr(dcls0), _ptr(dcls1), _ptr(dw), _ptr(dbias), _stream()), "la_level_reduce_bwd")

@@ -14,6 +14,8 @@ index_select, expand); every arithmetic node of the prompt encoder / mask decode
     region_mean   la_region_mean                       bwd: la_region_mean_bwd
     classify_max  la_classify_max                      bwd: la_classify_max_bwd
     bilinear      la_bilinear                          bwd: la_bilinear_bwd
+    classify_wide la_classify_wide                     bwd: la_classify_wide_bwd       (classification_levels = 2: the coarse level)
+    level_reduce  la_level_reduce                      bwd: la_level_reduce_bwd        (level_reducer over [fine, enlarged coarse])
 
 All tensors are fp32, contiguous, on the device; 2-D activations are [rows, channels] (NHWC rows), as in the inference engine.
 Reference graph: label_anything/models/{common,transformer,prompt_encoder,mask_decoder}.py under experiment/utils.py:266-303.
@@ -492,6 +494,66 @@ class _ClassifyMax(Function):
 
 def classify_max(feat: Tensor, protos: Tensor, flags_u8: Tensor, bsz: int, npix: int, n: int, c: int) -> Tensor:
     return _ClassifyMax.apply(feat, protos, flags_u8, bsz, npix, n, c)
+
+
+class _ClassifyWide(Function):
+    """seg[b, c, pix] = tok[b, c, :] . img[b, pix, :] over the transformer width (the coarse level of classification_levels = 2)."""
+
+    @staticmethod
+    def forward(ctx, img, tok, bsz, npix, c):
+        img, tok = _c(img), _c(tok)
+        d = img.shape[1]
+        seg = img.new_empty(bsz, c, npix)
+        L.classify_wide(tok, img, bsz, npix, c, d, seg)
+        ctx.save_for_backward(img, tok)
+        ctx.dims = (bsz, npix, c, d)
+        return seg
+
+    @staticmethod
+    def backward(ctx, dseg):
+        img, tok = ctx.saved_tensors
+        bsz, npix, c, d = ctx.dims
+        dimg, dtok = torch.empty_like(img), torch.zeros_like(tok)
+        L.classify_wide_bwd(_c(dseg), tok, img, bsz, npix, c, d, dimg, dtok)
+        return dimg, dtok, None, None, None
+
+
+def classify_wide(img: Tensor, tok: Tensor, bsz: int, npix: int, c: int) -> Tensor:
+    """img [B*npix, D] NHWC rows, tok [B*C, D] -> [B, C, npix]."""
+    return _ClassifyWide.apply(img, tok, bsz, npix, c)
+
+
+class _LevelReduce(Function):
+    """[B, C, 4gh, 4gw] fine logits + [B, C, gh, gw] coarse logits -> Conv2d(2, 1, 3x3, "same") over [fine, x4 enlargement of coarse]; w is
+    the nn.Conv2d weight (1, 2, 3, 3), bias (1,).  Their gradients go straight into the gradient sink when one is installed."""
+
+    @staticmethod
+    def forward(ctx, cls0, cls1, w, bias, bsz, c, gh, gw):
+        cls0, cls1, w, bias = _c(cls0), _c(cls1), _c(w), _c(bias)
+        seg = cls0.new_empty(bsz, c, 4 * gh, 4 * gw)
+        L.level_reduce(cls0, cls1, w, bias, bsz, c, gh, gw, seg)
+        ctx.save_for_backward(cls0, cls1, w, bias)
+        ctx.dims = (bsz, c, gh, gw)
+        return seg
+
+    @staticmethod
+    def backward(ctx, dseg):
+        cls0, cls1, w, bias = ctx.saved_tensors
+        bsz, c, gh, gw = ctx.dims
+        dcls0, dcls1 = torch.empty_like(cls0), torch.empty_like(cls1)
+        gw_, gb_ = SINK.find(w), SINK.find(bias)
+        dw = db = None
+        if gw_ is None:
+            dw = torch.zeros_like(w)
+        if gb_ is None:
+            db = torch.zeros_like(bias)
+        L.level_reduce_bwd(_c(dseg), cls0, cls1, w, bsz, c, gh, gw, dcls0, dcls1, gw_ if gw_ is not None else dw,
+                           gb_ if gb_ is not None else db)
+        return dcls0, dcls1, dw, db, None, None, None, None
+
+
+def level_reduce(cls0: Tensor, cls1: Tensor, w: Tensor, bias: Tensor, bsz: int, c: int, gh: int, gw: int) -> Tensor:
+    return _LevelReduce.apply(cls0, cls1, w, bias, bsz, c, gh, gw)
 
 
 class _Bilinear(Function):

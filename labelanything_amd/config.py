@@ -92,6 +92,10 @@ class LamConfig:
     # embeddings_per_example turns segment_example_logits on.  Adds no parameters.
     segment_example_logits: bool = False
     embeddings_per_example: Optional[int] = None
+    # 2: the decoder owns level_reducer = Conv2d(2, 1, 3x3, "same") over [fine logits, x4 enlargement of the transformer-level logits]
+    # (mask_decoder.py:204,345-346,358-362; parameters/trainval/pascal/mae_levels.yaml).  The reference's forward stacks exactly two
+    # levels, so 1 and 2 are the values that can run.  Adds mask_decoder.level_reducer.{weight,bias}.
+    classification_levels: int = 1
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -129,7 +133,7 @@ _OFF_PATH_DEFAULTS = dict(
     fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
     dropout=0.0, binary=False,
-    conv_classification=False, classification_levels=1, prompt_encoder=None, embedding_extraction=None,
+    conv_classification=False, prompt_encoder=None, embedding_extraction=None,
 )
 
 
@@ -144,6 +148,17 @@ def resolve_examples(segment_example_logits, embeddings_per_example):
     if epe and not seg:
         seg = True
     return seg, epe
+
+
+def check_levels(levels, segment_example_logits) -> None:
+    """The one check of ``classification_levels`` (config_from_kwargs and Lam): an int, 1 or 2, and 2 not with the per-example family."""
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels not in (1, 2):
+        raise ValueError(f"classification_levels={levels!r}: the reference's mask decoder stacks exactly two levels (mask_decoder.py:360), "
+                         f"so only the integers 1 and 2 can run")
+    if levels == 2 and segment_example_logits:
+        raise NotImplementedError("classification_levels=2 together with segment_example_logits / embeddings_per_example is not built: the "
+                                  "only reference recipe that combines them (parameters/trainval/pascal/mae_chooser.yaml) also needs the "
+                                  "`pooler` embedding extraction and the `masks` loss, neither of which is built")
 
 
 def config_from_kwargs(**kw) -> LamConfig:
@@ -163,6 +178,7 @@ def config_from_kwargs(**kw) -> LamConfig:
         raise TypeError(f"unexpected LabelAnything arguments: {unknown}")
     kw["segment_example_logits"], kw["embeddings_per_example"] = resolve_examples(kw.get("segment_example_logits", False),
                                                                                   kw.get("embeddings_per_example"))
+    check_levels(kw.get("classification_levels", 1), kw["segment_example_logits"])
     cfg = LamConfig(**kw)
     if cfg.pool_side > cfg.grid:
         raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools {cfg.pool_side} x {cfg.pool_side} bins from a "

@@ -1358,6 +1358,12 @@ class LamEngine:
             L.add_cast(query32, pe32, hw, out16=imgpe16, dt=self.idti)
         tok = self.h2d(class_emb, torch.float32).reshape(b * c, d).contiguous()
         t32, t16 = self.two_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.tw", want_tokens=True)
+        levels = cfg.classification_levels == 2
+        if levels:
+            # coarse level (mask_decoder.py:345-346): the transformer's fp32 tokens before class_mlp against the fp32 D-channel stream
+            # before the upscaler, at the grid resolution
+            cls1 = self.f32("md.cls1", (b, c, g, g))
+            L.classify_wide(t32, img32, b, hw, c, d, cls1)
         # class_mlp (3 x Linear, ReLU between) -> prototypes
         h1 = self.dbuf("md.cm1", (b * c, d))
         L.gemm(t16, p[md + ".class_mlp.0.w"], bias=w[md + ".class_mlp.layers.0.bias"], out16=h1, act=L.ACT_RELU)
@@ -1403,6 +1409,11 @@ class LamEngine:
             L.classify_max(feat32, protos, fex, b, npix, nex, ncls, cf, seg)
             return seg
         seg = torch.empty(b, c, 4 * g, 4 * g, device=self.dev, dtype=torch.float32)
+        if levels:      # level_reducer over [fine logits, x4 enlargement of the coarse ones] (mask_decoder.py:358-362)
+            cls0 = self.f32("md.cls0", (b, c, 4 * g, 4 * g))
+            L.classify(feat32, protos, b, npix, c, cf, cls0)
+            L.level_reduce(cls0, cls1, w[md + ".level_reducer.weight"], w[md + ".level_reducer.bias"], b, c, g, g, seg)
+            return seg
         L.classify(feat32, protos, b, npix, c, cf, seg)
         return seg
 

@@ -297,6 +297,9 @@ class DecoderGraph:
             class_emb = examples.reshape(b, nex * ncls, d)
         c = class_emb.shape[1]
         toks, keys = self.two_way(md + ".transformer", query, self.dense_pe(g), class_emb.reshape(b * c, d), b, c, hw, want_tokens=True)
+        cls1 = None
+        if cfg.classification_levels == 2:   # coarse level: tokens before class_mlp, stream before the upscaler (mask_decoder.py:345-346)
+            cls1 = A.classify_wide(keys, toks, b, hw, c)
         pr = A.relu(self.lin(md + ".class_mlp.layers.0", toks))
         pr = A.relu(self.lin(md + ".class_mlp.layers.1", pr))
         pr = self.lin(md + ".class_mlp.layers.2", pr)
@@ -313,6 +316,9 @@ class DecoderGraph:
             seg = A.classify_max(feat, pr.reshape(b, nex, ncls, -1), fex, b, 16 * hw, nex, ncls)
             return seg.view(b, ncls, 4 * g, 4 * g)
         seg = A.classify(feat, pr.reshape(b, c, -1), b, 16 * hw, c)
+        if cls1 is not None:                  # level_reducer over [fine, x4 enlargement of coarse] (mask_decoder.py:358-362)
+            return A.level_reduce(seg.view(b, c, 4 * g, 4 * g), cls1.view(b, c, g, g), self.w[md + ".level_reducer.weight"],
+                                  self.w[md + ".level_reducer.bias"], b, c, g, g)
         return seg.view(b, c, 4 * g, 4 * g)
 
     # ---- post-processing (lam.py:383-453) --------------------------------------------------------------------------------------

@@ -167,6 +167,10 @@ def decoder_shapes(cfg: LamConfig) -> Shapes:
             s[f"{md}.spatial_convs.{3 * i}.bias"] = (ch,)
             if i < cfg.spatial_convs - 1:
                 _ln_shapes(s, f"{md}.spatial_convs.{3 * i + 1}", ch)
+    if cfg.classification_levels == 2:
+        # LAST, so that every other tensor of init_state_dict(cfg, seed) is the one of the classification_levels = 1 model
+        s[md + ".level_reducer.weight"] = (1, 2, 3, 3)                # (out, level, ky, kx): level 0 = fine, 1 = enlarged coarse
+        s[md + ".level_reducer.bias"] = (1,)
     return s
 
 
