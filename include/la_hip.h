@@ -649,6 +649,30 @@ int la_level_reduce(const float* cls0, const float* cls1, const float* w, const 
 int la_level_reduce_bwd(const float* dseg, const float* cls0, const float* cls1, const float* w, int B, int C, int gh, int gw, float* dcls0,
                         float* dcls1, float* dw, float* dbias, void* stream);
 
+/* ---- conv_classification (prototype_tconv + the 5 x 5 per-episode correlation) ----------------------------------------------------------
+ * prototype_tconv = 2 x ConvTranspose2d(cf, cf, 3, stride 1, padding 0, bias=False) on every prototype as a cf x 1 x 1 map
+ * (mask_decoder.py:257-271,303-304).  protos fp32 [BC, cf]; W1, W2 the ConvTranspose2d weights [cf(in), cf(out), 3, 3]:
+ *   k1[bc][m][i][j] = sum_in protos[bc][in] W1[in][m][i][j]                               (written, [BC, cf, 3, 3]: the backward reads it)
+ *   K[bc][y*5+x][o] = sum_m sum_ij k1[bc][m][y-i][x-j] W2[m][o][i][j]                     ([BC, 25, cf]: tap-major, channel-minor)
+ * fp32 multiply-add in a fixed order.  cf a multiple of 32 up to 256; anything else is refused with a message.
+ * Backward from dK: dk1 [BC, cf, 3, 3] (scratch) and dprotos [BC, cf] are WRITTEN, dW1 and dW2 ACCUMULATED into the caller's gradient
+ * slots, every element by one thread with the prototypes in index order (no atomics). */
+int la_proto_kernels(const float* protos, const float* W1, const float* W2, int BC, int cf, float* k1, float* K, void* stream);
+int la_proto_kernels_bwd(const float* dK, const float* protos, const float* k1, const float* W1, const float* W2, int BC, int cf, float* dk1,
+                         float* dprotos, float* dW1, float* dW2, void* stream);
+
+/* F.conv2d(q, K_b, padding=2) per episode (mask_decoder.py:305-307): seg[b][c][y][x] = sum_d sum_uv feat[b][y+u-2][x+v-2][d] K[b][c][u*5+v][d],
+ * taps outside the H x W map absent.  feat fp32 NHWC [B, H, W, cf], K fp32 [B, C, 25, cf], seg fp32 [B, C, H, W]; the K of episode b meets
+ * only episode b.  Exact-fp32 MFMA over the channels, then the 25 taps added in (u, v) order; class pairs in one launch, an odd
+ * last class in a second.  Any H, W, C >= 1; cf a multiple of 32 up
+ * to 256; feat and K 16-byte aligned; anything else is refused with a message.
+ * Backward: dfeat [B, H, W, cf] (the same correlation with flipped taps, summed over the classes) and dK [B, C, 25, cf]
+ * (dK[b][c][uv][d] = sum_yx dseg[b][c][y][x] feat[b][y+u-2][x+v-2][d]) are both WRITTEN.  The pixel sum of dK has an order fixed by the shape
+ * (one workgroup per episode, class pair and 32 channels; no atomics), so two runs agree bit for bit. */
+int la_classify_conv(const float* feat, const float* K, int B, int C, int H, int W, int cf, float* seg, void* stream);
+int la_classify_conv_bwd(const float* dseg, const float* feat, const float* K, int B, int C, int H, int W, int cf, float* dfeat, float* dK,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

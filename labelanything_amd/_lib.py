@@ -71,6 +71,7 @@ EXPORTS = [
     "la_rle_scan", "la_rle_decode", "la_rle_prompt_masks", "la_rle_ground_truth", "la_rle_points",
     "la_region_mean", "la_classify_max", "la_region_mean_bwd", "la_classify_max_bwd",
     "la_classify_wide", "la_classify_wide_bwd", "la_level_reduce", "la_level_reduce_bwd",
+    "la_proto_kernels", "la_proto_kernels_bwd", "la_classify_conv", "la_classify_conv_bwd",
 ]
 
 
@@ -964,3 +965,39 @@ def level_reduce_bwd(dseg, cls0, cls1, w, b: int, c: int, gh: int, gw: int, dcls
            dw=(dw, 18), dbias=(dbias, 1))
     _check(lib().la_level_reduce_bwd(_ptr(dseg), _ptr(cls0), _ptr(cls1), _ptr(w), C.c_int(b), C.c_int(c), C.c_int(gh), C.c_int(gw),
                                      _ptr(dcls0), _ptr(dcls1), _ptr(dw), _ptr(dbias), _stream()), "la_level_reduce_bwd")
+
+
+# ---- conv_classification (prototype_tconv + the 5 x 5 per-episode correlation, csrc/convcls.hip) ----------------------------------------
+def proto_kernels(protos, w1, w2, bc: int, cf: int, k1, k) -> None:
+    """protos [bc, cf] through the two ConvTranspose2d(cf, cf, 3) weights w1, w2 (in, out, ky, kx): k1 [bc, cf, 3, 3] (kept for the
+    backward) and k [bc, 25, cf], tap-major and channel-minor.  cf a multiple of 32 up to 256: the library refuses anything else."""
+    _f32c(protos, w1, w2, k1, k)
+    _numel("proto_kernels", protos=(protos, bc * cf), w1=(w1, 9 * cf * cf), w2=(w2, 9 * cf * cf), k1=(k1, bc * cf * 9), k=(k, bc * 25 * cf))
+    _check(lib().la_proto_kernels(_ptr(protos), _ptr(w1), _ptr(w2), C.c_int(bc), C.c_int(cf), _ptr(k1), _ptr(k), _stream()),
+           "la_proto_kernels")
+
+
+def proto_kernels_bwd(dk, protos, k1, w1, w2, bc: int, cf: int, dk1, dprotos, dw1, dw2) -> None:
+    """dk1 [bc, cf, 3, 3] (scratch) and dprotos [bc, cf] are written; dw1, dw2 ACCUMULATED."""
+    _f32c(dk, protos, k1, w1, w2, dk1, dprotos, dw1, dw2)
+    _numel("proto_kernels_bwd", dk=(dk, bc * 25 * cf), protos=(protos, bc * cf), k1=(k1, bc * cf * 9), w1=(w1, 9 * cf * cf),
+           w2=(w2, 9 * cf * cf), dk1=(dk1, bc * cf * 9), dprotos=(dprotos, bc * cf), dw1=(dw1, 9 * cf * cf), dw2=(dw2, 9 * cf * cf))
+    _check(lib().la_proto_kernels_bwd(_ptr(dk), _ptr(protos), _ptr(k1), _ptr(w1), _ptr(w2), C.c_int(bc), C.c_int(cf), _ptr(dk1),
+                                      _ptr(dprotos), _ptr(dw1), _ptr(dw2), _stream()), "la_proto_kernels_bwd")
+
+
+def classify_conv(feat, k, b: int, c: int, h: int, w: int, cf: int, seg) -> None:
+    """seg [b, c, h, w] = the 5 x 5 cross-correlation (zero padding 2) of feat NHWC [b, h, w, cf] with episode b's kernels k [b, c, 25, cf]."""
+    _f32c(feat, k, seg)
+    _numel("classify_conv", feat=(feat, b * h * w * cf), k=(k, b * c * 25 * cf), seg=(seg, b * c * h * w))
+    _check(lib().la_classify_conv(_ptr(feat), _ptr(k), C.c_int(b), C.c_int(c), C.c_int(h), C.c_int(w), C.c_int(cf), _ptr(seg), _stream()),
+           "la_classify_conv")
+
+
+def classify_conv_bwd(dseg, feat, k, b: int, c: int, h: int, w: int, cf: int, dfeat, dk) -> None:
+    """dfeat [b, h, w, cf] and dk [b, c, 25, cf] are both written; the same input gives the same bits."""
+    _f32c(dseg, feat, k, dfeat, dk)
+    _numel("classify_conv_bwd", dseg=(dseg, b * c * h * w), feat=(feat, b * h * w * cf), k=(k, b * c * 25 * cf),
+           dfeat=(dfeat, b * h * w * cf), dk=(dk, b * c * 25 * cf))
+    _check(lib().la_classify_conv_bwd(_ptr(dseg), _ptr(feat), _ptr(k), C.c_int(b), C.c_int(c), C.c_int(h), C.c_int(w), C.c_int(cf),
+                                      _ptr(dfeat), _ptr(dk), _stream()), "la_classify_conv_bwd")

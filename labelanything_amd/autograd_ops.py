@@ -16,6 +16,8 @@ index_select, expand); every arithmetic node of the prompt encoder / mask decode
     bilinear      la_bilinear                          bwd: la_bilinear_bwd
     classify_wide la_classify_wide                     bwd: la_classify_wide_bwd       (classification_levels = 2: the coarse level)
     level_reduce  la_level_reduce                      bwd: la_level_reduce_bwd        (level_reducer over [fine, enlarged coarse])
+    proto_kernels la_proto_kernels                     bwd: la_proto_kernels_bwd       (conv_classification: prototype_tconv)
+    classify_conv la_classify_conv                     bwd: la_classify_conv_bwd       (conv_classification: 5 x 5 correlation per episode)
 
 All tensors are fp32, contiguous, on the device; 2-D activations are [rows, channels] (NHWC rows), as in the inference engine.
 Reference graph: label_anything/models/{common,transformer,prompt_encoder,mask_decoder}.py under experiment/utils.py:266-303.
@@ -554,6 +556,66 @@ class _LevelReduce(Function):
 
 def level_reduce(cls0: Tensor, cls1: Tensor, w: Tensor, bias: Tensor, bsz: int, c: int, gh: int, gw: int) -> Tensor:
     return _LevelReduce.apply(cls0, cls1, w, bias, bsz, c, gh, gw)
+
+
+class _ProtoKernels(Function):
+    """prototype_tconv (mask_decoder.py:257-271,303-304): protos [BC, cf] -> kernels [BC, 25, cf]; w1, w2 are the two ConvTranspose2d weights
+    (cf, cf, 3, 3).  Their gradients go straight into the gradient sink when one is installed."""
+
+    @staticmethod
+    def forward(ctx, protos, w1, w2):
+        protos, w1, w2 = _c(protos), _c(w1), _c(w2)
+        bc, cf = protos.shape
+        k1 = protos.new_empty(bc, cf, 3, 3)
+        kern = protos.new_empty(bc, 25, cf)
+        L.proto_kernels(protos, w1, w2, bc, cf, k1, kern)
+        ctx.save_for_backward(protos, k1, w1, w2)
+        return kern
+
+    @staticmethod
+    def backward(ctx, dkern):
+        protos, k1, w1, w2 = ctx.saved_tensors
+        bc, cf = protos.shape
+        dk1, dprotos = torch.empty_like(k1), torch.empty_like(protos)
+        g1, g2 = SINK.find(w1), SINK.find(w2)
+        dw1 = dw2 = None
+        if g1 is None:
+            dw1 = torch.zeros_like(w1)
+        if g2 is None:
+            dw2 = torch.zeros_like(w2)
+        L.proto_kernels_bwd(_c(dkern), protos, k1, w1, w2, bc, cf, dk1, dprotos, g1 if g1 is not None else dw1, g2 if g2 is not None else dw2)
+        return dprotos, dw1, dw2
+
+
+def proto_kernels(protos: Tensor, w1: Tensor, w2: Tensor) -> Tensor:
+    return _ProtoKernels.apply(protos, w1, w2)
+
+
+class _ClassifyConv(Function):
+    """feat [B*H*W, cf] NHWC rows, kern [B*C, 25, cf] -> [B, C, H, W]: F.conv2d(feat_b, kern_b, padding=2) per episode
+    (mask_decoder.py:305-307)."""
+
+    @staticmethod
+    def forward(ctx, feat, kern, bsz, c, h, wd):
+        feat, kern = _c(feat), _c(kern)
+        cf = feat.shape[1]
+        seg = feat.new_empty(bsz, c, h, wd)
+        L.classify_conv(feat, kern, bsz, c, h, wd, cf, seg)
+        ctx.save_for_backward(feat, kern)
+        ctx.dims = (bsz, c, h, wd, cf)
+        return seg
+
+    @staticmethod
+    def backward(ctx, dseg):
+        feat, kern = ctx.saved_tensors
+        bsz, c, h, wd, cf = ctx.dims
+        dfeat, dkern = torch.empty_like(feat), torch.empty_like(kern)
+        L.classify_conv_bwd(_c(dseg), feat, kern, bsz, c, h, wd, cf, dfeat, dkern)
+        return dfeat, dkern, None, None, None, None
+
+
+def classify_conv(feat: Tensor, kern: Tensor, bsz: int, c: int, h: int, wd: int) -> Tensor:
+    return _ClassifyConv.apply(feat, kern, bsz, c, h, wd)
 
 
 class _Bilinear(Function):

@@ -66,7 +66,7 @@ class LamConfig:
     """Keyword surface of ``LabelAnything.__init__`` (build_lam.py:470-498), on-path subset.
 
     Off-path switches (few_type=Affinity, OneWay/Identity fusion, binary, pyramids,
-    conv_classification, class_embedding_dim, TokenPool, embedding_extraction) are
+    class_embedding_dim, TokenPool, embedding_extraction) are
     accepted only at their default value; anything else raises NotImplementedError.
     """
 
@@ -96,6 +96,14 @@ class LamConfig:
     # (mask_decoder.py:204,345-346,358-362; parameters/trainval/pascal/mae_levels.yaml).  The reference's forward stacks exactly two
     # levels, so 1 and 2 are the values that can run.  Adds mask_decoder.level_reducer.{weight,bias}.
     classification_levels: int = 1
+    # Channel widths of the mask decoder's upscaler (mask_decoder.py:198-255): output_upscaling.0 gives embed_dim // max(r // 2, 1)
+    # channels, output_upscaling.3, class_mlp's last layer and the spatial convolutions embed_dim // r.  1 and 8 are built
+    # (parameters/trainval/pascal/mae_nodown.yaml uses 1).
+    classification_layer_downsample_rate: int = 8
+    # True: the decoder owns prototype_tconv = 2 x ConvTranspose2d(cf, cf, 3, bias=False), which turn every prototype into a cf x 5 x 5
+    # kernel; the logits are the 5 x 5 cross-correlation of the feature map with it (mask_decoder.py:257-271,299-307).  Adds
+    # mask_decoder.prototype_tconv.{0,1}.weight.
+    conv_classification: bool = False
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -108,6 +116,16 @@ class LamConfig:
     @property
     def lam_neck(self) -> bool:
         return self.image_embed_dim != self.embed_dim
+
+    @property
+    def up_mid(self) -> int:
+        """Channels after output_upscaling.0 (mask_decoder.py:198-202,210)."""
+        return self.embed_dim // max(self.classification_layer_downsample_rate // 2, 1)
+
+    @property
+    def class_width(self) -> int:
+        """Channels of the map the pixels are classified on, = the prototype width (mask_decoder.py:218,226)."""
+        return self.embed_dim // self.classification_layer_downsample_rate
 
     @property
     def encoder_spec(self) -> Optional[EncoderSpec]:
@@ -129,11 +147,11 @@ class LamConfig:
 _OFF_PATH_DEFAULTS = dict(
     class_embedding_dim=None,
     encoder_attention_downsample_rate=2, decoder_attention_downsample_rate=2,
-    classification_layer_downsample_rate=8, use_support_features_in_prompt_encoder=True,
+    use_support_features_in_prompt_encoder=True,
     fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
     dropout=0.0, binary=False,
-    conv_classification=False, prompt_encoder=None, embedding_extraction=None,
+    prompt_encoder=None, embedding_extraction=None,
 )
 
 
@@ -161,6 +179,27 @@ def check_levels(levels, segment_example_logits) -> None:
                                   "`pooler` embedding extraction and the `masks` loss, neither of which is built")
 
 
+def check_classification(rate, conv_classification, segment_example_logits, levels) -> None:
+    """The one check of ``classification_layer_downsample_rate`` and ``conv_classification`` (config_from_kwargs and Lam)."""
+    if isinstance(rate, bool) or not isinstance(rate, int) or rate not in (1, 2, 4, 8):
+        raise ValueError(f"classification_layer_downsample_rate={rate!r}: a power of two from 1 to 8 (it divides embed_dim twice, "
+                         f"mask_decoder.py:198-226)")
+    if rate not in (1, 8):
+        raise NotImplementedError(f"classification_layer_downsample_rate={rate}: only 1 and 8, the values of the reference's recipes, "
+                                  f"are built")
+    if conv_classification and segment_example_logits:
+        raise NotImplementedError("conv_classification together with segment_example_logits / embeddings_per_example is not built: the "
+                                  "reference's _classify groups the N C kernels by C there (mask_decoder.py:301-305), mixing examples and "
+                                  "classes")
+    if rate != 8 and segment_example_logits:
+        raise NotImplementedError(f"classification_layer_downsample_rate={rate} together with segment_example_logits / "
+                                  f"embeddings_per_example is not built: la_classify_max takes prototype widths up to 64, and no "
+                                  f"reference recipe combines them")
+    if levels == 2 and (conv_classification or rate != 8):
+        raise NotImplementedError("classification_levels=2 together with conv_classification or classification_layer_downsample_rate != 8 "
+                                  "is not built: no reference recipe combines them")
+
+
 def config_from_kwargs(**kw) -> LamConfig:
     """Build a LamConfig from reference-style kwargs, rejecting off-path ablation switches."""
     kw = dict(kw)
@@ -179,6 +218,9 @@ def config_from_kwargs(**kw) -> LamConfig:
     kw["segment_example_logits"], kw["embeddings_per_example"] = resolve_examples(kw.get("segment_example_logits", False),
                                                                                   kw.get("embeddings_per_example"))
     check_levels(kw.get("classification_levels", 1), kw["segment_example_logits"])
+    kw["conv_classification"] = bool(kw.get("conv_classification", False))
+    check_classification(kw.get("classification_layer_downsample_rate", 8), kw["conv_classification"], kw["segment_example_logits"],
+                         kw.get("classification_levels", 1))
     cfg = LamConfig(**kw)
     if cfg.pool_side > cfg.grid:
         raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools {cfg.pool_side} x {cfg.pool_side} bins from a "

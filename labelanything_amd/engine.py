@@ -1369,11 +1369,11 @@ class LamEngine:
         L.gemm(t16, p[md + ".class_mlp.0.w"], bias=w[md + ".class_mlp.layers.0.bias"], out16=h1, act=L.ACT_RELU)
         h2 = self.dbuf("md.cm2", (b * c, d))
         L.gemm(h1, p[md + ".class_mlp.1.w"], bias=w[md + ".class_mlp.layers.1.bias"], out16=h2, act=L.ACT_RELU)
-        cf = d // 8
+        cf = cfg.class_width
         protos = self.f32("md.protos", (b * c, cf))
         L.gemm(h2, p[md + ".class_mlp.2.w"], bias=w[md + ".class_mlp.layers.2.bias"], out32=protos)
         # output_upscaling: ConvT(k2,s2) -> LN2d -> GELU -> ConvT(k2,s2), both as pixel-shuffle GEMMs
-        c1 = d // 4
+        c1 = cfg.up_mid
         up1 = self.f32("md.up1", (b * 4 * hw, c1))
         if fused:       # the stream itself is the (fp32) operand: there is no separate copy to read
             L.gemm(img32, p[md + ".up0.w"], bias=w[md + ".output_upscaling.0.bias"], out32=up1, map=L.MAP_CONVT2X2, p=(g, g, c1, 0, 0))
@@ -1413,6 +1413,15 @@ class LamEngine:
             cls0 = self.f32("md.cls0", (b, c, 4 * g, 4 * g))
             L.classify(feat32, protos, b, npix, c, cf, cls0)
             L.level_reduce(cls0, cls1, w[md + ".level_reducer.weight"], w[md + ".level_reducer.bias"], b, c, g, g, seg)
+            return seg
+        if cfg.conv_classification:     # prototype_tconv -> one cf x 5 x 5 kernel per class, F.conv2d(padding=2) per episode (:302-307)
+            k1 = self.f32("md.k1", (b * c, cf, 3, 3))
+            kern = self.f32("md.kern", (b, c, 25, cf))
+            L.proto_kernels(protos, w[md + ".prototype_tconv.0.weight"], w[md + ".prototype_tconv.1.weight"], b * c, cf, k1, kern)
+            L.classify_conv(feat32, kern, b, c, 4 * g, 4 * g, cf, seg)
+            return seg
+        if cf > 64:                     # the same product over a wide map (downsample rate 1): la_classify takes widths up to 64
+            L.classify_wide(protos, feat32, b, npix, c, cf, seg)
             return seg
         L.classify(feat32, protos, b, npix, c, cf, seg)
         return seg

@@ -21,7 +21,7 @@ from typing import Any, Dict, Optional
 import torch
 from torch import nn
 
-from .config import LamConfig, ENCODER_SPECS, check_levels, config_from_kwargs, resolve_examples
+from .config import LamConfig, ENCODER_SPECS, check_classification, check_levels, config_from_kwargs, resolve_examples
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
 from . import _lib as L
@@ -83,10 +83,17 @@ class Lam(nn.Module):
     def __init__(self, cfg: LamConfig, seed: Optional[int] = None, compute_dtype: torch.dtype = torch.float16,
                  decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT,
                  segment_example_logits: Optional[bool] = None, embeddings_per_example: Optional[int] = None,
-                 classification_levels: Optional[int] = None):
+                 classification_levels: Optional[int] = None, classification_layer_downsample_rate: Optional[int] = None,
+                 conv_classification: Optional[bool] = None):
         """segment_example_logits / embeddings_per_example: the per-example family on top of ``cfg`` (resolved as build_lam.py:145-148
-        does); classification_levels: 2 adds the two-level head (mask_decoder.py:204,345-362).  Left at None they keep what ``cfg`` says."""
+        does); classification_levels: 2 adds the two-level head (mask_decoder.py:204,345-362); classification_layer_downsample_rate /
+        conv_classification: the decoder's channel widths and the 5 x 5 prototype kernels (mask_decoder.py:198-271,299-307).  Left at None
+        they keep what ``cfg`` says."""
         super().__init__()
+        if classification_layer_downsample_rate is not None:
+            cfg = dataclasses.replace(cfg, classification_layer_downsample_rate=classification_layer_downsample_rate)
+        if conv_classification is not None:
+            cfg = dataclasses.replace(cfg, conv_classification=bool(conv_classification))
         if classification_levels is not None:
             cfg = dataclasses.replace(cfg, classification_levels=classification_levels)
         if segment_example_logits is not None or embeddings_per_example is not None:
@@ -96,6 +103,8 @@ class Lam(nn.Module):
         if cfg.pool_side > cfg.grid:
             raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools more bins than the {cfg.grid} x {cfg.grid} grid has")
         check_levels(cfg.classification_levels, cfg.segment_example_logits)
+        check_classification(cfg.classification_layer_downsample_rate, cfg.conv_classification, cfg.segment_example_logits,
+                             cfg.classification_levels)
         self.cfg = cfg
         self.image_size = cfg.image_size
         self.custom_preprocess = cfg.custom_preprocess
@@ -722,9 +731,9 @@ class LabelAnything(nn.Module, PyTorchModelHubMixin):
                  fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
                  transformer_keys_are_images=True, transformer_feature_size=None, class_encoder=None,
                  segment_example_logits=False, dropout: float = 0.0, binary=False, custom_preprocess=True,
-                 classification_levels: int = 1):
-        """classification_levels is not an argument of the reference's class (its builders take it, build_lam.py:118,251): it is accepted
-        here so that a mae_levels model round-trips through config.json."""
+                 classification_levels: int = 1, conv_classification: bool = False):
+        """classification_levels and conv_classification are not arguments of the reference's class (its builders take them,
+        build_lam.py:118,251): they are accepted here so that a mae_levels / mae_nodown model round-trips through config.json."""
         super().__init__()
         cfg = dict(self.config)
         enc = cfg.pop("encoder")

@@ -315,6 +315,11 @@ class DecoderGraph:
             fex = flag_examples.reshape(b, nex, ncls).to(device=feat.device, dtype=torch.uint8).contiguous()
             seg = A.classify_max(feat, pr.reshape(b, nex, ncls, -1), fex, b, 16 * hw, nex, ncls)
             return seg.view(b, ncls, 4 * g, 4 * g)
+        if cfg.conv_classification:           # prototype_tconv + F.conv2d(padding=2) per episode (mask_decoder.py:302-307)
+            kern = A.proto_kernels(pr, self.w[md + ".prototype_tconv.0.weight"], self.w[md + ".prototype_tconv.1.weight"])
+            return A.classify_conv(feat, kern, b, c, 4 * g, 4 * g)
+        if pr.shape[1] > 64:                  # downsample rate 1: the same product on the wide kernel (la_classify takes up to 64 channels)
+            return A.classify_wide(feat, pr, b, 16 * hw, c).view(b, c, 4 * g, 4 * g)
         seg = A.classify(feat, pr.reshape(b, c, -1), b, 16 * hw, c)
         if cls1 is not None:                  # level_reducer over [fine, x4 enlargement of coarse] (mask_decoder.py:358-362)
             return A.level_reduce(seg.view(b, c, 4 * g, 4 * g), cls1.view(b, c, g, g), self.w[md + ".level_reducer.weight"],

@@ -149,19 +149,20 @@ def decoder_shapes(cfg: LamConfig) -> Shapes:
         _attn_mlp_block_shapes(s, pe + ".example_attention", d, d // 2, mlp)
     md = "mask_decoder"
     _two_way_shapes(s, md + ".transformer", d, mlp)
-    s[md + ".output_upscaling.0.weight"] = (d, d // 4, 2, 2)      # ConvTranspose2d: (Cin, Cout, kh, kw)
-    s[md + ".output_upscaling.0.bias"] = (d // 4,)
-    _ln_shapes(s, md + ".output_upscaling.1", d // 4)
-    s[md + ".output_upscaling.3.weight"] = (d // 4, d // 8, 2, 2)
-    s[md + ".output_upscaling.3.bias"] = (d // 8,)
+    c1, cf = cfg.up_mid, cfg.class_width                          # D // 4 and D // 8 at the default downsample rate of 8
+    s[md + ".output_upscaling.0.weight"] = (d, c1, 2, 2)          # ConvTranspose2d: (Cin, Cout, kh, kw)
+    s[md + ".output_upscaling.0.bias"] = (c1,)
+    _ln_shapes(s, md + ".output_upscaling.1", c1)
+    s[md + ".output_upscaling.3.weight"] = (c1, cf, 2, 2)
+    s[md + ".output_upscaling.3.bias"] = (cf,)
     s[md + ".class_mlp.layers.0.weight"] = (d, d)
     s[md + ".class_mlp.layers.0.bias"] = (d,)
     s[md + ".class_mlp.layers.1.weight"] = (d, d)
     s[md + ".class_mlp.layers.1.bias"] = (d,)
-    s[md + ".class_mlp.layers.2.weight"] = (d // 8, d)
-    s[md + ".class_mlp.layers.2.bias"] = (d // 8,)
+    s[md + ".class_mlp.layers.2.weight"] = (cf, d)
+    s[md + ".class_mlp.layers.2.bias"] = (cf,)
     if cfg.spatial_convs:
-        ch = d // 8
+        ch = cf
         for i in range(cfg.spatial_convs):
             s[f"{md}.spatial_convs.{3 * i}.weight"] = (ch, ch, 3, 3)
             s[f"{md}.spatial_convs.{3 * i}.bias"] = (ch,)
@@ -171,6 +172,10 @@ def decoder_shapes(cfg: LamConfig) -> Shapes:
         # LAST, so that every other tensor of init_state_dict(cfg, seed) is the one of the classification_levels = 1 model
         s[md + ".level_reducer.weight"] = (1, 2, 3, 3)                # (out, level, ky, kx): level 0 = fine, 1 = enlarged coarse
         s[md + ".level_reducer.bias"] = (1,)
+    if cfg.conv_classification:
+        # LAST as well (never together with the level reducer): ConvTranspose2d(cf, cf, 3, bias=False) weights, (in, out, ky, kx)
+        s[md + ".prototype_tconv.0.weight"] = (cf, cf, 3, 3)
+        s[md + ".prototype_tconv.1.weight"] = (cf, cf, 3, 3)
     return s
 
 
@@ -182,6 +187,12 @@ def model_shapes(cfg: LamConfig) -> Shapes:
     s.update(decoder_shapes(cfg))
     return s
 
+
+# prototype_tconv.{0,1}: std = 1 / sqrt(9 cf), the fan-in of a 3 x 3 convolution over cf channels.  An entry of the composed 5 x 5 kernel
+# sums cf products in the first layer and up to 9 cf in the second, which makes it |e| / 3 at the centre tap and less towards the rim; a
+# logit then sums 25 cf products of features and kernel entries.  Measured on the fixtures (tests/golden/convcls_r*.json, "scale"): the
+# low-resolution logits have an rms of 3.6 (max 12) at cf = 256 and 1.7 (max 6) at cf = 32, next to 5.4 for the plain dot product.
+PROTOTYPE_TCONV_FAN = 9
 
 _NORM_TAGS = (".norm", ".layernorm", "neck.1.", "neck.3.", "mask_downscaling.1.", "mask_downscaling.4.",
               "output_upscaling.1.", "spatial_convs.1.", "spatial_convs.4.", "spatial_convs.7.")
@@ -217,6 +228,8 @@ def init_state_dict(cfg: LamConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
         else:
             if "output_upscaling" in name and len(shape) == 4:
                 fan_in = shape[0]                    # ConvTranspose2d (Cin, Cout, k, k), stride == k: one tap per output
+            elif "prototype_tconv" in name:
+                fan_in = PROTOTYPE_TCONV_FAN * shape[0]
             else:
                 fan_in = int(math.prod(shape[1:]))
             t = torch.randn(shape, generator=gen) / math.sqrt(max(fan_in, 1))
