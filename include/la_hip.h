@@ -673,6 +673,32 @@ int la_classify_conv(const float* feat, const float* K, int B, int C, int H, int
 int la_classify_conv_bwd(const float* dseg, const float* feat, const float* K, int B, int C, int H, int W, int cf, float* dfeat, float* dK,
                          void* stream);
 
+/* embedding_extraction = "cross_attention": the attention of EmbeddingTransformer.forward (prompt_encoder.py:289-298) inside
+ * OneWayAttentionBlock.forward (transformer.py:140-147), i.e. Attention.forward (common.py:105-146) with n learned queries per (episode,
+ * class) pair over the M hw stream rows of the pair, 8 heads of width D / 16 - FOLDED so that the stream is never projected: with
+ * q = q_proj(E), the folded query of head h and query j is qt[h n + j] = W_k,h^T q_hj / sqrt(hd) in R^D (the key bias is constant along
+ * the keys and cancels in the softmax), pooled[h n + j] = sum_l softmax_l(qt[h n + j] . x_l) x_l, and the head output is
+ * W_v,h pooled[h n + j] + b_v,h.  R = 8 n rows per pair, in (head, query) order.  NO KEY IS MASKED: with only a key mask the reference
+ * builds an all-False score mask (common.py:120-124), so padded supports take part in the softmax; this port reproduces that.
+ *
+ * la_extract_pool: x fp32 NHWC [B M C, hw, D], slabs in (b, m, c) order; qt fp32 [B C, R, D], or ONE [R, D] block for every pair with
+ * qt_broadcast != 0; out fp32 [B C, R, D], out[z][j][:] = sum_l softmax_l(qt[z][j] . x[z][l]) x[z][l] over the M hw rows l of pair
+ * z = b C + c, slab m of which starts at row ((b M + m) C + c) hw.  One pass over the stream with an online softmax (for n > 4 one pass
+ * per 32 rows of qt), both products on the exact-fp32 MFMA, expf; nothing projected or transposed is written.  The rows of a pair are
+ * split into pieces of `split_rows` rows, one workgroup each, which leave (max, sum, accumulator) partials in `scratch`; a second small
+ * launch merges them in index order.  la_extract_pool_plan gives split_rows, the number of pieces and the scratch size in floats PER
+ * PAIR (scratch holds B C times that); they depend on (M, hw, D, R) only, so a pair computed alone or inside a batch gives the same
+ * bits.  D in {64, 128, 256}, 1 <= n <= 16, any hw, M >= 1; x, qt, scratch 16-byte aligned; anything else is refused with a message
+ * and nothing is written.
+ * la_extract_fold: q fp32 [BC n, D / 2] (= q_proj(E)), Wk fp32 [D / 2, D] (k_proj.weight) -> qt [BC, R, D].
+ * la_extract_unfold: pooled fp32 [BC, R, D], Wv fp32 [D / 2, D], bv [D / 2] -> o fp32 [BC n, D / 2], the recombined heads that
+ * out_proj takes (common.py:144-146). */
+int la_extract_pool_plan(int M, int hw, int D, int R, int* split_rows, int* nsplit, long long* scratch_floats_per_pair);
+int la_extract_pool(const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n, float* scratch, float* out,
+                    void* stream);
+int la_extract_fold(const float* q, const float* Wk, int BC, int n, int D, float* qt, void* stream);
+int la_extract_unfold(const float* pooled, const float* Wv, const float* bv, int BC, int n, int D, float* o, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,7 @@ EXPORTS = [
     "la_region_mean", "la_classify_max", "la_region_mean_bwd", "la_classify_max_bwd",
     "la_classify_wide", "la_classify_wide_bwd", "la_level_reduce", "la_level_reduce_bwd",
     "la_proto_kernels", "la_proto_kernels_bwd", "la_classify_conv", "la_classify_conv_bwd",
+    "la_extract_pool_plan", "la_extract_pool", "la_extract_fold", "la_extract_unfold",
 ]
 
 
@@ -1001,3 +1002,48 @@ def classify_conv_bwd(dseg, feat, k, b: int, c: int, h: int, w: int, cf: int, df
            dfeat=(dfeat, b * h * w * cf), dk=(dk, b * c * 25 * cf))
     _check(lib().la_classify_conv_bwd(_ptr(dseg), _ptr(feat), _ptr(k), C.c_int(b), C.c_int(c), C.c_int(h), C.c_int(w), C.c_int(cf),
                                       _ptr(dfeat), _ptr(dk), _stream()), "la_classify_conv_bwd")
+
+
+# ---- embedding_extraction = "cross_attention" (the folded attention over the stream, csrc/extract.hip) ---------------------------------
+EXTRACT_HEADS = 8
+
+
+def extract_pool_plan(m: int, hw: int, d: int, r: int):
+    """(split_rows, nsplit, scratch floats per pair) of ``extract_pool`` for m slabs of hw rows, width d and r = 8 n folded queries: the
+    rows of a pair are cut into nsplit pieces of split_rows rows.  A function of these four sizes only."""
+    split, ns, per = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _check(lib().la_extract_pool_plan(C.c_int(m), C.c_int(hw), C.c_int(d), C.c_int(r), C.byref(split), C.byref(ns), C.byref(per)),
+           "la_extract_pool_plan")
+    return split.value, ns.value, per.value
+
+
+def extract_pool(x, qt, b: int, m: int, c: int, hw: int, d: int, n: int, scratch, out) -> None:
+    """out [b c, 8 n, d] = softmax-weighted means of the m hw stream rows of every pair under the folded queries qt ([b c, 8 n, d], or
+    one [8 n, d] block for all pairs).  scratch: fp32, at least b c times the per-pair size of ``extract_pool_plan``."""
+    _f32c(x, qt, scratch, out)
+    r = EXTRACT_HEADS * n
+    bcast = qt.numel() == r * d and b * c != 1
+    if x.numel() != b * m * c * hw * d or out.numel() != b * c * r * d or qt.numel() not in (r * d, b * c * r * d):
+        raise ValueError(f"extract_pool: x must hold [{b * m * c}, {hw}, {d}], qt [{b * c}, {r}, {d}] or [{r}, {d}] and out [{b * c}, {r}, {d}] "
+                         f"elements (got {x.numel()}, {qt.numel()}, {out.numel()})")
+    if 1 <= n <= 16 and d in (64, 128, 256):
+        need = b * c * extract_pool_plan(m, hw, d, r)[2]
+        if scratch.numel() < need:
+            raise ValueError(f"extract_pool: scratch holds {scratch.numel()} floats, {need} needed")
+    _check(lib().la_extract_pool(_ptr(x), _ptr(qt), C.c_int(1 if bcast else 0), C.c_int(b), C.c_int(m), C.c_int(c), C.c_int(hw), C.c_int(d),
+                                 C.c_int(n), _ptr(scratch), _ptr(out), _stream()), "la_extract_pool")
+
+
+def extract_fold(q, wk, bc: int, n: int, d: int, qt) -> None:
+    """qt [bc, 8 n, d], row h n + j = W_k,h^T q[z n + j, head h] / sqrt(d / 16)."""
+    _f32c(q, wk, qt)
+    _numel("extract_fold", q=(q, bc * n * (d // 2)), wk=(wk, (d // 2) * d), qt=(qt, bc * EXTRACT_HEADS * n * d))
+    _check(lib().la_extract_fold(_ptr(q), _ptr(wk), C.c_int(bc), C.c_int(n), C.c_int(d), _ptr(qt), _stream()), "la_extract_fold")
+
+
+def extract_unfold(pooled, wv, bv, bc: int, n: int, d: int, o) -> None:
+    """o [bc n, d / 2]: column h hd + e of row z n + j = W_v[h hd + e] . pooled[z, h n + j] + b_v[h hd + e]."""
+    _f32c(pooled, wv, bv, o)
+    _numel("extract_unfold", pooled=(pooled, bc * EXTRACT_HEADS * n * d), wv=(wv, (d // 2) * d), bv=(bv, d // 2), o=(o, bc * n * (d // 2)))
+    _check(lib().la_extract_unfold(_ptr(pooled), _ptr(wv), _ptr(bv), C.c_int(bc), C.c_int(n), C.c_int(d), _ptr(o), _stream()),
+           "la_extract_unfold")

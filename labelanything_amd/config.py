@@ -66,8 +66,8 @@ class LamConfig:
     """Keyword surface of ``LabelAnything.__init__`` (build_lam.py:470-498), on-path subset.
 
     Off-path switches (few_type=Affinity, OneWay/Identity fusion, binary, pyramids,
-    class_embedding_dim, TokenPool, embedding_extraction) are
-    accepted only at their default value; anything else raises NotImplementedError.
+    class_embedding_dim, TokenPool) are accepted only at their default value; anything else raises NotImplementedError.
+    ``embedding_extraction`` takes None and "cross_attention"; every other value ("pooler" ...) raises NotImplementedError.
     """
 
     encoder: Optional[str] = "vit_b"
@@ -104,6 +104,11 @@ class LamConfig:
     # kernel; the logits are the 5 x 5 cross-correlation of the feature map with it (mask_decoder.py:257-271,299-307).  Adds
     # mask_decoder.prototype_tconv.{0,1}.weight.
     conv_classification: bool = False
+    # "cross_attention": the per-example embeddings are not pooled from the stream but read out of it by ``embeddings_per_example`` learned
+    # queries through two OneWayAttentionBlocks over the M hw rows of every (episode, class) pair (EmbeddingTransformer,
+    # prompt_encoder.py:280-313,719-724; parameters/validation/Pascal/mae_cross.yaml).  Adds 37 tensors under
+    # prompt_encoder.embedding_extraction.; the three merge attentions are not run.  embeddings_per_example need not be a square.
+    embedding_extraction: Optional[str] = None
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -137,6 +142,8 @@ class LamConfig:
     def pool_side(self) -> int:
         """k of the k x k adaptive average pool: floor(sqrt(embeddings_per_example)) (prompt_encoder.py:727); 1 = the plain mean."""
         e = self.embeddings_per_example
+        if self.embedding_extraction is not None:       # the learned queries replace the pooling (prompt_encoder.py:722-724)
+            return 1
         return math.isqrt(int(e)) if e and int(e) > 1 else 1
 
     @property
@@ -151,7 +158,7 @@ _OFF_PATH_DEFAULTS = dict(
     fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
     dropout=0.0, binary=False,
-    prompt_encoder=None, embedding_extraction=None,
+    prompt_encoder=None,
 )
 
 
@@ -166,6 +173,24 @@ def resolve_examples(segment_example_logits, embeddings_per_example):
     if epe and not seg:
         seg = True
     return seg, epe
+
+
+def check_extraction(embedding_extraction, embeddings_per_example, embed_dim: int = 256) -> None:
+    """The one check of ``embedding_extraction`` (config_from_kwargs and Lam), on the RESOLVED embeddings_per_example."""
+    if embedding_extraction is None:
+        return
+    if embedding_extraction != "cross_attention":
+        raise NotImplementedError(f"embedding_extraction={embedding_extraction!r} is not built: only None and 'cross_attention' "
+                                  f"(prompt_encoder.py:442-447; 'pooler' draws Gumbel noise in eval and needs the `masks` loss)")
+    if not embeddings_per_example or int(embeddings_per_example) < 1:
+        raise ValueError("embedding_extraction='cross_attention' needs embeddings_per_example >= 1 learned queries (the reference "
+                         "fails in nn.Embedding(None, D), prompt_encoder.py:286); segment_example_logits alone resolves to 1")
+    if int(embeddings_per_example) > 16:
+        raise NotImplementedError(f"embeddings_per_example={embeddings_per_example} with embedding_extraction='cross_attention': "
+                                  f"la_extract_pool takes up to 16 queries per pair")
+    if embed_dim not in (64, 128, 256):
+        raise NotImplementedError(f"embedding_extraction='cross_attention' with embed_dim={embed_dim}: la_extract_pool is built for the "
+                                  f"widths 64, 128 and 256")
 
 
 def check_levels(levels, segment_example_logits) -> None:
@@ -217,6 +242,7 @@ def config_from_kwargs(**kw) -> LamConfig:
         raise TypeError(f"unexpected LabelAnything arguments: {unknown}")
     kw["segment_example_logits"], kw["embeddings_per_example"] = resolve_examples(kw.get("segment_example_logits", False),
                                                                                   kw.get("embeddings_per_example"))
+    check_extraction(kw.get("embedding_extraction"), kw["embeddings_per_example"], kw.get("embed_dim", 256))
     check_levels(kw.get("classification_levels", 1), kw["segment_example_logits"])
     kw["conv_classification"] = bool(kw.get("conv_classification", False))
     check_classification(kw.get("classification_layer_downsample_rate", 8), kw["conv_classification"], kw["segment_example_logits"],

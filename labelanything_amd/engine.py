@@ -502,6 +502,8 @@ class LamEngine:
             if f"{pe}.{blk}.norm.weight" in w:
                 self._pack_attn(f"{pe}.{blk}.attn", "qkv")
                 self._pack_mlp(f"{pe}.{blk}.mlp")
+        if cfg.embedding_extraction == "cross_attention":
+            self._pack_extraction(pe + ".embedding_extraction")
         md = "mask_decoder"
         self._pack_two_way(md + ".transformer")
         for i in range(3):
@@ -515,6 +517,25 @@ class LamEngine:
         if cfg.spatial_convs:
             for i in range(cfg.spatial_convs):
                 p[f"{md}.sc{i}.w"] = self._hd(w[f"{md}.spatial_convs.{3 * i}.weight"].permute(0, 2, 3, 1).flatten(1))
+
+    def _pack_extraction(self, ex: str) -> None:
+        """EmbeddingTransformer (prompt_encoder.py:280-298).  The k / v projections stay fp32 matrices: la_extract_fold / la_extract_unfold
+        apply them per head to the few query rows, the stream itself is never projected.  Layer 0's input is the learned queries, the same
+        for every pair, so its folded queries are a constant of the weights: computed here, once."""
+        w, p, cfg = self.w32, self.p, self.cfg
+        d, n = cfg.embed_dim, int(cfg.embeddings_per_example)
+        for l in range(2):
+            lp = f"{ex}.layers.{l}"
+            for nm in ("q_proj", "out_proj"):
+                p[f"{lp}.cross_attn_image_to_token.{nm}.w"] = self._hd(w[f"{lp}.cross_attn_image_to_token.{nm}.weight"])
+            self._pack_mlp(lp + ".mlp")
+        ca = ex + ".layers.0.cross_attn_image_to_token"
+        emb = w[ex + ".embeddings.weight"].contiguous()
+        q0 = torch.empty(n, d // 2, device=self.dev, dtype=torch.float32)
+        L.gemm(self._hd(emb), p[ca + ".q_proj.w"], bias=w[ca + ".q_proj.bias"], out32=q0)
+        qt0 = torch.empty(L.EXTRACT_HEADS * n, d, device=self.dev, dtype=torch.float32)
+        L.extract_fold(q0, w[ca + ".k_proj.weight"], 1, n, d, qt0)
+        p[ex + ".qt0"] = qt0
 
     def repack_encoder(self, weights: Dict[str, Tensor]) -> None:
         """Refresh the packed image-encoder weights from ``weights`` (live parameters after an optimizer step); the arena, the cached
@@ -1294,6 +1315,12 @@ class LamEngine:
         self.two_way(pe_ + ".transformer", sp, pcount, ns, src32, src16, srcpe16, hw, pe32, "pe.tw", want_tokens=False)
         k = cfg.pool_side
         fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
+        if cfg.embedding_extraction == "cross_attention":
+            emb = self.extract_embeddings(src32, b, m, c, hw)
+            n = emb.shape[1]
+            # prompt_encoder.py:299-300: a query of class c is valid when any support of the episode shows the class
+            flags = (fe != 0).any(dim=1, keepdim=True).to(torch.uint8).expand(b, n, c).contiguous()
+            return {"flag_examples": flags, "class_examples_embeddings": emb, "class_examples_src": src32.view(pcount, hw, d)}
         if k > 1:
             # embeddings_per_example > 1 (prompt_encoder.py:726-731): k x k region means per (support, class) instead of the slab mean; every
             # bin is an example of its own from here on - M k k of them, flagged like the support they come from
@@ -1317,6 +1344,48 @@ class LamEngine:
         L.class_mean(emb, fe, b, m, c, d, cls)
         return {"flag_examples": flag_examples, "class_embeddings": cls,
                 "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(pcount, hw, d)}
+
+    def extract_embeddings(self, src32: Tensor, b: int, m: int, c: int, hw: int) -> Tensor:
+        """embedding_extraction = "cross_attention" (EmbeddingTransformer.forward, prompt_encoder.py:289-313): n learned queries per (b, c)
+        pair through two OneWayAttentionBlocks (transformer.py:140-154) over the M hw stream rows of the pair -> (B, n, C, D).  query_pe is
+        zero, the activation is ReLU, norm3 is never applied, and NO key is masked: the key mask the reference builds from flag_examples
+        leaves the scores untouched (common.py:120-124), so padded supports take part in the softmax exactly as there."""
+        cfg, w, p = self.cfg, self.w32, self.p
+        ex = "prompt_encoder.embedding_extraction"
+        d, n = cfg.embed_dim, int(cfg.embeddings_per_example)
+        di, bc, r = d // 2, b * c, L.EXTRACT_HEADS * n
+        rows = bc * n
+        t32 = self.f32("pe.xa.t32", (rows, d))
+        t16 = self.dbuf("pe.xa.t16", (rows, d))
+        tnew = self.f32("pe.xa.tnew", (rows, d))
+        t32.view(bc, n, d).copy_(w[ex + ".embeddings.weight"])             # "n d -> (b c) n d"
+        scratch = self.f32("pe.xa.part", (bc * L.extract_pool_plan(m, hw, d, r)[2],))
+        pooled = self.f32("pe.xa.pooled", (bc, r, d))
+        o = self.f32("pe.xa.o", (rows, di))
+        for l in range(2):
+            lp = f"{ex}.layers.{l}"
+            ca = lp + ".cross_attn_image_to_token"
+            if l == 0:
+                qt = p[ex + ".qt0"]
+            else:
+                q = self.f32("pe.xa.q", (rows, di))
+                L.gemm(t16, p[ca + ".q_proj.w"], bias=w[ca + ".q_proj.bias"], out32=q)
+                qt = self.f32("pe.xa.qt", (bc, r, d))
+                L.extract_fold(q, w[ca + ".k_proj.weight"], bc, n, d, qt)
+            L.extract_pool(src32, qt, b, m, c, hw, d, n, scratch, pooled)
+            L.extract_unfold(pooled, w[ca + ".v_proj.weight"], w[ca + ".v_proj.bias"], bc, n, d, o)
+            o16 = o
+            if self.ddt != torch.float32:
+                o16 = self.dbuf("pe.xa.o16", (rows, di))
+                L.add_cast(o, out16=o16, dt=self.ddti)
+            L.gemm(o16, p[ca + ".out_proj.w"], bias=w[ca + ".out_proj.bias"], res=t32, out32=tnew)
+            self.dln(tnew, lp + ".norm1", 1e-5, out32=t32, out16=t16)
+            hbuf = self.dbuf("pe.xa.mlp", (rows, cfg.dec_mlp))
+            L.gemm(t16, p[lp + ".mlp.lin1.w"], bias=w[lp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_RELU)
+            L.gemm(hbuf, p[lp + ".mlp.lin2.w"], bias=w[lp + ".mlp.lin2.bias"], res=t32, out32=tnew)
+            self.dln(tnew, lp + ".norm2", 1e-5, out32=t32, out16=t16)
+        # "(b c) n d -> b n c d"; always a copy: the arena buffer is overwritten by the next forward (with n = 1 the permutation is a view)
+        return t32.view(b, c, n, d).permute(0, 2, 1, 3).clone(memory_format=torch.contiguous_format)
 
     # ------------------------------------------------------------------------------------------------
     # mask decoder (mask_decoder.py:316-363)

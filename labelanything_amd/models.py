@@ -21,7 +21,7 @@ from typing import Any, Dict, Optional
 import torch
 from torch import nn
 
-from .config import LamConfig, ENCODER_SPECS, check_classification, check_levels, config_from_kwargs, resolve_examples
+from .config import LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_levels, config_from_kwargs, resolve_examples
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
 from . import _lib as L
@@ -84,12 +84,15 @@ class Lam(nn.Module):
                  decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT,
                  segment_example_logits: Optional[bool] = None, embeddings_per_example: Optional[int] = None,
                  classification_levels: Optional[int] = None, classification_layer_downsample_rate: Optional[int] = None,
-                 conv_classification: Optional[bool] = None):
+                 conv_classification: Optional[bool] = None, embedding_extraction: Optional[str] = None):
         """segment_example_logits / embeddings_per_example: the per-example family on top of ``cfg`` (resolved as build_lam.py:145-148
         does); classification_levels: 2 adds the two-level head (mask_decoder.py:204,345-362); classification_layer_downsample_rate /
-        conv_classification: the decoder's channel widths and the 5 x 5 prototype kernels (mask_decoder.py:198-271,299-307).  Left at None
-        they keep what ``cfg`` says."""
+        conv_classification: the decoder's channel widths and the 5 x 5 prototype kernels (mask_decoder.py:198-271,299-307);
+        embedding_extraction: "cross_attention" reads the per-example embeddings out of the stream with learned queries
+        (prompt_encoder.py:280-313).  Left at None they keep what ``cfg`` says."""
         super().__init__()
+        if embedding_extraction is not None:
+            cfg = dataclasses.replace(cfg, embedding_extraction=embedding_extraction)
         if classification_layer_downsample_rate is not None:
             cfg = dataclasses.replace(cfg, classification_layer_downsample_rate=classification_layer_downsample_rate)
         if conv_classification is not None:
@@ -102,6 +105,10 @@ class Lam(nn.Module):
             cfg = dataclasses.replace(cfg, segment_example_logits=seg, embeddings_per_example=epe)
         if cfg.pool_side > cfg.grid:
             raise ValueError(f"embeddings_per_example={cfg.embeddings_per_example} pools more bins than the {cfg.grid} x {cfg.grid} grid has")
+        if cfg.embedding_extraction is not None and not cfg.segment_example_logits:     # (a cfg built by hand: resolve as the builder does)
+            seg, epe = resolve_examples(True, cfg.embeddings_per_example)
+            cfg = dataclasses.replace(cfg, segment_example_logits=seg, embeddings_per_example=epe)
+        check_extraction(cfg.embedding_extraction, cfg.embeddings_per_example, cfg.embed_dim)
         check_levels(cfg.classification_levels, cfg.segment_example_logits)
         check_classification(cfg.classification_layer_downsample_rate, cfg.conv_classification, cfg.segment_example_logits,
                              cfg.classification_levels)
@@ -321,9 +328,10 @@ class Lam(nn.Module):
         support = ev[:, 1:].contiguous().view(b * (n - 1) * hw, d)
         points, boxes, masks = self._prompts_of(inp)
         pe_result = eng.prompt_encoder(support, b, n - 1, g, points, boxes, masks, inp["flag_examples"], inp.get("selected_rows"))
-        seg = eng.mask_decoder(query, b, g, pe_result["class_embeddings"], pe_result["class_examples_embeddings"], pe_result["flag_examples"])
-        out = {"low_res_logits": seg, "class_embeddings": pe_result["class_embeddings"],
-               "class_examples_embeddings": pe_result["class_examples_embeddings"]}
+        seg = eng.mask_decoder(query, b, g, pe_result.get("class_embeddings"), pe_result["class_examples_embeddings"], pe_result["flag_examples"])
+        out = {"low_res_logits": seg, "class_examples_embeddings": pe_result["class_examples_embeddings"]}
+        if "class_embeddings" in pe_result:      # (embedding_extraction has no class mean: prompt_encoder.py:310-313)
+            out["class_embeddings"] = pe_result["class_embeddings"]
         if self.cfg.segment_example_logits:      # the flags that go with the (B, M k k, C, D) example embeddings, as the reference's pe_result
             out["flag_examples"] = pe_result["flag_examples"]
         if want_post:
@@ -413,7 +421,7 @@ class Lam(nn.Module):
         query = e32.view(b, n, g * g, d)[:, 0].contiguous().view(b * g * g, d)
         if self.cfg.segment_example_logits:
             # the per-example family serves from the cached per-example embeddings and their flags (mask_decoder.py:279-287)
-            seg = eng.mask_decoder(query, b, g, class_embeddings["class_embeddings"], class_embeddings["class_examples_embeddings"],
+            seg = eng.mask_decoder(query, b, g, class_embeddings.get("class_embeddings"), class_embeddings["class_examples_embeddings"],
                                    class_embeddings["flag_examples"])
             return eng.postprocess(seg, batched_input["dims"].unsqueeze(1), eng.example_valid(class_embeddings["flag_examples"]))
         seg = eng.mask_decoder(query, b, g, class_embeddings["class_embeddings"])
@@ -731,9 +739,11 @@ class LabelAnything(nn.Module, PyTorchModelHubMixin):
                  fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
                  transformer_keys_are_images=True, transformer_feature_size=None, class_encoder=None,
                  segment_example_logits=False, dropout: float = 0.0, binary=False, custom_preprocess=True,
-                 classification_levels: int = 1, conv_classification: bool = False):
-        """classification_levels and conv_classification are not arguments of the reference's class (its builders take them,
-        build_lam.py:118,251): they are accepted here so that a mae_levels / mae_nodown model round-trips through config.json."""
+                 classification_levels: int = 1, conv_classification: bool = False, embedding_extraction: Optional[str] = None):
+        """classification_levels, conv_classification and embedding_extraction are not arguments of the reference's class (its builders
+        take them, build_lam.py:118-127,251): they are accepted here so that such a model round-trips through config.json.  Like the
+        reference's class this one takes segment_example_logits only, so embedding_extraction comes with one learned query here; the
+        build_lam functions and Lam take embeddings_per_example."""
         super().__init__()
         cfg = dict(self.config)
         enc = cfg.pop("encoder")

@@ -398,6 +398,11 @@ class LamTrainer:
             # build_lam.py:128); the training graph here has no dropout node, so training such a model would silently be a different model
             raise NotImplementedError(f"dropout={lam.cfg.dropout} is not built into the training graph (every canonical parameters/*.yaml "
                                       f"leaves it at 0); build the model with dropout=0.0 to train it here")
+        if lam.cfg.embedding_extraction is not None:
+            # no reference recipe trains it here, in train mode the reference drops learned queries with host-side random draws
+            # (prompt_encoder.py:301-307), and la_extract_pool has no backward
+            raise NotImplementedError(f"embedding_extraction={lam.cfg.embedding_extraction!r} is an inference configuration here: its "
+                                      f"training graph (the backward of la_extract_pool, the reference's embedding dropout) is not built")
         if lam.cfg.pool_side > 1 and isinstance(loss, LabelAnythingLoss) and len(loss.prompt_components):
             # the contrastive term pairs the examples of a class across supports; with k x k region embeddings per support the reference's
             # pairing treats the bins of ONE support as independent positives, which nobody has checked here

@@ -176,6 +176,20 @@ def decoder_shapes(cfg: LamConfig) -> Shapes:
         # LAST as well (never together with the level reducer): ConvTranspose2d(cf, cf, 3, bias=False) weights, (in, out, ky, kx)
         s[md + ".prototype_tconv.0.weight"] = (cf, cf, 3, 3)
         s[md + ".prototype_tconv.1.weight"] = (cf, cf, 3, 3)
+    if cfg.embedding_extraction == "cross_attention":
+        # LAST as well: EmbeddingTransformer (prompt_encoder.py:280-287) = 2 x OneWayAttentionBlock (transformer.py:129-138) + the learned
+        # queries, 37 tensors.  norm3 is a parameter of the block that its forward never applies: held and saved, never read.
+        ex = pe + ".embedding_extraction"
+        for l in range(2):
+            lp = f"{ex}.layers.{l}"
+            _attn_shapes(s, lp + ".cross_attn_image_to_token", d, d // 2)
+            for n in ("norm1", "norm2", "norm3"):
+                _ln_shapes(s, f"{lp}.{n}", d)
+            s[lp + ".mlp.lin1.weight"] = (mlp, d)
+            s[lp + ".mlp.lin1.bias"] = (mlp,)
+            s[lp + ".mlp.lin2.weight"] = (d, mlp)
+            s[lp + ".mlp.lin2.bias"] = (d,)
+        s[ex + ".embeddings.weight"] = (int(cfg.embeddings_per_example), d)
     return s
 
 
@@ -223,8 +237,8 @@ def init_state_dict(cfg: LamConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
         elif name.endswith("pos_embed") or "position_embeddings" in name or "cls_token" in name \
                 or "pos_embedding" in name:
             t = 0.02 * torch.randn(shape, generator=gen)
-        elif len(shape) == 2 and shape[0] == 1:      # nn.Embedding(1, D) rows
-            t = torch.randn(shape, generator=gen)
+        elif (len(shape) == 2 and shape[0] == 1) or name.endswith("embedding_extraction.embeddings.weight"):
+            t = torch.randn(shape, generator=gen)    # nn.Embedding rows: N(0, 1) per entry
         else:
             if "output_upscaling" in name and len(shape) == 4:
                 fan_in = shape[0]                    # ConvTranspose2d (Cin, Cout, k, k), stride == k: one tap per output
