@@ -139,6 +139,25 @@ int la_gemm_fused_act_ok(int M, int N, int K);
 int la_gemm(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
             const LaGemmEpilogue* epi, int dt, void* stream);
 
+/* What la_gemm would launch for a call: one kernel template (`kernel`) and the launch parameters that pick its instantiation and grid.
+ *  epi      compile-time epilogue of the 256 x 256 kernels (0 run-time generic, 1 bias -> 16 bit, 2 bias -> GELU -> 16 bit, 3 fp32 (+ 16 bit)
+ *           with residual, 4 split-K atomics, 5 - 12 the fused forms of LaGemmEpilogue.aux16 / nstat_*); LA_GEMM_F32_N*: 1 = vectorised epilogue
+ *  planes   weight planes walked against one A k-tile (2: a_kmod = K / 2 on the 256 x 256 kernels)
+ *  direct / ragged   LA_GEMM_T256W: the kernel's own epilogue on unmapped tiles / its form with a partial last row tile (M % 256 != 0)
+ *  gm       row panels per tile group (bits 0-7; a -DLA_DEBUG library carries la_gemm_variant's ablation bits above them)
+ *  ksplit, kchunk    K chunks that run as independent tiles and their depth (1, K unless LaGemmEpilogue.ksplit)
+ *  grid, block, lds_bytes   workgroups, threads per workgroup, dynamic LDS of the launch */
+enum { LA_GEMM_NT = 0, LA_GEMM_DMA128, LA_GEMM_DMA256x128, LA_GEMM_T256, LA_GEMM_T256P, LA_GEMM_T256Q, LA_GEMM_T256W,
+       LA_GEMM_F32_N32, LA_GEMM_F32_N128, LA_GEMM_F32_SMALL, LA_GEMM_SKINNY };
+typedef struct LaGemmPlan {
+  int kernel, epi, planes, direct, ragged, gm, ksplit, kchunk, grid, block, lds_bytes;
+} LaGemmPlan;
+
+/* la_gemm's decision without the launch: same arguments (A and W are only tested for NULL and alignment, never read - any address
+ * will do), same checks and error texts; ncu <= 0 = the CU count of the current device.  Fills *out, launches nothing. */
+int la_gemm_plan(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                 const LaGemmEpilogue* epi, int dt, int ncu, LaGemmPlan* out);
+
 /* 3x3 / pad 1 convolution as an IMPLICIT GEMM on the exact-fp32 MFMA (no im2col buffer): in fp32 NHWC [B,H,W,Cin]
  * (Cin % 32 == 0), wt fp32 [Cout, (ky,kx,cin)], bias fp32 [Cout] or NULL -> out32 fp32 NHWC [B*H*W, Cout]
  * (spatial convs of the mask decoder, mask_decoder.py:236-255). */

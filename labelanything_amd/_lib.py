@@ -62,7 +62,7 @@ EXPORTS = [
     "la_dense_pe", "la_point_embed", "la_mask_embed", "la_attn_small", "la_colmean", "la_class_mean",
     "la_classify", "la_add_cast", "la_conv3x3_f32", "la_nchw_to_nhwc", "la_nhwc_to_nchw", "la_bilinear", "la_post_final",
     "la_confmat_update", "la_resample_u8", "la_u8_to_chw_norm", "la_prompt_masks", "la_focal_loss", "la_adamw_step",
-    "la_gemm_tn", "la_gemm_tn16", "la_gemm_fused_act_ok", "la_colsum_acc", "la_layernorm_bwd", "la_layernorm_bwd_res", "la_transpose_many", "la_act_fwd", "la_act_bwd", "la_attn_small_lse", "la_attn_small_bwd", "la_bilinear_bwd", "la_bilinear_bwd_set", "la_bilinear_bwd_set_ok", "la_bilinear_rows", "la_bilinear_rows_bwd_set",
+    "la_gemm_tn", "la_gemm_tn16", "la_gemm_fused_act_ok", "la_gemm_plan", "la_colsum_acc", "la_layernorm_bwd", "la_layernorm_bwd_res", "la_transpose_many", "la_act_fwd", "la_act_bwd", "la_attn_small_lse", "la_attn_small_bwd", "la_bilinear_bwd", "la_bilinear_bwd_set", "la_bilinear_bwd_set_ok", "la_bilinear_rows", "la_bilinear_rows_bwd_set",
     "la_classify_bwd", "la_row_broadcast", "la_twoway_t2i", "la_twoway_i2t", "la_gemm_variant", "la_attn_fwd_lse", "la_head_transpose", "la_attn_bwd", "la_cast", "la_gelu_bwd16", "la_axpy", "la_transpose16", "la_qk_fp8", "la_attn_fwd_fp8", "la_colmean16", "la_layernorm_g", "la_add_rowvec", "la_add_rowvec_split", "la_attn_fwd_cs", "la_attn_fwd_rows", "la_colsum_fold", "la_gelu_fwd16", "la_gemm_tn_db",
     "la_attn_fwd_relpos_lse", "la_attn_bwd_relpos", "la_relpos_bwd", "la_twoway_pe_layout",
     "la_norm_finalize", "la_norm_stats", "la_conv3x3_split", "la_conv3x3_split_ok",
@@ -77,8 +77,10 @@ EXPORTS = [
 
 
 def gemm_variant(v: int = -1) -> int:
-    """la_gemm_variant: select the main loop of the large encoder GEMMs - 2 (default): four waves x 512 registers (gemm_w4.hip),
-    1: eight waves in quadrant phases, 0: the BK 32 kernel.  All are bit-identical.  Returns the previous value."""
+    """la_gemm_variant: the persistent kernel of the single-plane shapes with K % 64 == 0, K >= 128 (``gemm_plan`` says which calls those
+    are) - 2 (default): gemm_t256w, four waves x 512 registers (gemm_w4.hip); 1: gemm_t256q, eight waves in quadrant phases; 0:
+    gemm_t256p, the BK 32 kernel, which two-plane shapes take at every value.  The LaGemmEpilogue.aux16 / nstat_* forms exist at 2 only.
+    All are bit-identical; v < 0 only queries.  Returns the previous value."""
     return int(lib().la_gemm_variant(int(v)))
 
 
@@ -111,55 +113,81 @@ def _dev(t: torch.Tensor) -> None:
 
 
 # ----------------------------------------------------------------------------------------------
-def gemm(a: torch.Tensor, w: torch.Tensor, *, bias=None, res=None, res_mod=0, out32=None, out16=None,
-         act=ACT_NONE, map=MAP_NONE, p=(0, 0, 0, 0, 0), vt=None, vt_col0=0, vt_T=0, vt_Tpad=0, vt_hd=64,
-         vt_heads=0, vt_ws=0, M=None, lda=None, amap=MAP_NONE, a_kmod=0, ksplit=0, aux16=None, nstat_out=None, rvec=None, rvec_rpg=0,
-         nstat_in=None, ncol=None) -> None:
-    """C = epilogue(a @ w.T).  a: [M,K] 16-bit (row stride lda), w: [N,K] 16-bit.  a_kmod > 0: w is [N, j*a_kmod] (split-precision
-    planes [W_hi | W_lo]) and the columns of a repeat with period a_kmod.  aux16 (training, shapes with ``gemm_fused_act_ok``): with
-    ACT_GELU the pre-activation is written there beside out16 = GELU; with ACT_GELU_BWD out16 = (a @ w.T) * gelu'(aux16).
-    nstat_out / rvec / nstat_in / ncol: the producer and consumer sides of a LayerNorm folded into its neighbour GEMMs (see
-    LaGemmEpilogue in include/la_hip.h; ``norm_finalize`` turns the producer's partial sums into the consumer's (mean, rstd) rows)."""
-    _dev(a)
-    m = a.shape[0] if M is None else M
-    k = w.shape[1]
-    n = w.shape[0]
+class LaGemmPlan(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("kernel", "epi", "planes", "direct", "ragged", "gm", "ksplit", "kchunk", "grid", "block", "lds_bytes")]
+
+
+GEMM_KERNELS = ("NT", "DMA128", "DMA256x128", "T256", "T256P", "T256Q", "T256W", "F32_N32", "F32_N128", "F32_SMALL", "SKINNY")   # LaGemmPlan.kernel
+
+
+def _addr(x) -> Optional[int]:
+    """Device address of a tensor; None and plain integers (a planned call needs no memory) pass through."""
+    return x.data_ptr() if isinstance(x, torch.Tensor) else x
+
+
+def _gemm_epilogue(m: int, n: int, *, bias=None, res=None, res_mod=0, out32=None, out16=None, act=ACT_NONE, map=MAP_NONE, p=(0, 0, 0, 0, 0), vt=None,
+                   vt_col0=0, vt_T=0, vt_Tpad=0, vt_hd=64, vt_heads=0, vt_ws=0, amap=MAP_NONE, a_kmod=0, ksplit=0, aux16=None, nstat_out=None, rvec=None,
+                   rvec_rpg=0, nstat_in=None, ncol=None, ldr=None, ld32=None, ld16=None, ldaux=None) -> LaGemmEpilogue:
+    """The LaGemmEpilogue of a ``gemm`` / ``gemm_plan`` call.  Buffers are tensors or plain addresses; the leading dimension of a tensor
+    is its row stride, of an address the ld* argument (default: n)."""
+    def ld(x, given):
+        if x is None:
+            return 0
+        if given is not None:
+            return given
+        return n if not isinstance(x, torch.Tensor) else (x.stride(-2) if x.dim() >= 2 else 0)
+
     e = LaGemmEpilogue()
-    e.bias = bias.data_ptr() if bias is not None else None
-    e.res = res.data_ptr() if res is not None else None
-    e.ldr = res.stride(-2) if res is not None and res.dim() >= 2 else 0
+    e.bias, e.res, e.out32, e.out16, e.vt, e.aux16 = _addr(bias), _addr(res), _addr(out32), _addr(out16), _addr(vt), _addr(aux16)
+    e.ldr, e.ld32, e.ld16, e.ldaux = ld(res, ldr), ld(out32, ld32), ld(out16, ld16), ld(aux16, ldaux)
     e.res_mod = res_mod
-    e.out32 = out32.data_ptr() if out32 is not None else None
-    e.ld32 = out32.stride(-2) if out32 is not None else 0
-    e.out16 = out16.data_ptr() if out16 is not None else None
-    e.ld16 = out16.stride(-2) if out16 is not None else 0
     e.act, e.map = act, map
     e.p0, e.p1, e.p2, e.p3, e.p4 = p
-    e.vt = vt.data_ptr() if vt is not None else None
     e.vt_col0, e.vt_T, e.vt_Tpad, e.vt_hd, e.vt_heads = vt_col0, vt_T, vt_Tpad, vt_hd, vt_heads
     e.vt_ws = vt_ws
     e.amap = amap
     e.a_kmod = a_kmod
     e.ksplit = ksplit
-    e.aux16 = aux16.data_ptr() if aux16 is not None else None
-    e.ldaux = aux16.stride(-2) if aux16 is not None else 0
-    if nstat_out is not None or nstat_in is not None or rvec is not None:
-        mpad = -(-m // 256) * 256
-        if nstat_out is not None and (nstat_out.dtype != torch.float32 or nstat_out.numel() < m * (n // 64) * 2):
-            raise RuntimeError(f"gemm: nstat_out must be fp32 with at least M * (N / 64) * 2 = {m * (n // 64) * 2} entries")
-        if nstat_in is not None and (nstat_in.dtype != torch.float32 or nstat_in.numel() < mpad * 2 or ncol is None
-                                     or ncol.dtype != torch.float32 or ncol.numel() < n):
-            raise RuntimeError(f"gemm: nstat_in must be fp32 [ceil(M / 256) * 256, 2] (>= {mpad * 2} entries) and needs ncol fp32 [N]")
-        if rvec is not None and (rvec.dtype != torch.float32 or rvec_rpg <= 0 or rvec.numel() < -(-m // rvec_rpg) * n):
-            raise RuntimeError("gemm: rvec must be fp32 [ceil(M / rvec_rpg), N] with rvec_rpg > 0")
-    e.nstat_out = nstat_out.data_ptr() if nstat_out is not None else None
-    e.rvec = rvec.data_ptr() if rvec is not None else None
+    mpad = -(-m // 256) * 256
+    if isinstance(nstat_out, torch.Tensor) and (nstat_out.dtype != torch.float32 or nstat_out.numel() < m * (n // 64) * 2):
+        raise RuntimeError(f"gemm: nstat_out must be fp32 with at least M * (N / 64) * 2 = {m * (n // 64) * 2} entries")
+    if isinstance(nstat_in, torch.Tensor) and (nstat_in.dtype != torch.float32 or nstat_in.numel() < mpad * 2 or ncol is None
+                                               or ncol.dtype != torch.float32 or ncol.numel() < n):
+        raise RuntimeError(f"gemm: nstat_in must be fp32 [ceil(M / 256) * 256, 2] (>= {mpad * 2} entries) and needs ncol fp32 [N]")
+    if isinstance(rvec, torch.Tensor) and (rvec.dtype != torch.float32 or rvec_rpg <= 0 or rvec.numel() < -(-m // rvec_rpg) * n):
+        raise RuntimeError("gemm: rvec must be fp32 [ceil(M / rvec_rpg), N] with rvec_rpg > 0")
+    e.nstat_out, e.rvec, e.nstat_in, e.ncol = _addr(nstat_out), _addr(rvec), _addr(nstat_in), _addr(ncol)
     e.rvec_rpg = rvec_rpg
-    e.nstat_in = nstat_in.data_ptr() if nstat_in is not None else None
-    e.ncol = ncol.data_ptr() if ncol is not None else None
+    return e
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, *, M=None, lda=None, **epilogue) -> None:
+    """C = epilogue(a @ w.T).  a: [M,K] 16-bit (row stride lda), w: [N,K] 16-bit.  a_kmod > 0: w is [N, j*a_kmod] (split-precision
+    planes [W_hi | W_lo]) and the columns of a repeat with period a_kmod.  aux16 (training, shapes with ``gemm_fused_act_ok``): with
+    ACT_GELU the pre-activation is written there beside out16 = GELU; with ACT_GELU_BWD out16 = (a @ w.T) * gelu'(aux16).
+    nstat_out / rvec / nstat_in / ncol: the producer and consumer sides of a LayerNorm folded into its neighbour GEMMs (see
+    LaGemmEpilogue in include/la_hip.h; ``norm_finalize`` turns the producer's partial sums into the consumer's (mean, rstd) rows).
+    The epilogue keywords are those of ``_gemm_epilogue``."""
+    _dev(a)
+    m = a.shape[0] if M is None else M
+    k = w.shape[1]
+    n = w.shape[0]
+    e = _gemm_epilogue(m, n, **epilogue)
     rc = lib().la_gemm(_ptr(a), C.c_int(a.stride(0) if lda is None else lda), _ptr(w), C.c_int(w.stride(0)),
                        C.c_int(m), C.c_int(n), C.c_int(k), C.byref(e), C.c_int(dt_of(a)), _stream())
     _check(rc, "la_gemm")
+
+
+def gemm_plan(a, lda: int, w, ldw: int, m: int, n: int, k: int, dt: int, ncu: int = 0, **epilogue) -> LaGemmPlan:
+    """la_gemm_plan: what ``gemm`` would launch for these arguments (kernel family - GEMM_KERNELS[plan.kernel] -, epilogue, grid), with
+    la_gemm's argument errors and no launch.  a, w and the epilogue buffers are tensors or plain integer addresses (they are only tested
+    for None and alignment), so this runs without a GPU when ncu is given; ncu <= 0 takes the CU count of the current device."""
+    plan = LaGemmPlan()
+    e = _gemm_epilogue(m, n, **epilogue)
+    rc = lib().la_gemm_plan(C.c_void_p(_addr(a)), C.c_int(lda), C.c_void_p(_addr(w)), C.c_int(ldw), C.c_int(m), C.c_int(n), C.c_int(k), C.byref(e),
+                            C.c_int(dt), C.c_int(ncu), C.byref(plan))
+    _check(rc, "la_gemm_plan")
+    return plan
 
 
 def norm_finalize(part: Optional[torch.Tensor], m: int, e: int, eps: float, mr: torch.Tensor, x16: Optional[torch.Tensor] = None, rpg: int = 0,

@@ -7,10 +7,12 @@
 // written to the other LDS stage after them.  Tiles are handed to XCDs in contiguous chunks (xcd_remap) so
 // the workgroups sharing an A row-panel / the whole W hit the same L2.
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include "la_common.h"
 #include "../../include/la_hip.h"
 #include "gemm_shared.h"
+#include "gemm_plan.h"
 
 namespace la {
 
@@ -334,19 +336,6 @@ __device__ __forceinline__ void epilogue_lds(float* epi, const f32x16 (&acc)[TI]
   }
 }
 
-static bool epi_vec_ok(int N, const LaGemmEpilogue& e, int elt_bytes) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if ((N % 8) != 0) return false;
-  if (e.bias && !al16(e.bias)) return false;
-  if (e.res && (!al16(e.res) || (e.ldr % 4) != 0)) return false;
-  if (e.out32 && (!al16(e.out32) || (e.ld32 % 4) != 0)) return false;
-  if (e.out16 && (!al16(e.out16) || (e.ld16 % (16 / elt_bytes)) != 0)) return false;
-  if (e.map == LA_MAP_CONVT2X2 && (e.p2 % 8) != 0) return false;
-  if (e.vt && ((e.vt_col0 % BN) != 0 || (e.vt_Tpad % 4) != 0 || !al16(e.vt))) return false;
-  return true;
-}
-
-
 // One 64-deep K tile for a 64 x 64 wave tile: 4 MFMA k-steps, fragments of step ks+1 are fetched from LDS before the
 // MFMAs of step ks are issued (two register sets), so the ds_read latency hides behind matrix work.
 template <typename T>
@@ -381,14 +370,6 @@ __device__ __forceinline__ void mma_ktile(const char* sa, const char* sw, int ar
 // handles 8 consecutive output columns (16-byte stores, float4 residual / bias loads).  Tile BM x BN with one
 // 64 x 64 sub-tile per wave: 128x128 (4 waves, 2 blocks/CU).
 // =================================================================================================================
-constexpr int EPI_LD = BN + 4;                      // fp32 row stride of the staged output tile
-constexpr int EPI_BYTES = 128 * EPI_LD * 4;         // one 128-row chunk
-
-template <int BM_>
-constexpr int fast_lds_bytes() {
-  return (2 * (BM_ + BN) * BK * 2) > EPI_BYTES ? (2 * (BM_ + BN) * BK * 2) : EPI_BYTES;
-}
-
 template <typename T, int BM_>
 __global__ __launch_bounds__(BM_ * 2, 2) void gemm_dma_kernel(const T* __restrict__ A, int lda, const T* __restrict__ Wt, int ldw,
                                                                int M, int N, int K, LaGemmEpilogue e, int gm) {
@@ -543,34 +524,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma4_kernel(const T* __restrict__
   epilogue_lds<T, 4, 2, BN, NT>(reinterpret_cast<float*>(smem), acc, 2, wm, 0, wn * 64, m0, n0, M, N, e, tid);
 }
 
-// row-panels per tile group (tile_coords); measured flat within +-2 % for 1..16 on the 256 x 128 / 128 x 128 kernels (default 8)
-// and ~2 % better at 1..4 for the 256 x 256 kernel (dflt = 2 there) - except with >= 10 column tiles (lin1: N = 3072), where 8 row
-// panels per group fetch 25 % less through the L2 (1.77 -> 1.33 M KiB of FETCH_SIZE per launch, tools/gemm_group_m.sh: with 2 row panels
-// per group an XCD streams the whole 4.7 MB weight for every pair of panels) and run 1.3 % faster; lin2 / proj (3 column tiles) fetch
-// and run worse beyond 2.  LA_GEMM_GROUP_M overrides both
-static int tile_group_m(int dflt = 8) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char* v = la_dbg_env("LA_GEMM_GROUP_M");
-    forced = v ? atoi(v) : -1;
-  }
-  return forced >= 0 ? forced : dflt;
-}
-
-template <typename T>
-static void launch_fast4(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  constexpr int LDS = 3 * (256 + BN) * 32 * 2;     // 72 KiB >= 67.5 KiB epilogue chunk
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_dma4_kernel<T>), LDS, attr_mask);
-  const int ntm = (M + 255) / 256, ntn = (N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_dma4_kernel<T>), dim3(ntm * ntn), dim3(256), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m());
-}
-
-
-constexpr int PP_BM = 256, PP_BN = 256;
-constexpr int PP_STAGE = (PP_BM + PP_BN) * BK * 2;     // 64 KiB
-constexpr int PP_HALF = 128 * BK * 2;                   // 16 KiB half-tile
+constexpr int PP_BN = 256;                             // tile width of the 256 x 256 kernels
 
 // Epilogue of the 256 x 256 tile kernels (8 waves, wave (grp, wi) holds rows [128 grp, +128) x columns [64 wi, +64) as
 // acc[4][2]): four 64-row chunks staged through LDS (each wave's 128 rows span two chunks).
@@ -676,176 +630,6 @@ __device__ __forceinline__ void epilogue_256(char* smem, const f32x16 (&acc)[4][
     }
   }}
 
-// =================================================================================================================
-// v6 "ping-pong": 256 x 256 x 64 tile, 8 waves = 2 groups of 4; group g owns rows [128 g, +128), wave i of a group the
-// columns [64 i, +64) -> 128 x 64 per wave (4 x 2 MFMA 32x32 accumulators).  Every SIMD hosts one wave of each group.
-// A k-step (64) is walked QUADRANT-major: the wave's tile is 2 x 2 quadrants of 64 x 32 and one burst = one quadrant
-// over the whole k-step (2 row tiles x 4 k-slices = 8 MFMAs = 256 matrix-pipe cycles); quadrant order (0,0) (0,1)
-// (1,1) (1,0) so that each burst loads only one new operand half.  The two groups run ONE BARRIER OUT OF PHASE: while
-// group 0 issues a burst, group 1 fetches fragments from LDS and issues its share of the LDS-DMA, then they swap.
-//
-//   interval      8t     8t+1    8t+2    8t+3    8t+4    8t+5    8t+6    8t+7        (one s_barrier between intervals)
-//   group 0       L1      M1      L2      M2      L3      M3      L4      M4
-//   group 1     M4(t-1)   L1      M1      L2      M2      L3      M3      L4
-//   L1: read A0,W0  L2: read W1  L3: read A1  L4: read W0        M1: q(0,0)  M2: q(0,1)  M3: q(1,1)  M4: q(1,0)
-//
-// LDS: 2 stages x (A 256x64 + W 256x64) x 2 B = 128 KiB, k-step t in stage t & 1; full 128-byte rows so every DMA piece
-// (8 rows) moves whole cache lines.  Rows are stored HALF-major: operand half h (the rows of quadrant index h of every
-// wave) is one contiguous 16 KiB "half-tile" = 16 DMA pieces = 2 per wave, and a half-tile is restaged as soon as its
-// last reader is done instead of waiting for the whole stage:
-//   L1 issues A1(t+1)   L2 issues W0(t+1)   L3 issues A0(t+2)   L4 issues W1(t+2)
-// Hazards (g1 runs one interval later than g0; reads are retired by the lgkmcnt(0) at the top of the following M):
-//   * WAR: each half-tile is restaged two L phases after the L phase that read it last (A0: L1 -> L3, W1: L2 -> L4,
-//     A1: L3 -> next L1, W0: L4 -> next L2), i.e. >= 1 full interval after the slower group's reads retired.
-//   * RAW: k-step t+1 is first read in interval 8t+8.  Every wave retires its own pieces of k-step t+1 with a COUNTED
-//     vmcnt before the barrier that closes interval 8t+7 (group 0 at the end of M4, group 1 in L4): only the younger
-//     A0(t+2), W1(t+2) may stay in flight -> vmcnt(4).
-// Operand traffic per MFMA: 0.75 KiB of fragment reads + 0.25 KiB of DMA (vs 1.0 + 0.5 in the 128x128 kernel) and half
-// the L2 reads per FLOP.
-// =================================================================================================================
-
-template <typename T>
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const T* __restrict__ A, int lda, const T* __restrict__ Wt, int ldw,
-                                                          int M, int N, int K, LaGemmEpilogue e, int gm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int grp = __builtin_amdgcn_readfirstlane(wave >> 2), wi = wave & 3;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int ntn = (N + PP_BN - 1) / PP_BN, ntm = (M + PP_BM - 1) / PP_BM;
-  int tm_, tn_;
-  tile_coords(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, gm, tm_, tn_);
-  const int m0 = tm_ * PP_BM, n0 = tn_ * PP_BN;
-
-  // DMA pieces of this wave: for half-tile (operand o, half h) the 8-row groups p = wave and wave + 8 of its 128 LDS rows.
-  // LDS row lr of A half h holds tile row (lr / 64) * 128 + h * 64 + lr % 64; of W half h tile column (lr / 32) * 64 +
-  // h * 32 + lr % 32.  The 16-byte chunk c of a row sits in slot c ^ ((lr >> 1) & 7) (conflict-free ds_read_b128).
-  unsigned soff[2][2][2];    // [operand][half][piece] byte offsets from A / W (launcher checks < 4 GiB)
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int lr = (wave + 8 * i) * 8 + (lane >> 3);
-      const int slot = lane & 7;
-      const int ch = (slot ^ ((lr >> 1) & 7)) << 3;
-      const int ra = (lr >> 6) * 128 + h * 64 + (lr & 63);
-      const int rw = (lr >> 5) * 64 + h * 32 + (lr & 31);
-      soff[0][h][i] = (unsigned)(((size_t)a_row(e, min(m0 + ra, M - 1)) * lda + ch) * sizeof(T));
-      soff[1][h][i] = (unsigned)(((size_t)min(n0 + rw, N - 1) * ldw + ch) * sizeof(T));
-    }
-  const unsigned lds0 = lds_addr_of(smem);
-  const int nk = K / BK;
-  // half-tile (o, h) of k-step kt: stage kt & 1, operand o at + o * 32 KiB, half h at + h * 16 KiB; this wave's pieces at
-  // + wave KiB and + (8 + wave) KiB.  Source = wave-uniform base advanced by the k-step + 32-bit lane offset.
-  auto dma_ht = [&](int kt, int o, int h) {
-    if (kt >= nk) return;
-    const unsigned base = lds0 + (kt & 1) * PP_STAGE + o * (2 * PP_HALF) + h * PP_HALF + wave * 1024;
-    const T* sb = o ? Wt + kt * BK : A + a_koff(e, kt * BK);
-    dma16s(sb, soff[o][h][0], base);
-    dma16s(sb, soff[o][h][1], base + 8 * 1024);
-  };
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  uint4 af[4][2], wf[4];                              // fragments [k-slice][row tile] / [k-slice] of the current halves
-  const int wrow = wi * 64;                           // first tile column of this wave (epilogue)
-  auto load_a = [&](int kt, int h) {
-    const char* sa = smem + (kt & 1) * PP_STAGE + h * PP_HALF;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) af[ks][i] = *reinterpret_cast<const uint4*>(sa + swz_off(grp * 64 + i * 32 + fr, ks * 2 + fh));
-  };
-  auto load_w = [&](int kt, int h) {
-    const char* sw = smem + (kt & 1) * PP_STAGE + 2 * PP_HALF + h * PP_HALF;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) wf[ks] = *reinterpret_cast<const uint4*>(sw + swz_off(wi * 32 + fr, ks * 2 + fh));
-  };
-  auto bar = [&]() {
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-#define LA_PP_BURST(HA, HB)                                                                \
-  do {                                                                                               \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                               \
-    __builtin_amdgcn_s_setprio(1);                                                                   \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                               \
-      acc[2 * HA][HB] = Half16<T>::mfma32(af[ks][0], wf[ks], acc[2 * HA][HB]);                       \
-      acc[2 * HA + 1][HB] = Half16<T>::mfma32(af[ks][1], wf[ks], acc[2 * HA + 1][HB]);               \
-    }                                                                                                \
-    __builtin_amdgcn_s_setprio(0);                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                               \
-  } while (0)
-
-  // prologue: all of k-step 0, then A0(1), W1(1) (what L3/L4 of a "k-step -1" would have issued)
-  dma_ht(0, 0, 0);
-  dma_ht(0, 1, 0);
-  dma_ht(0, 0, 1);
-  dma_ht(0, 1, 1);
-  dma_ht(1, 0, 0);
-  dma_ht(1, 1, 1);
-  if (nk > 1) dma_wait<4>();
-  else dma_wait<0>();
-  bar();                                   // k-step 0 resident
-  if (grp == 1) bar();                     // group 1 runs one interval behind
-  for (int kt = 0; kt < nk; ++kt) {
-    // ---- L1 / M1: quadrant (0,0) -------------------------------------------------------------------------------------
-    dma_ht(kt + 1, 0, 1);
-    load_w(kt, 0);
-    load_a(kt, 0);
-    bar();
-    LA_PP_BURST(0, 0);
-    bar();
-    // ---- L2 / M2: quadrant (0,1) -------------------------------------------------------------------------------------
-    dma_ht(kt + 1, 1, 0);
-    load_w(kt, 1);
-    bar();
-    LA_PP_BURST(0, 1);
-    bar();
-    // ---- L3 / M3: quadrant (1,1) -------------------------------------------------------------------------------------
-    dma_ht(kt + 2, 0, 0);
-    load_a(kt, 1);
-    bar();
-    LA_PP_BURST(1, 1);
-    bar();
-    // ---- L4 / M4: quadrant (1,0) -------------------------------------------------------------------------------------
-    dma_ht(kt + 2, 1, 1);
-    load_w(kt, 0);
-    if (grp == 1) {                        // group 1 closes interval 8 kt + 7 here: k-step kt+1 must be complete
-      if (kt + 2 < nk) dma_wait<4>();
-      else dma_wait<0>();
-    }
-    bar();
-    LA_PP_BURST(1, 0);
-    if (grp == 0) {
-      if (kt + 2 < nk) dma_wait<4>();
-      else dma_wait<0>();
-    }
-    bar();
-  }
-#undef LA_PP_BURST
-  if (grp == 0) bar();                     // re-align the two groups
-  __syncthreads();
-
-  epilogue_256<T>(smem, acc, grp, wrow, m0, n0, M, N, e, tid);
-}
-
-template <typename T>
-static void launch_pp(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  constexpr int LDS = 2 * PP_STAGE;      // 128 KiB (epilogue chunk 64 x 260 x 4 = 65 KiB, transposed 256 x 68 x 4 = 68 KiB)
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_pp_kernel<T>), LDS, attr_mask);
-  const int ntm = (M + PP_BM - 1) / PP_BM, ntn = (N + PP_BN - 1) / PP_BN;
-  hipLaunchKernelGGL((gemm_pp_kernel<T>), dim3(ntm * ntn), dim3(512), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m(2));
-}
-
 // Epilogue of gemm_t256_kernel: the tile leaves in four 64-row chunks (wave group g holds rows [128 g, +128) = chunks 2g, 2g+1)
 // through TWO staging buffers, in the order g0/h0, g1/h0, g0/h1, g1/h1: while every thread turns chunk p into 16-byte global
 // stores, the owning group already writes chunk p+1 into the other buffer - one barrier per chunk, and the residual rows of
@@ -857,10 +641,6 @@ static void launch_pp(const void* A, int lda, const void* W, int ldw, int M, int
 // The chunk loop is a real loop, and EPI specialises the per-element work at compile time for the four hot GEMMs:
 //   EPI 1  bias -> 16-bit                  (qkv)          EPI 3  bias + fp32 residual -> fp32 [+ 16-bit]   (proj, lin2)
 //   EPI 2  bias -> GELU -> 16-bit          (lin1)         EPI 0  everything at run time (maps, ReLU, res_mod, ...)
-template <int EPI> struct EpiTraits {
-  static constexpr bool generic = (EPI == 0);
-};
-
 template <typename T, int EPI>
 __device__ __forceinline__ void epilogue_t256(char* smem, const f32x16 (&acc)[4][2], int grp, int wcol, int m0, int n0, int M, int N,
                                               const LaGemmEpilogue& e, int tid) {
@@ -1386,7 +1166,7 @@ __global__ __launch_bounds__(512, 2) void gemm_t256p_kernel(const T* __restrict_
 // from the accumulator layout (a register is 32 consecutive columns of one row per half wave: 128-byte segments).  ksplit > 1 cuts the
 // K range into chunks of kchunk (a multiple of 64) that run as independent tiles: dW[N, K] = dY^T X over 10^4 - 10^5 tokens has
 // 9 - 36 output tiles only, the chunks are what fills the chip.
-static int g_gemm_variant = 2;       // see launch_t256p (0: the BK = 32 persistent kernel everywhere)
+static int g_gemm_variant = 2;       // see plan_t256 in gemm_plan.h (0: the BK = 32 persistent kernel everywhere)
 
 #ifdef LA_DEBUG
 constexpr int LA_DBG_NSTAMP = 64;
@@ -1605,127 +1385,6 @@ __global__ __launch_bounds__(512, 2) void gemm_t256q_kernel(const T* __restrict_
   }
 }
 
-
-template <typename T, int EPI>
-static void launch_t256q(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  constexpr int LDS = 2 * 65536 + 8 * 2048 + 8 * 512;       // two k-tile buffers + 2 KiB slab per wave + row tables: 148 KiB
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256q_kernel<T, EPI>), LDS, attr_mask);
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (ncu <= 0) ncu = 256;
-  }
-  int ksplit = 1, kchunk = K;
-  if (EPI == 4) {
-    // chunks of c k-tiles (every chunk, the last included, at least 2 deep): ONE round of tiles over the chip.  Every chunk ends in
-    // 64 K fp32 atomics on its output tile, and the chunks of a tile serialise on them in L2: with K = 46912 and 9 output tiles,
-    // 16 / 28 / 32 / 64 / 114 chunks measured 97 / - / 131 / 155 / 210 us (more than one round also pays the tile quantisation)
-    const int tmn = ((M + 255) / 256) * (N / 256), nkt = K / 64;
-    int want = ncu / tmn;
-    static const char* wenv = la_dbg_env("LA_KSPLIT_WANT");      // debugging: force the number of K chunks
-    if (wenv) want = atoi(wenv);
-    if (want > nkt / 2) want = nkt / 2;
-    if (want < 1) want = 1;
-    int c = (nkt + want - 1) / want;
-    if (c < 2) c = 2;
-    while (c < nkt && (nkt % c) == 1) ++c;
-    if (c > nkt) c = nkt;
-    kchunk = c * 64;
-    ksplit = (nkt + c - 1) / c;
-  }
-  const int ntiles = ((M + 255) / 256) * (N / 256) * ksplit;
-  int grid = ntiles < ncu ? ntiles : ncu;
-  static const char* genv = la_dbg_env("LA_KSPLIT_GRID");      // debugging: workgroups launched (0 = one per tile)
-  if (EPI == 4 && genv) grid = atoi(genv) > 0 ? atoi(genv) : ntiles;
-  hipLaunchKernelGGL((gemm_t256q_kernel<T, EPI>), dim3(grid), dim3(512), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m(N >= 2560 ? 8 : 2) | (g_gemm_variant & 0x800500), ksplit, kchunk);
-}
-
-template <typename T, int NPL, int EPI>
-static void launch_t256p(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  // main loop of the single-plane 64-deep shapes (la_gemm_variant): 2 (default) = the four-wave kernel (gemm_w4.hip; its own epilogue on
-  // interior unmapped tiles - lin1, lin2, proj - and epilogue_wave elsewhere: measured ahead of the eight-wave kernel on every encoder
-  // shape, profiles/r05_notes.md), 1 = the eight-wave quadrant-phase kernel
-  const int var = g_gemm_variant & 0xff;
-  const bool k64 = NPL == 1 && (K % 64) == 0 && K >= 128 && (e.a_kmod == 0 || (e.a_kmod % 64) == 0);
-  if (k64 && var == 2) return launch_t256w<T, EPI>(A, lda, W, ldw, M, N, K, e, tile_group_m(N >= 2560 ? 8 : 2) | (g_gemm_variant & 0xf500), st);
-  if (k64 && var >= 1) return launch_t256q<T, EPI>(A, lda, W, ldw, M, N, K, e, st);
-  constexpr int LDS = ((NPL == 2) ? 3 * 49152 : 4 * 32768 + 8 * 512) + 8 * 2048;      // ring + 2 KiB slab per wave (+ row tables): 148 / 160 KiB
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256p_kernel<T, NPL, EPI>), LDS, attr_mask);
-  static int ncu = 0;                                // (the GPUs of one host are the same part)
-  if (ncu == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (ncu <= 0) ncu = 256;
-  }
-  const int ntiles = ((M + 255) / 256) * (N / 256);
-  const int grid = ntiles < ncu ? ntiles : ncu;
-  hipLaunchKernelGGL((gemm_t256p_kernel<T, NPL, EPI>), dim3(grid), dim3(512), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m(2));
-}
-
-template <typename T, int NPL, int EPI>
-static void launch_t256_epi(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  constexpr int LDS = (NPL == 2) ? 3 * 49152 : 136 * 1024;     // ring 144 / 128 KiB; epilogue: two staging buffers of 65 KiB
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256_kernel<T, NPL, EPI>), LDS, attr_mask);
-  const int ntm = (M + 255) / 256, ntn = (N + 255) / 256;
-  hipLaunchKernelGGL((gemm_t256_kernel<T, NPL, EPI>), dim3(ntm * ntn), dim3(512), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m(2));
-}
-
-// pick the compile-time epilogue variant that covers this call (see epilogue_t256)
-template <typename T, int NPL>
-static void launch_t256(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  const bool plain = e.map == LA_MAP_NONE && e.res_mod == 0;
-  static const char* nop = la_dbg_env("LA_GEMM_NO_PERSISTENT");
-  const bool al = (N % 256) == 0 && K / 32 >= 8 && !nop && (e.ld16 % 8) == 0;
-  if (al && plain && e.act == LA_ACT_NONE && !e.res && !e.out32 && e.out16) return launch_t256p<T, NPL, 1>(A, lda, W, ldw, M, N, K, e, st);
-  // qkv of a SAM window block from image-order tokens: rows scattered into window order by the epilogue (no padded rows multiplied)
-  const bool scatter = e.map == LA_MAP_WINDOW_PART && e.res_mod == 0 && e.amap == LA_MAP_NONE && e.act == LA_ACT_NONE && !e.res && !e.out32 &&
-                       e.out16 && (NPL == 1 || (e.vt && e.vt_col0 == 0)) &&
-                       (!e.vt || (size_t)((M + e.vt_T - 1) / e.vt_T + 4096) * e.vt_heads * e.vt_hd * e.vt_Tpad < (1ull << 32));
-  if (al && scatter) return launch_t256p<T, NPL, 1>(A, lda, W, ldw, M, N, K, e, st);
-  if (al && plain && e.act == LA_ACT_GELU && !e.res && !e.out32 && e.out16 && !e.vt) return launch_t256p<T, NPL, 2>(A, lda, W, ldw, M, N, K, e, st);
-  // a residual that repeats every res_mod rows (the patch embedding's position table: one row per token of the image) stays on the
-  // persistent four-wave kernel when whole 256-row tiles sit inside one period - its direct epilogue takes the residual rows modulo
-  const bool w4_resmod = NPL == 1 && e.map == LA_MAP_NONE && e.res_mod > 0 && (e.res_mod % 256) == 0 && (M % 256) == 0 && e.res && (g_gemm_variant & 0xff) == 2 &&
-                         (K % 64) == 0 && K >= 128 && (e.a_kmod == 0 || (e.a_kmod % 64) == 0) && !((g_gemm_variant >> 8) & 1);
-  if (al && (plain || w4_resmod) && e.act == LA_ACT_NONE && e.out32 && !e.vt && (e.ld32 % 4) == 0 && (!e.res || (e.ldr % 4) == 0)) {
-    // (fp32 atomics from the accumulator layout instead of the read-modify-write through the slab were measured in round 4 and are
-    // slower: profiles/r04_notes.md 1)
-    return launch_t256p<T, NPL, 3>(A, lda, W, ldw, M, N, K, e, st);
-  }
-  if (plain && e.act == LA_ACT_NONE && !e.res && !e.out32 && e.out16) launch_t256_epi<T, NPL, 1>(A, lda, W, ldw, M, N, K, e, st);
-  else if (plain && e.act == LA_ACT_GELU && !e.res && !e.out32 && e.out16 && !e.vt) launch_t256_epi<T, NPL, 2>(A, lda, W, ldw, M, N, K, e, st);
-  else if (plain && e.act == LA_ACT_NONE && e.res && e.out32 && !e.vt) launch_t256_epi<T, NPL, 3>(A, lda, W, ldw, M, N, K, e, st);
-  else launch_t256_epi<T, NPL, 0>(A, lda, W, ldw, M, N, K, e, st);
-}
-
-template <typename T, int BM_>
-static void launch_fast(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  constexpr int LDS = fast_lds_bytes<BM_>();
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_dma_kernel<T, BM_>), LDS, attr_mask);
-  const int ntm = (M + BM_ - 1) / BM_, ntn = (N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_dma_kernel<T, BM_>), dim3(ntm * ntn), dim3(BM_ * 2), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, tile_group_m());
-}
-
-static bool fast_ok(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if ((K % 64) != 0) return false;
-  if ((size_t)M * lda * 2 >= (1ull << 32) || (size_t)N * ldw * 2 >= (1ull << 32)) return false;   // 32-bit DMA offsets
-  if (!al16(A) || !al16(W)) return false;
-  return epi_vec_ok(N, e, 2);
-}
-
-
 // =================================================================================================================
 // fp32 path (dt == LA_F32): exact-fp32 MFMA v_mfma_f32_32x32x2_f32 (bitwise an fmaf chain, 157 TF/s peak).
 // Same 128 x 128 tile / 4 waves / register-staged double buffer as gemm_nt_kernel with BK = 32 floats (128-byte
@@ -1879,17 +1538,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const float* __restric
   }
 }
 
-template <int BN_>
-static void launch_f32(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, const ConvA& cv,
-                       hipStream_t st) {
-  constexpr int EPI = 128 * (BN_ + 4) * 4;
-  constexpr int LDS = (2 * (BM + BN_) * 128) > EPI ? (2 * (BM + BN_) * 128) : EPI;
-  const int vec_epi = epi_vec_ok(N, e, 4) ? 1 : 0;
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_f32_kernel<BN_>), LDS, attr_mask);
-  const int ntm = (M + BM - 1) / BM, ntn = (N + BN_ - 1) / BN_;
-  hipLaunchKernelGGL(gemm_f32_kernel<BN_>, dim3(ntm * ntn), dim3(256), LDS, st, reinterpret_cast<const float*>(A), lda,
-                     reinterpret_cast<const float*>(W), ldw, M, N, K, e, cv, vec_epi);
+static void launch_f32(const LaGemmPlan& p, const GemmArgs& g, const ConvA& cv) {
+  with_int<32, 128>(p.kernel == LA_GEMM_F32_N32 ? 32 : 128, [&](auto bn) { launch<float, gemm_f32_kernel<LA_V(bn)>>(dim3(p.grid), p, g, cv, p.epi); });
 }
 
 // =================================================================================================================
@@ -1987,21 +1637,12 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const T* __restrict__ 
   }
 }
 
-template <typename T, int KW>
-static void launch_skinny_kw(const T* a, int lda, const T* w, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  const int groups = (N + SK_COLS - 1) / SK_COLS;
-  const dim3 grid(KW == 4 ? groups : (groups + 3) / 4, M > 32 ? (M + 31) / 32 : 1), block(256);
-  if (M <= 8) hipLaunchKernelGGL((gemm_skinny_kernel<T, 8, KW>), grid, block, 0, st, a, lda, w, ldw, M, N, K, e);
-  else if (M <= 16) hipLaunchKernelGGL((gemm_skinny_kernel<T, 16, KW>), grid, block, 0, st, a, lda, w, ldw, M, N, K, e);
-  else hipLaunchKernelGGL((gemm_skinny_kernel<T, 32, KW>), grid, block, 0, st, a, lda, w, ldw, M, N, K, e);
-}
-
 template <typename T>
-static void launch_skinny(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  const T* a = reinterpret_cast<const T*>(A);
-  const T* w = reinterpret_cast<const T*>(W);
-  if (K >= 1024) launch_skinny_kw<T, 4>(a, lda, w, ldw, M, N, K, e, st);
-  else launch_skinny_kw<T, 1>(a, lda, w, ldw, M, N, K, e, st);
+static void launch_skinny(const LaGemmPlan& p, const GemmArgs& g) {      // MR rows per workgroup pass, KW-wide k stride of the lanes
+  const dim2 d = skinny_grid(g.M, g.N, g.K);
+  with_int<1, 4>(g.K >= 1024 ? 4 : 1, [&](auto kw) {
+    with_int<8, 16, 32>(g.M <= 8 ? 8 : g.M <= 16 ? 16 : 32, [&](auto mr) { launch<T, gemm_skinny_kernel<T, LA_V(mr), LA_V(kw)>>(dim3(d.x, d.y), p, g); });
+  });
 }
 
 // =================================================================================================================
@@ -2073,26 +1714,79 @@ __global__ __launch_bounds__(256) void gemm_f32_small_kernel(const float* __rest
   }
 }
 
-static void launch_f32_small(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, hipStream_t st) {
-  const int tm = (M + 31) / 32, tn = (N + 31) / 32;
-  if (K >= 1024)
-    hipLaunchKernelGGL(gemm_f32_small_kernel<4>, dim3(tn, tm), dim3(256), 0, st, reinterpret_cast<const float*>(A), lda,
-                       reinterpret_cast<const float*>(W), ldw, M, N, K, e);
-  else
-    hipLaunchKernelGGL(gemm_f32_small_kernel<1>, dim3((tn + 1) / 2, (tm + 1) / 2), dim3(256), 0, st, reinterpret_cast<const float*>(A), lda,
-                       reinterpret_cast<const float*>(W), ldw, M, N, K, e);
+static void launch_f32_small(const LaGemmPlan& p, const GemmArgs& g) {
+  const dim2 d = f32_small_grid(g.M, g.N, g.K);
+  with_int<1, 4>(g.K >= 1024 ? 4 : 1, [&](auto ks) { launch<float, gemm_f32_small_kernel<LA_V(ks)>>(dim3(d.x, d.y), p, g); });
 }
 
+// la_gemm behind its plan (gemm_plan.h): the one place a kernel family becomes an instantiation
 template <typename T>
-static int launch_gemm(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e,
-                       hipStream_t st) {
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_nt_kernel<T>), 2 * STAGE_BYTES, attr_mask);
-  const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-  hipLaunchKernelGGL(gemm_nt_kernel<T>, dim3(ntm * ntn), dim3(256), 2 * STAGE_BYTES, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e);
-  return 0;
+static void launch_plan(const LaGemmPlan& p, const GemmArgs& g, int stg) {
+  const dim3 grid(p.grid);
+  if constexpr (std::is_same<T, float>::value) {
+    switch (p.kernel) {
+      case LA_GEMM_F32_SMALL: return launch_f32_small(p, g);
+      case LA_GEMM_SKINNY: return launch_skinny<float>(p, g);
+      default: return launch_f32(p, g, ConvA{0, 0, 0, 0});
+    }
+  } else {
+    switch (p.kernel) {
+      case LA_GEMM_SKINNY: return launch_skinny<T>(p, g);
+      case LA_GEMM_NT: return launch<T, gemm_nt_kernel<T>>(grid, p, g);
+      case LA_GEMM_DMA128: return launch<T, gemm_dma_kernel<T, 128>>(grid, p, g, p.gm);
+      case LA_GEMM_DMA256x128: return launch<T, gemm_dma4_kernel<T>>(grid, p, g, p.gm);
+      case LA_GEMM_T256:
+        return (void)with_int<1, 2>(p.planes, [&](auto npl) {
+          with_int<0, 1, 2, 3>(p.epi, [&](auto e) { launch<T, gemm_t256_kernel<T, LA_V(npl), LA_V(e)>>(grid, p, g, p.gm); });
+        });
+      case LA_GEMM_T256P:
+        return (void)with_int<1, 2>(p.planes, [&](auto npl) {
+          with_int<1, 2, 3>(p.epi, [&](auto e) { launch<T, gemm_t256p_kernel<T, LA_V(npl), LA_V(e)>>(grid, p, g, p.gm); });
+        });
+      case LA_GEMM_T256Q:
+        return (void)with_int<1, 2, 3, 4>(p.epi, [&](auto e) { launch<T, gemm_t256q_kernel<T, LA_V(e)>>(grid, p, g, p.gm, p.ksplit, p.kchunk); });
+      default:      // LA_GEMM_T256W: EPI 1 - 3 by the shared / direct epilogue, 5 / 6 for both 16-bit types, 7 - 12 (the folded LayerNorm) fp16 only
+        with_int<1, 2, 3>(p.epi, [&](auto e) { launch_t256w<T, LA_V(e)>(p, g, stg); });
+        with_int<5, 6>(p.epi, [&](auto e) { launch_t256w_fused<T, LA_V(e)>(p, g, stg); });
+        if constexpr (std::is_same<T, f16_t>::value) with_int<7, 8, 9, 10, 11, 12>(p.epi, [&](auto e) { launch_t256w_fused<T, LA_V(e)>(p, g, stg); });
+    }
+  }
 }
+
+#ifdef LA_DEBUG
+// The measurement library only: the environment edits the FINISHED plan - the pure plan never sees it.  LA_GEMM_PATH: family of the 16-bit
+// tile shapes ("v1" register staged, "2" 128x128, "4" 256x128, "7" the 256 x 256 kernels); LA_GEMM_NO_PERSISTENT: gemm_t256_kernel instead
+// of the persistent kernels; LA_NO_F32_SMALL: the VALU kernel for every few-row fp32 shape; LA_KSPLIT_WANT / LA_KSPLIT_GRID: K chunks /
+// workgroups (0 = one per tile) of split-K; LA_GEMM_GROUP_M; LA_W4_GRID: workgroups of gemm_t256w; LA_W4_STAGGER "P,D": P start classes, D x 1024 cycles apart
+static void plan_debug_overrides(LaGemmPlan* p, uintptr_t A, int lda, uintptr_t W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int ncu,
+                                 int variant, int* stg) {
+  static const char *path = getenv("LA_GEMM_PATH"), *nop = getenv("LA_GEMM_NO_PERSISTENT"), *nosmall = getenv("LA_NO_F32_SMALL"),
+                    *want = getenv("LA_KSPLIT_WANT"), *kgrid = getenv("LA_KSPLIT_GRID"), *gmenv = getenv("LA_GEMM_GROUP_M"),
+                    *w4grid = getenv("LA_W4_GRID"), *stagger = getenv("LA_W4_STAGGER");
+  const bool tiles16 = p->kernel <= LA_GEMM_T256P || (p->kernel == LA_GEMM_T256Q && p->epi != 4) || (p->kernel == LA_GEMM_T256W && p->epi <= 3);
+  const int planes = p->planes;
+  if (tiles16 && path && (path[0] == 'v' || p->kernel != LA_GEMM_NT)) {
+    *p = plan_default(K);
+    if (path[0] == 'v') plan_launch(p, LA_GEMM_NT, M, N, K, ncu, variant);
+    else if (path[0] == '7' && (!e.vt || (e.vt_col0 % 256) == 0)) plan_t256(p, planes, M, N, K / planes, e, ncu, variant);
+    else plan_launch(p, path[0] == '4' || (path[0] != '2' && K <= 1536 && tiles_of(M, N, 256, 128) >= 512) ? LA_GEMM_DMA256x128 : LA_GEMM_DMA128, M, N, K, ncu, variant);
+  }
+  if (tiles16 && nop && p->kernel >= LA_GEMM_T256P) {
+    *p = plan_default(K);
+    plan_t256(p, planes, M, N, K / planes, e, ncu, variant, false);
+  }
+  if (nosmall && p->kernel == LA_GEMM_F32_SMALL) plan_launch(p, LA_GEMM_SKINNY, M, N, K, ncu, variant);
+  if (p->kernel == LA_GEMM_T256Q && p->epi == 4) {
+    if (want) ksplit_chunks(K / 64, atoi(want), p), plan_launch(p, LA_GEMM_T256Q, M, N, K, ncu, variant);
+    if (kgrid) p->grid = atoi(kgrid) > 0 ? atoi(kgrid) : (int)tiles_of(M, N, 256, 256) * p->ksplit;
+  }
+  if (gmenv && group_m(p->kernel, N)) p->gm = (p->gm & ~0xff) | atoi(gmenv);
+  if (p->kernel == LA_GEMM_T256W) {
+    if (w4grid && atoi(w4grid) > 0 && atoi(w4grid) < p->grid) p->grid = atoi(w4grid);
+    if (stagger) *stg = (atoi(stagger) << 16) | (strchr(stagger, ',') ? atoi(strchr(stagger, ',') + 1) : 0);
+  }
+}
+#endif
 
 }  // namespace la
 
@@ -2118,189 +1812,41 @@ extern "C" int la_dbg_gemm_stamps_clear() {
 }
 #endif
 
-// (the persistent kernel pays off from one tile per CU of the CURRENT device - not a constant, not cached across devices)
-extern "C" int la_gemm_fused_act_ok(int M, int N, int K) {
-  int dev = 0, ncu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-  return M > 0 && (N % 256) == 0 && (K % 64) == 0 && K >= 128 && (long)((M + 255) / 256) * (N / 256) >= ncu && (la::g_gemm_variant & 0xff) == 2;
+// (the CU count of the CURRENT device: la::cu_count caches per device)
+extern "C" int la_gemm_fused_act_ok(int M, int N, int K) { return la::fused_act_ok(M, N, K, la::cu_count(), la::g_gemm_variant); }
+
+// the plan of a call, with la_gemm's errors; ncu <= 0: the current device's.  (-DLA_DEBUG: then edited from the environment, *stg = start stagger)
+static int gemm_plan_checked(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue* epi, int dt, int ncu,
+                             LaGemmPlan* p, int* stg) {
+  LA_CHECK_ARG(A && W && epi && p, "la_gemm: null pointer");
+  if (ncu <= 0) ncu = la::cu_count();
+  const uintptr_t a = reinterpret_cast<uintptr_t>(A), w = reinterpret_cast<uintptr_t>(W);
+  char err[640];
+  if (la::gemm_plan(a, lda, w, ldw, M, N, K, *epi, dt, ncu, la::g_gemm_variant, p, err, sizeof(err)) != 0) {
+    la_set_error("%s", err);
+    return -1;
+  }
+#ifdef LA_DEBUG
+  la::plan_debug_overrides(p, a, lda, w, ldw, M, N, K, *epi, ncu, la::g_gemm_variant, stg);
+#endif
+  return 0;
+}
+
+extern "C" int la_gemm_plan(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue* epi, int dt, int ncu,
+                            LaGemmPlan* out) {
+  int stg = 0;
+  return gemm_plan_checked(A, lda, W, ldw, M, N, K, epi, dt, ncu, out, &stg);
 }
 
 extern "C" int la_gemm(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue* epi, int dt,
                        void* stream) {
-  LA_CHECK_ARG(A && W && epi, "la_gemm: null pointer");
-  LA_CHECK_ARG(M > 0 && N > 0 && K > 0, "la_gemm: bad shape M=%d N=%d K=%d", M, N, K);
-  // (the four-wave epilogue reaches the 128 rows of a wave's block with 32-bit byte offsets from the tile's base: 128 x ld x 4 B < 2^31)
-  LA_CHECK_ARG(epi->ld16 < (1 << 22) && epi->ldaux < (1 << 22) && epi->ld32 < (1 << 22) && epi->ldr < (1 << 22) && N < (1 << 22),
-               "la_gemm: output / residual leading dimensions must be below %d elements", 1 << 22);
-  const int kq = (dt == LA_F32) ? 4 : 8;
-  LA_CHECK_ARG((K % kq) == 0 && (lda % kq) == 0 && (ldw % kq) == 0, "la_gemm: K, lda, ldw must be multiples of %d (K=%d lda=%d ldw=%d)", kq, K,
-               lda, ldw);
-  LA_CHECK_ARG(epi->out32 || epi->out16 || epi->vt, "la_gemm: no output");
-  LA_CHECK_ARG(epi->a_kmod == 0 || (dt != LA_F32 && epi->a_kmod > 0 && (epi->a_kmod % 64) == 0 && epi->a_kmod <= K && lda >= epi->a_kmod && M > 32),
-               "la_gemm: a_kmod=%d must be a multiple of 64, <= K=%d and <= lda=%d (16-bit operands, M > 32)", epi->a_kmod, K, lda);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16 || dt == LA_F32, "la_gemm: bad dtype %d", dt);
-  LA_CHECK_ARG(epi->amap == LA_MAP_NONE || (epi->amap == LA_MAP_WINDOW_PART && epi->map == LA_MAP_NONE && dt != LA_F32) ||
-                   (epi->amap == LA_MAP_CONV3X3 && epi->map == LA_MAP_NONE && dt == LA_F16 && epi->a_kmod == 0 && epi->p1 > 0 && (epi->p1 % 64) == 0 &&
-                    K == 27 * epi->p1 && epi->p2 == lda && lda == 2 * epi->p1 && epi->p0 > 2 && (N % 256) == 0 && !epi->vt && epi->ksplit == 0 && M > 512),
-               "la_gemm: amap must be LA_MAP_NONE, LA_MAP_WINDOW_PART (16-bit operands, no output map) or LA_MAP_CONV3X3 (fp16 plane pairs, p0 = padded "
-               "width, p1 = C %% 64 == 0, p2 = lda = 2 C, K = 27 C, N %% 256 == 0), got amap=%d map=%d dt=%d", epi->amap, epi->map, dt);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LA_CHECK_ARG(epi->act != LA_ACT_GELU_BWD || epi->aux16, "la_gemm: LA_ACT_GELU_BWD needs aux16 (the saved pre-activation)");
-  if (epi->aux16 && !epi->nstat_out) {
-    // the training forms of the MLP's GELU (see LaGemmEpilogue.aux16): the direct epilogue of the persistent four-wave kernel only
-    LA_CHECK_ARG(epi->act == LA_ACT_GELU || epi->act == LA_ACT_GELU_BWD, "la_gemm: aux16 goes with LA_ACT_GELU (written) or LA_ACT_GELU_BWD (read)");
-    LA_CHECK_ARG(dt != LA_F32 && la_gemm_fused_act_ok(M, N, K) && la::fast_ok(A, lda, W, ldw, M, N, K, *epi),
-                 "la_gemm: aux16 needs 16-bit operands and a shape la_gemm_fused_act_ok() accepts (M=%d N=%d K=%d)", M, N, K);
-    LA_CHECK_ARG(epi->out16 && !epi->out32 && !epi->res && !epi->vt && epi->map == LA_MAP_NONE && epi->amap == LA_MAP_NONE && epi->a_kmod == 0 &&
-                     epi->ksplit == 0 && (epi->ld16 % 8) == 0 && (epi->ldaux % 8) == 0 && epi->ld16 >= N && epi->ldaux >= N &&
-                     ((reinterpret_cast<uintptr_t>(epi->out16) | reinterpret_cast<uintptr_t>(epi->aux16)) & 15) == 0,
-                 "la_gemm: aux16 forms write out16 only (no residual / fp32 output / maps / V^T / planes), rows 16-byte aligned");
-    LA_CHECK_ARG(epi->act == LA_ACT_GELU || !epi->bias, "la_gemm: LA_ACT_GELU_BWD takes no bias");
-    const int gm = la::tile_group_m(N >= 2560 ? 8 : 2);
-    if (epi->act == LA_ACT_GELU) {
-      if (dt == LA_F16) la::launch_t256w_fused<la::f16_t, 5>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-      else la::launch_t256w_fused<la::bf16_t, 5>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    } else {
-      if (dt == LA_F16) la::launch_t256w_fused<la::f16_t, 6>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-      else la::launch_t256w_fused<la::bf16_t, 6>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    }
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  if (epi->nstat_out || epi->nstat_in || epi->rvec) {
-    // LayerNorm folded into its neighbour GEMMs (see LaGemmEpilogue.nstat_out): the direct epilogue of the persistent four-wave kernel only
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    LA_CHECK_ARG(dt == LA_F16 && (N % 256) == 0 && K >= 128 && (epi->a_kmod == 0 || (epi->a_kmod % 64) == 0) &&
-                     la::fast_ok(A, lda, W, ldw, M, N, K, *epi) && (la::g_gemm_variant & 0xff) == 2,
-                 "la_gemm: nstat_out / nstat_in need fp16 operands, N %% 256 == 0, K %% 64 == 0, K >= 128, 16-byte aligned rows (M=%d N=%d K=%d)", M,
-                 N, K);
-    LA_CHECK_ARG(!epi->vt && epi->map == LA_MAP_NONE && epi->amap == LA_MAP_NONE && epi->ksplit == 0 && !(epi->nstat_out && epi->nstat_in) &&
-                     (!epi->aux16 || (epi->nstat_out && (epi->ldaux % 8) == 0 && epi->ldaux >= N && (reinterpret_cast<uintptr_t>(epi->aux16) & 15) == 0)),
-                 "la_gemm: nstat_out / nstat_in take no row maps / V^T / ksplit, not both at once; aux16 only with nstat_out (the lo plane, 16-byte aligned rows)");
-    const int gm = la::tile_group_m(N >= 2560 ? 8 : 2);
-    if (epi->nstat_in) {
-      LA_CHECK_ARG(epi->ncol && epi->out16 && !epi->out32 && !epi->res && !epi->rvec && (epi->act == LA_ACT_NONE || epi->act == LA_ACT_GELU) &&
-                       (epi->ld16 % 8) == 0 && epi->ld16 >= N && al16(epi->out16) && al16(epi->nstat_in) && al16(epi->ncol) && epi->a_kmod == 0,
-                   "la_gemm: nstat_in writes out16 only (act NONE / GELU), needs ncol, one weight plane");
-      if (epi->act == LA_ACT_GELU) la::launch_t256w_fused<la::f16_t, 9>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-      else la::launch_t256w_fused<la::f16_t, 8>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    } else if (epi->nstat_out && !epi->out32 && epi->res && epi->aux16) {
-      // fp32 residual in (the position table of the patch embedding), plane pairs out, no fp32 matrix at all
-      LA_CHECK_ARG(epi->out16 && epi->act == LA_ACT_NONE && (epi->ld16 % 8) == 0 && epi->ld16 >= N && al16(epi->out16) && (epi->ldr % 4) == 0 &&
-                       (reinterpret_cast<uintptr_t>(epi->nstat_out) & 7) == 0 && !epi->rvec,
-                   "la_gemm: nstat_out with a residual and no out32 writes plane pairs only (out16 + aux16), no group vector");
-      LA_CHECK_ARG(epi->res_mod == 0 || ((epi->res_mod % 256) == 0 && (M % 256) == 0),
-                   "la_gemm: nstat_out with a periodic residual needs res_mod %% 256 == 0 and M %% 256 == 0 (res_mod=%d M=%d)", epi->res_mod, M);
-      la::launch_t256w_fused<la::f16_t, 7>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    } else if (epi->nstat_out && !epi->out32 && !epi->res) {
-      // the stream as fp16 plane pairs, read-modify-written in place: out16 = hi plane, aux16 = lo plane (see LaGemmEpilogue.nstat_out)
-      LA_CHECK_ARG(epi->out16 && epi->aux16 && epi->act == LA_ACT_NONE && (epi->ld16 % 8) == 0 && (epi->ldaux % 8) == 0 && epi->ld16 >= N &&
-                       epi->ldaux >= N && al16(epi->out16) && al16(epi->aux16) && (reinterpret_cast<uintptr_t>(epi->nstat_out) & 7) == 0 && epi->res_mod == 0,
-                   "la_gemm: nstat_out without out32 / res updates a plane-pair stream in place: out16 (hi) and aux16 (lo), 16-byte aligned rows");
-      LA_CHECK_ARG(!epi->rvec || (epi->rvec_rpg > 0 && al16(epi->rvec) && ((epi->rvec_rpg % 256) == 0 || epi->rvec_rpg >= 128)),
-                   "la_gemm: rvec needs a 16-byte aligned vector and groups of whole 256-row tiles or of at least 128 rows (rvec_rpg=%d)", epi->rvec_rpg);
-      if (epi->rvec && (epi->rvec_rpg % 256) != 0) la::launch_t256w_fused<la::f16_t, 12>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-      else la::launch_t256w_fused<la::f16_t, 11>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    } else {
-      LA_CHECK_ARG(epi->nstat_out && epi->out32 && epi->out16 && epi->act == LA_ACT_NONE && (epi->ld16 % 8) == 0 && epi->ld16 >= N &&
-                       (epi->ld32 % 4) == 0 && epi->ld32 >= N && al16(epi->out16) && al16(epi->out32) && (!epi->res || (epi->ldr % 4) == 0) &&
-                       (reinterpret_cast<uintptr_t>(epi->nstat_out) & 7) == 0,
-                   "la_gemm: nstat_out goes with out32 + out16 (no activation), 16-byte aligned rows");
-      LA_CHECK_ARG(epi->res_mod == 0 || ((epi->res_mod % 256) == 0 && (M % 256) == 0 && epi->res),
-                   "la_gemm: nstat_out with a periodic residual needs res_mod %% 256 == 0 and M %% 256 == 0 (res_mod=%d M=%d)", epi->res_mod, M);
-      LA_CHECK_ARG(!epi->rvec || (epi->rvec_rpg > 0 && al16(epi->rvec) && ((epi->rvec_rpg % 256) == 0 || epi->rvec_rpg >= 128)),
-                   "la_gemm: rvec needs a 16-byte aligned vector and groups of whole 256-row tiles or of at least 128 rows (rvec_rpg=%d)", epi->rvec_rpg);
-      if (epi->rvec && (epi->rvec_rpg % 256) != 0) la::launch_t256w_fused<la::f16_t, 10>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-      else la::launch_t256w_fused<la::f16_t, 7>(A, lda, W, ldw, M, N, K, *epi, gm, st);
-    }
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  // up to 512 fp32 rows (decoder tokens of many prompt pairs): an MFMA grid of 128 x 128 tiles is a handful of workgroups and leaves the
-  // chip idle (240 x 256 x 2048: 155 us on four tiles) - 32 x 32 wave tiles (gemm_f32_small_kernel) above 128 rows, the VALU kernel below
-  const bool few_rows = M <= 32 || (dt == LA_F32 && M <= 512 && (long)((M + 127) / 128) * ((N + 127) / 128) < 64);
-  const bool skinny = few_rows && (K % 8) == 0 && epi->map == LA_MAP_NONE && epi->amap == LA_MAP_NONE && !epi->vt;
-  static const char* nosmall = la_dbg_env("LA_NO_F32_SMALL");   // debugging: the row-chunked VALU kernel for every few-row fp32 shape
-  // (from 129 rows: up to 128 rows - the per-image vectors of the encoder's token-mean corrections, one row per image - stay on the VALU
-  // kernel, whose lane-parallel partial sums round 4 x closer to fp64 than the MFMA's serial chain (9e-8 against 4e-7 on 52 x 768 x 1536);
-  // the corrections accumulate over every block of the encoder and a 26- and a 52-image batch must not take different kernels:
-  // tests/test_model_gpu.py::test_full_geometry_episode_properties measured 2.7e-4 on the cfg3 logits between the two)
-  if (skinny && dt == LA_F32 && M > 128 && !nosmall && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) == 0) {
-    la::launch_f32_small(A, lda, W, ldw, M, N, K, *epi, st);       // (K, lda, ldw are multiples of 4 here: float4 operand loads)
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  if (skinny) {
-    if (dt == LA_F32) la::launch_skinny<float>(A, lda, W, ldw, M, N, K, *epi, st);
-    else if (dt == LA_F16) la::launch_skinny<la::f16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-    else la::launch_skinny<la::bf16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  if (dt == LA_F32) {
-    LA_CHECK_ARG(!epi->vt, "la_gemm: the transposed-V epilogue is 16-bit only");
-    const la::ConvA nocv{0, 0, 0, 0};
-    if (N <= 32) la::launch_f32<32>(A, lda, W, ldw, M, N, K, *epi, nocv, st);
-    else la::launch_f32<128>(A, lda, W, ldw, M, N, K, *epi, nocv, st);
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  if (epi->ksplit > 0) {
-    // split-K accumulate (weight gradients): out32 += A . W^T with fp32 atomics, K cut into independent chunks
-    LA_CHECK_ARG(epi->out32 && !epi->out16 && !epi->res && !epi->bias && !epi->vt && epi->act == LA_ACT_NONE &&
-                     (epi->map == LA_MAP_NONE || (epi->map == LA_MAP_GROUP && epi->p0 > 0)) && epi->amap == LA_MAP_NONE && epi->a_kmod == 0,
-                 "la_gemm: ksplit accumulates the bare product into out32 (no bias / residual / activation / second output; row map none or LA_MAP_GROUP)");
-    LA_CHECK_ARG((N % 256) == 0 && (K % 64) == 0 && K >= 128 && (size_t)M * lda * 2 < (1ull << 32) && (size_t)N * ldw * 2 < (1ull << 32) &&
-                     (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0,
-                 "la_gemm: ksplit needs N %% 256 == 0, K %% 64 == 0, K >= 128, 16-byte aligned operands below 4 GiB (M=%d N=%d K=%d)", M, N, K);
-    if (dt == LA_F16) la::launch_t256q<la::f16_t, 4>(A, lda, W, ldw, M, N, K, *epi, st);
-    else la::launch_t256q<la::bf16_t, 4>(A, lda, W, ldw, M, N, K, *epi, st);
-    LA_CHECK_LAUNCH("la_gemm");
-    return 0;
-  }
-  static const char* force = la_dbg_env("LA_GEMM_PATH");   // debugging: "v1" (register staged), "2" (128x128), "4" (256x128), "6" (256x256)
-  bool fast = la::fast_ok(A, lda, W, ldw, M, N, K, *epi) && !(force && force[0] == 'v');
-  if (fast) {
-    // measured on MI355X (profiles/r01_gemm_variants.log): the 256x128 / 128x64-per-wave kernel wins by ~5 % on the short-K
-    // (K = 768) shapes once there are >= 2 full waves of tiles; the 128x128 kernel wins on long K and small grids.
-    const long tiles256 = (long)((M + 255) / 256) * ((N + la::BN - 1) / la::BN);
-    bool v4 = (K <= 1536) && (tiles256 >= 512);
-    if (force && force[0] == '4') v4 = true;
-    if (force && force[0] == '2') v4 = false;
-    // long-K shapes with >= 2 full waves of 256 x 256 tiles: the ping-pong kernel (+15 % on 65536x768x3072)
-    const long tiles_pp = (long)((M + la::PP_BM - 1) / la::PP_BM) * ((N + la::PP_BN - 1) / la::PP_BN);
-    bool pp = (K > 1536) && (tiles_pp >= 512);
-    if (force) pp = force[0] == '6';
-    pp = pp && (!epi->vt || (epi->vt_col0 % la::PP_BN) == 0);
-    // two weight planes against one A ([W_hi | W_lo], a_kmod = K / 2): the 256 x 256 two-plane kernel, which reuses every A fragment
-    // for both planes; LA_GEMM_PATH=7 also sends single-plane shapes through its NPL = 1 form (A/B experiments)
-    const bool planes2 = epi->a_kmod > 0 && K == 2 * epi->a_kmod;
-    // ... and, measured on MI355X (tools/gemm_planes_bench.py), its single-plane form beats the 256 x 128, the 128 x 128 and the older
-    // ping-pong kernel on every shape with >= 2 full rounds of 256 x 256 tiles (K = 768: +10-15 %, K = 3072: equal)
-    bool t256 = ((planes2 && tiles_pp >= 128) || (!planes2 && tiles_pp >= 512)) && (!epi->vt || (epi->vt_col0 % 256) == 0);
-    if (force) t256 = (force[0] == '7') && (!epi->vt || (epi->vt_col0 % 256) == 0);
-    if (t256) {
-      if (planes2) {
-        if (dt == LA_F16) la::launch_t256<la::f16_t, 2>(A, lda, W, ldw, M, N, K / 2, *epi, st);
-        else la::launch_t256<la::bf16_t, 2>(A, lda, W, ldw, M, N, K / 2, *epi, st);
-      } else {
-        if (dt == LA_F16) la::launch_t256<la::f16_t, 1>(A, lda, W, ldw, M, N, K, *epi, st);
-        else la::launch_t256<la::bf16_t, 1>(A, lda, W, ldw, M, N, K, *epi, st);
-      }
-    } else if (pp) {
-      if (dt == LA_F16) la::launch_pp<la::f16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-      else la::launch_pp<la::bf16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-    } else if (v4) {
-      if (dt == LA_F16) la::launch_fast4<la::f16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-      else la::launch_fast4<la::bf16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-    } else {
-      if (dt == LA_F16) la::launch_fast<la::f16_t, 128>(A, lda, W, ldw, M, N, K, *epi, st);
-      else la::launch_fast<la::bf16_t, 128>(A, lda, W, ldw, M, N, K, *epi, st);
-    }
-  } else {
-    if (dt == LA_F16) la::launch_gemm<la::f16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-    else la::launch_gemm<la::bf16_t>(A, lda, W, ldw, M, N, K, *epi, st);
-  }
+  LaGemmPlan p;
+  int stg = 0;
+  if (gemm_plan_checked(A, lda, W, ldw, M, N, K, epi, dt, 0, &p, &stg) != 0) return -1;
+  const la::GemmArgs g{A, W, lda, ldw, M, N, K, *epi, reinterpret_cast<hipStream_t>(stream)};
+  if (dt == LA_F32) la::launch_plan<float>(p, g, stg);
+  else if (dt == LA_F16) la::launch_plan<la::f16_t>(p, g, stg);
+  else la::launch_plan<la::bf16_t>(p, g, stg);
   LA_CHECK_LAUNCH("la_gemm");
   return 0;
 }
@@ -2313,11 +1859,10 @@ extern "C" int la_conv3x3_f32(const float* in, int B, int H, int W, int Cin, con
   e.bias = bias;
   e.out32 = out32;
   e.ld32 = Cout;
-  const la::ConvA cv{1, H, W, Cin};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int M = B * H * W, K = 9 * Cin;
-  if (Cout <= 32) la::launch_f32<32>(in, Cin, wt, K, M, Cout, K, e, cv, st);
-  else la::launch_f32<128>(in, Cin, wt, K, M, Cout, K, e, cv, st);
+  LaGemmPlan p = la::plan_default(K);
+  la::plan_f32(&p, M, Cout, K, e);
+  la::launch_f32(p, la::GemmArgs{in, wt, Cin, K, M, Cout, K, e, reinterpret_cast<hipStream_t>(stream)}, la::ConvA{1, H, W, Cin});
   LA_CHECK_LAUNCH("la_conv3x3_f32");
   return 0;
 }

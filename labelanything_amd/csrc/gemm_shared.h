@@ -1,6 +1,7 @@
 // Device code shared by the la_gemm translation units (gemm.hip, gemm_w4.hip): row maps, the A-operand maps and the wave-private
 // epilogue of the persistent 256 x 256 kernels (a 128 x 64 accumulator block through a 2 KiB slab).
 #pragma once
+#include <type_traits>
 #include "la_common.h"
 #include "../../include/la_hip.h"
 
@@ -392,10 +393,34 @@ __device__ __forceinline__ void epilogue_wave(char* slab, unsigned* rtab, f32x16
   }
 }
 
-// gemm_w4.hip: the four-wave persistent 256 x 256 x 64 kernel (EPI 1 / 2 / 3 as epilogue_wave; K % 64 == 0, K >= 128, N % 256 == 0)
+// one la_gemm call as its launchers see it
+struct GemmArgs {
+  const void *A, *W;
+  int lda, ldw, M, N, K;
+  const LaGemmEpilogue& e;
+  hipStream_t st;
+};
+
+// launch kernel instantiation Kern as its plan says (K = depth of one weight plane; extra = the kernel's arguments behind the epilogue)
+template <typename T, auto Kern, typename... Extra>
+static void launch(dim3 grid, const LaGemmPlan& p, const GemmArgs& g, Extra... extra) {
+  static unsigned long long attr_mask = 0;
+  if (p.lds_bytes) ensure_dyn_lds(reinterpret_cast<const void*>(Kern), p.lds_bytes, attr_mask);
+  hipLaunchKernelGGL(Kern, grid, dim3(p.block), p.lds_bytes, g.st, reinterpret_cast<const T*>(g.A), g.lda, reinterpret_cast<const T*>(g.W), g.ldw, g.M,
+                     g.N, g.K / p.planes, g.e, extra...);
+}
+
+// f(std::integral_constant<int, E>) for the E among Es that v equals: a plan field becomes a template argument; false: none did
+template <int... Es, typename F>
+static bool with_int(int v, F&& f) {
+  return (((v == Es) && (f(std::integral_constant<int, Es>{}), true)) || ...);
+}
+#define LA_V(x) decltype(x)::value
+
+// gemm_w4.hip: the four-wave persistent 256 x 256 x 64 kernel (EPI 1 / 2 / 3 as epilogue_wave); stg: start stagger (measurement library only, else 0)
 template <typename T, int EPI>
-void launch_t256w(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st);
+void launch_t256w(const LaGemmPlan& p, const GemmArgs& g, int stg);
 template <typename T, int EPI>
-void launch_t256w_fused(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st);
+void launch_t256w_fused(const LaGemmPlan& p, const GemmArgs& g, int stg);
 
 }  // namespace la

@@ -855,75 +855,33 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
 }
 
 template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false>
-static void launch_t256w_abl(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st) {
-  constexpr int LDS = 4 * 32768 + 4 * 8192;      // two k-tile buffers + 8 KiB slab per wave: all 160 KiB
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>), LDS, attr_mask);
-  static int ncu_of[64] = {0};                        // per device: a process may drive several GPUs
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int& ncu = ncu_of[dev & 63];
-  if (ncu == 0) {
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (ncu <= 0) ncu = 256;
-  }
-  const int ntiles = ((M + 255) / 256) * (N / 256);
-  int grid = ntiles < ncu ? ntiles : ncu;
-  int stg = 0;
-  static const char* genv = la_dbg_env("LA_W4_GRID");        // debugging: workgroups launched
-  if (genv && atoi(genv) > 0 && atoi(genv) < grid) grid = atoi(genv);
-  static const char* senv = la_dbg_env("LA_W4_STAGGER");     // debugging: "P,D" = P start classes, D x 1024 cycles apart
-  if (senv) stg = (atoi(senv) << 16) | (strchr(senv, ',') ? atoi(strchr(senv, ',') + 1) : 0);
-  hipLaunchKernelGGL((gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>), dim3(grid), dim3(256), LDS, st, reinterpret_cast<const T*>(A), lda,
-                     reinterpret_cast<const T*>(W), ldw, M, N, K, e, gm & 0x5ff, stg);
+static void launch_t256w_abl(const LaGemmPlan& p, const GemmArgs& g, int stg) {
+  launch<T, gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>>(dim3(p.grid), p, g, p.gm & 0x5ff, stg);
 }
 
 template <typename T, int EPI>
-void launch_t256w(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st) {
+void launch_t256w(const LaGemmPlan& p, const GemmArgs& g, int stg) {
 #ifdef LA_DEBUG
   // la_gemm_variant bits 12-15 = ABL (EPI 1 only)
-  if (EPI == 1) {
-    switch ((gm >> 12) & 15) {
-      case 1: return launch_t256w_abl<T, 1, 1, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 2: return launch_t256w_abl<T, 1, 2, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 3: return launch_t256w_abl<T, 1, 3, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 4: return launch_t256w_abl<T, 1, 4, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 5: return launch_t256w_abl<T, 1, 5, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 7: return launch_t256w_abl<T, 1, 7, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 8: return launch_t256w_abl<T, 1, 8, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      case 14: return launch_t256w_abl<T, 1, 14, false>(A, lda, W, ldw, M, N, K, e, gm, st);
-      default: break;
-    }
-  }
+  if (EPI == 1 && with_int<1, 2, 3, 4, 5, 7, 8, 14>((p.gm >> 12) & 15, [&](auto abl) { launch_t256w_abl<T, 1, LA_V(abl), false>(p, g, stg); })) return;
 #endif
-  // (a ragged last row tile - M % 256 != 0: the HF encoders' 57664 = 225.25 tiles - stays on the direct epilogue: its loads and stores are
-  // predicated on the row; a residual modulo res_mod needs whole tiles inside a period and is only sent here with M % 256 == 0)
-  const bool direct = e.map == LA_MAP_NONE && !e.vt && !((gm >> 8) & 1);
-  if (direct && (M & 255) == 0) launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm, st);
-  else if (direct) launch_t256w_abl<T, EPI, 0, true, true>(A, lda, W, ldw, M, N, K, e, gm, st);
-  else launch_t256w_abl<T, EPI, 0, false>(A, lda, W, ldw, M, N, K, e, gm, st);
+  if (p.direct && !p.ragged) launch_t256w_abl<T, EPI, 0, true>(p, g, stg);
+  else if (p.direct) launch_t256w_abl<T, EPI, 0, true, true>(p, g, stg);
+  else launch_t256w_abl<T, EPI, 0, false>(p, g, stg);
 }
 
 // EPI 5 / 6 (GELU forward that also keeps the pre-activation; data gradient times gelu' - training only) exist on the direct epilogue alone
 template <typename T, int EPI>
-void launch_t256w_fused(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const LaGemmEpilogue& e, int gm, hipStream_t st) {
-  if ((M & 255) == 0) launch_t256w_abl<T, EPI, 0, true>(A, lda, W, ldw, M, N, K, e, gm & ~0x100, st);
-  else launch_t256w_abl<T, EPI, 0, true, true>(A, lda, W, ldw, M, N, K, e, gm & ~0x100, st);
+void launch_t256w_fused(const LaGemmPlan& p, const GemmArgs& g, int stg) {
+  if (!p.ragged) launch_t256w_abl<T, EPI, 0, true>(p, g, stg);
+  else launch_t256w_abl<T, EPI, 0, true, true>(p, g, stg);
 }
-template void launch_t256w_fused<f16_t, 5>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 6>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<bf16_t, 5>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<bf16_t, 6>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-// EPI 7 / 10 / 8 / 9: the producer and consumer sides of a folded LayerNorm (LaGemmEpilogue.nstat_out / nstat_in), fp16 operands
-template void launch_t256w_fused<f16_t, 7>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 10>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 8>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 9>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 11>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
-template void launch_t256w_fused<f16_t, 12>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
+#define LA_W4_FUSED(T, EPI) template void launch_t256w_fused<T, EPI>(const LaGemmPlan&, const GemmArgs&, int);
+LA_W4_FUSED(f16_t, 5) LA_W4_FUSED(f16_t, 6) LA_W4_FUSED(bf16_t, 5) LA_W4_FUSED(bf16_t, 6)
+// EPI 7 / 10 / 8 / 9 / 11 / 12: the producer and consumer sides of a folded LayerNorm (LaGemmEpilogue.nstat_out / nstat_in), fp16 operands
+LA_W4_FUSED(f16_t, 7) LA_W4_FUSED(f16_t, 10) LA_W4_FUSED(f16_t, 8) LA_W4_FUSED(f16_t, 9) LA_W4_FUSED(f16_t, 11) LA_W4_FUSED(f16_t, 12)
 
-#define LA_W4_INST(T, EPI) \
-  template void launch_t256w<T, EPI>(const void*, int, const void*, int, int, int, int, const LaGemmEpilogue&, int, hipStream_t);
+#define LA_W4_INST(T, EPI) template void launch_t256w<T, EPI>(const LaGemmPlan&, const GemmArgs&, int);
 LA_W4_INST(f16_t, 1) LA_W4_INST(f16_t, 2) LA_W4_INST(f16_t, 3)
 LA_W4_INST(bf16_t, 1) LA_W4_INST(bf16_t, 2) LA_W4_INST(bf16_t, 3)
 

@@ -216,6 +216,16 @@ static inline void ensure_dyn_lds(const void* kernel, int bytes, unsigned long l
   if (dev >= 0 && dev < 64) mask |= 1ull << dev;
 }
 
+// compute units of the CURRENT device, cached per device (a process may drive several GPUs)
+inline int cu_count() {
+  static int ncu_of[64] = {0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int& ncu = ncu_of[dev & 63];
+  if (ncu == 0 && (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)) ncu = 256;
+  return ncu;
+}
+
 // XCD-aware tile order: consecutive workgroups round-robin over the 8 XCDs, so give each XCD a
 // contiguous chunk of the tile sequence (bijective also when n % 8 != 0).
 __device__ __forceinline__ int xcd_remap(int bid, int n) {

@@ -464,8 +464,20 @@ def test_gemm_window_partition_output_and_gather(L, dt, shape):
 
 
 def test_gemm_shape_fuzz_all_kernel_paths(L):
-    """Seeded sweep over ragged shapes (M / N tails, every K granularity, fp32 and 16-bit, strided A) through every la_gemm
-    kernel (LA_GEMM_PATH is not forced: the dispatcher picks skinny / fallback / 128x128 / 256x128 / ping-pong by shape)."""
+    """Seeded sweep over ragged shapes (M / N tails, every K granularity, fp32 and 16-bit, strided A) through every la_gemm kernel
+    family.  Nothing is forced: the dispatch picks by shape, and la_gemm_plan (asked with the device's own CU count) says for every
+    case which family that was - the sweep must have run each family a call can reach at the default la_gemm_variant.  Two are left
+    to other tests by name: gemm_t256q with the epilogues of the persistent kernels (variant 1: test_gemm_four_wave_kernel_bit_identical)
+    and gemm_t256p with one weight plane (variant 0)."""
+    ran = set()
+
+    def family(a, w, m, n, k, **kw):
+        p = L.gemm_plan(a, a.stride(0), w, w.stride(0), m, n, k, L.dt_of(a), 0, **kw)
+        name = L.GEMM_KERNELS[p.kernel]
+        if (name == "T256Q" and p.epi != 4) or (name == "T256P" and p.planes == 1):
+            name += " (left to another test)"
+        ran.add(name)
+
     g = torch.Generator().manual_seed(1234)
     shapes = []
     for _ in range(36):
@@ -474,7 +486,8 @@ def test_gemm_shape_fuzz_all_kernel_paths(L):
         k = int(torch.randint(1, 24, (1,), generator=g)) * [8, 32, 64][int(torch.randint(0, 3, (1,), generator=g))]
         shapes.append((m, n, k))
     shapes += [(33, 8, 8), (257, 136, 72), (512, 512, 2048), (1025, 264, 64), (131072, 256, 64), (65536 + 17, 384, 128),
-               (4096, 1024, 2048), (131072, 1024, 2048)]       # the last: 512 ping-pong tiles (K >= 2048) -> gemm_pp_kernel
+               (4096, 1024, 2048), (131072, 1024, 2048),      # the last: 2048 tiles of 256 x 256 behind a ReLU -> gemm_t256_kernel, generic epilogue
+               (65280, 384, 64), (600, 32, 64)]               # 765 tiles of 256 x 128 (510 of 256 x 256) -> gemm_dma4_kernel; fp32 N <= 32
     for idx, (m, n, k) in enumerate(shapes):
         for dt in (torch.float16, torch.float32):
             if dt == torch.float32 and (m * n * k > 3e9):
@@ -492,17 +505,36 @@ def test_gemm_shape_fuzz_all_kernel_paths(L):
             if use_res:
                 ref = ref + res
             o32 = torch.full((m, n), float("nan"), device="cuda")
+            family(a, w, m, n, k, bias=bias, res=res, out32=o32, act=act)
             L.gemm(a_full, w, bias=bias, res=res, out32=o32, act=act, lda=lda) if lda != k else L.gemm(a, w, bias=bias, res=res, out32=o32, act=act)
             torch.cuda.synchronize()
             tol = 2e-5 if dt == torch.float32 else 1e-3
             assert torch.isfinite(o32).all(), (m, n, k, dt)
             assert rel_err(o32, ref) < tol, (m, n, k, dt, float(rel_err(o32, ref)))
+    # the families an fp32 output with bias (+ residual) never reaches, each at its smallest shape: 512 tiles of 256 x 256 with a 16-bit
+    # output (the four-wave kernel), 128 tiles against two weight planes (gemm_t256p), a split-K accumulation (gemm_t256q, EPI 4)
+    dt = torch.float16
+    for m, n, k, kw in [(131072, 256, 256, {}), (32768, 256, 512, {"a_kmod": 256}), (128, 256, 5056, {"ksplit": 1})]:
+        a = rnd(m, kw.get("a_kmod", k), seed=500 + k).to(dt)
+        w = (rnd(n, k, seed=501 + k) / math.sqrt(k)).to(dt)
+        bias = None if kw else rnd(n, seed=502)
+        out = torch.zeros(m, n, device="cuda", dtype=torch.float32 if kw else dt)
+        kw = dict(kw, bias=bias, **({"out32": out} if kw else {"out16": out}))
+        family(a, w, m, n, k, **kw)
+        L.gemm(a, w, **kw)
+        torch.cuda.synchronize()
+        wsum = w.float() if "a_kmod" not in kw else w[:, :256].float() + w[:, 256:].float()
+        ref = a.float() @ wsum.t() + (bias if bias is not None else 0)
+        assert rel_err(out, ref) < (1e-3 if kw.get("out32") is not None else TOL16[dt]), (m, n, k, float(rel_err(out, ref)))
+    reachable = {"NT", "DMA128", "DMA256x128", "T256", "T256P", "T256Q", "T256W", "F32_N32", "F32_N128", "F32_SMALL", "SKINNY"}
+    assert reachable == set(L.GEMM_KERNELS)
+    assert ran >= reachable, sorted(reachable - ran)
 
 
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("mnk", [(300, 200, 768),          # 128x128 LDS-DMA kernel
                                  (256 * 80, 1024, 768),     # >= 512 tiles of 256x128: 256x128 kernel (K = 1536 with two planes)
-                                 (256 * 48, 3072, 1024),    # >= 512 tiles of 256x256, K = 2048: ping-pong kernel
+                                 (256 * 48, 3072, 1024),    # >= 128 tiles of 256x256 with two planes: the persistent two-plane kernel
                                  (40, 72, 64)])             # unaligned N: register-staged kernel
 def test_gemm_split_precision_weights(L, dt, mnk):
     """a_kmod: W = [W_hi | W_lo] against ONE 16-bit A -> the weights enter with ~2x the mantissa bits.

@@ -54,7 +54,7 @@ if __name__ == "__main__":
         sys.argv.remove("--one")
         one()
     else:
-        for path in (sys.argv[1:] or ["", "7", "6", "4", "2"]):
+        for path in (sys.argv[1:] or ["", "7", "4", "2"]):
             env = dict(os.environ)
             if path and path != "auto":
                 env["LA_GEMM_PATH"] = path
