@@ -38,10 +38,12 @@ enum { LA_ATTN_PLAIN = 0, LA_ATTN_RELPOS = 1, LA_ATTN_RELPOS_WIN16 = 2 };
 const char* la_last_error(void);
 int la_version(void);
 
-/* Tuning hook of la_gemm (measurement A/B only, results are bit-identical): 1 = 64-deep quadrant-phase main loop where it
- * applies (default), 0 = the 32-deep persistent kernel everywhere; v < 0 only queries.  Returns the previous value.
- * Only bit 0 is honoured by the product library; the timing ablations behind the higher bits and every environment
+/* Tuning hook of la_gemm (measurement A/B only, results are bit-identical): 2 = the four-wave main loop where it applies (default),
+ * 1 = the 64-deep quadrant-phase main loop, 0 = the 32-deep persistent kernel everywhere; + LA_GEMM_VARIANT_MFMA32 (0x10000): the
+ * four-wave main loop stays on the 32x32x16 MFMA where the plan would take 16x16x32; v < 0 only queries.  Returns the previous value.
+ * Only these values are honoured by the product library; the timing ablations behind the higher bits and every environment
  * override of kernel selection are compiled into the -DLA_DEBUG library alone (`make -C labelanything_amd/csrc DEBUG=1`). */
+enum { LA_GEMM_VARIANT_MFMA32 = 0x10000 };
 int la_gemm_variant(int v);
 
 /* Epilogue of la_gemm: out = map( act(A.W^T + bias) + residual ).
@@ -146,17 +148,25 @@ int la_gemm(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
  *  direct / ragged   LA_GEMM_T256W: the kernel's own epilogue on unmapped tiles / its form with a partial last row tile (M % 256 != 0)
  *  gm       row panels per tile group (bits 0-7; a -DLA_DEBUG library carries la_gemm_variant's ablation bits above them)
  *  ksplit, kchunk    K chunks that run as independent tiles and their depth (1, K unless LaGemmEpilogue.ksplit)
- *  grid, block, lds_bytes   workgroups, threads per workgroup, dynamic LDS of the launch */
+ *  grid, block, lds_bytes   workgroups, threads per workgroup, dynamic LDS of the launch
+ *  mfma     LA_GEMM_T256W with its direct epilogue: the MFMA shape of the main loop, 0 = 32x32x16, 1 = 16x16x32 (bit-identical sums; 0 on
+ *           every other kernel) */
 enum { LA_GEMM_NT = 0, LA_GEMM_DMA128, LA_GEMM_DMA256x128, LA_GEMM_T256, LA_GEMM_T256P, LA_GEMM_T256Q, LA_GEMM_T256W,
        LA_GEMM_F32_N32, LA_GEMM_F32_N128, LA_GEMM_F32_SMALL, LA_GEMM_SKINNY };
 typedef struct LaGemmPlan {
-  int kernel, epi, planes, direct, ragged, gm, ksplit, kchunk, grid, block, lds_bytes;
+  int kernel, epi, planes, direct, ragged, gm, ksplit, kchunk, grid, block, lds_bytes, mfma;
 } LaGemmPlan;
 
 /* la_gemm's decision without the launch: same arguments (A and W are only tested for NULL and alignment, never read - any address
  * will do), same checks and error texts; ncu <= 0 = the CU count of the current device.  Fills *out, launches nothing. */
 int la_gemm_plan(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                  const LaGemmEpilogue* epi, int dt, int ncu, LaGemmPlan* out);
+
+/* The 32 x 32 product out[32][32] (fp32) = A[32, K] . W[32, K]^T of 16-bit operands on ONE wave, K % 64 == 0 walked in ascending 64-deep
+ * tiles, on either MFMA shape of gfx950: shape 0 = v_mfma_f32_32x32x16 (four k-steps per tile), 1 = v_mfma_f32_16x16x32 (two).  Not a
+ * product path: the probe behind tests/test_mfma_shape_gpu.py, which records whether the two shapes round alike - what decides whether a
+ * GEMM main loop may change its MFMA shape without moving results. */
+int la_mfma_shape_probe(const void* A, const void* W, float* out, int K, int dt, int shape, void* stream);
 
 /* 3x3 / pad 1 convolution as an IMPLICIT GEMM on the exact-fp32 MFMA (no im2col buffer): in fp32 NHWC [B,H,W,Cin]
  * (Cin % 32 == 0), wt fp32 [Cout, (ky,kx,cin)], bias fp32 [Cout] or NULL -> out32 fp32 NHWC [B*H*W, Cout]

@@ -73,13 +73,18 @@ EXPORTS = [
     "la_classify_wide", "la_classify_wide_bwd", "la_level_reduce", "la_level_reduce_bwd",
     "la_proto_kernels", "la_proto_kernels_bwd", "la_classify_conv", "la_classify_conv_bwd",
     "la_extract_pool_plan", "la_extract_pool", "la_extract_fold", "la_extract_unfold",
+    "la_mfma_shape_probe",
 ]
+
+
+GEMM_VARIANT_MFMA32 = 0x10000
 
 
 def gemm_variant(v: int = -1) -> int:
     """la_gemm_variant: the persistent kernel of the single-plane shapes with K % 64 == 0, K >= 128 (``gemm_plan`` says which calls those
     are) - 2 (default): gemm_t256w, four waves x 512 registers (gemm_w4.hip); 1: gemm_t256q, eight waves in quadrant phases; 0:
     gemm_t256p, the BK 32 kernel, which two-plane shapes take at every value.  The LaGemmEpilogue.aux16 / nstat_* forms exist at 2 only.
+    + GEMM_VARIANT_MFMA32: gemm_t256w keeps the 32x32x16 MFMA where the plan (``LaGemmPlan.mfma``) would take 16x16x32.
     All are bit-identical; v < 0 only queries.  Returns the previous value."""
     return int(lib().la_gemm_variant(int(v)))
 
@@ -114,7 +119,7 @@ def _dev(t: torch.Tensor) -> None:
 
 # ----------------------------------------------------------------------------------------------
 class LaGemmPlan(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("kernel", "epi", "planes", "direct", "ragged", "gm", "ksplit", "kchunk", "grid", "block", "lds_bytes")]
+    _fields_ = [(f, C.c_int) for f in ("kernel", "epi", "planes", "direct", "ragged", "gm", "ksplit", "kchunk", "grid", "block", "lds_bytes", "mfma")]
 
 
 GEMM_KERNELS = ("NT", "DMA128", "DMA256x128", "T256", "T256P", "T256Q", "T256W", "F32_N32", "F32_N128", "F32_SMALL", "SKINNY")   # LaGemmPlan.kernel
@@ -188,6 +193,18 @@ def gemm_plan(a, lda: int, w, ldw: int, m: int, n: int, k: int, dt: int, ncu: in
                             C.c_int(dt), C.c_int(ncu), C.byref(plan))
     _check(rc, "la_gemm_plan")
     return plan
+
+
+def mfma_shape_probe(a: torch.Tensor, w: torch.Tensor, shape: int) -> torch.Tensor:
+    """la_mfma_shape_probe: a [32, K] . w [32, K]^T (16-bit, K % 64 == 0) on one wave with MFMA shape 0 (32x32x16) or 1 (16x16x32),
+    fp32 [32, 32]: the accumulators as they are, K ascending in 64-deep tiles."""
+    _dev(a)
+    if a.dtype != w.dtype or a.shape != w.shape or a.shape[0] != 32 or not (a.is_contiguous() and w.is_contiguous()):
+        raise RuntimeError("mfma_shape_probe: a and w must be contiguous [32, K] of one 16-bit type")
+    out = torch.empty(32, 32, device=a.device, dtype=torch.float32)
+    rc = lib().la_mfma_shape_probe(_ptr(a), _ptr(w), _ptr(out), C.c_int(a.shape[1]), C.c_int(dt_of(a)), C.c_int(shape), _stream())
+    _check(rc, "la_mfma_shape_probe")
+    return out
 
 
 def norm_finalize(part: Optional[torch.Tensor], m: int, e: int, eps: float, mr: torch.Tensor, x16: Optional[torch.Tensor] = None, rpg: int = 0,

@@ -1762,7 +1762,7 @@ static void plan_debug_overrides(LaGemmPlan* p, uintptr_t A, int lda, uintptr_t 
                                  int variant, int* stg) {
   static const char *path = getenv("LA_GEMM_PATH"), *nop = getenv("LA_GEMM_NO_PERSISTENT"), *nosmall = getenv("LA_NO_F32_SMALL"),
                     *want = getenv("LA_KSPLIT_WANT"), *kgrid = getenv("LA_KSPLIT_GRID"), *gmenv = getenv("LA_GEMM_GROUP_M"),
-                    *w4grid = getenv("LA_W4_GRID"), *stagger = getenv("LA_W4_STAGGER");
+                    *w4grid = getenv("LA_W4_GRID"), *stagger = getenv("LA_W4_STAGGER"), *w4mfma = getenv("LA_W4_MFMA");
   const bool tiles16 = p->kernel <= LA_GEMM_T256P || (p->kernel == LA_GEMM_T256Q && p->epi != 4) || (p->kernel == LA_GEMM_T256W && p->epi <= 3);
   const int planes = p->planes;
   if (tiles16 && path && (path[0] == 'v' || p->kernel != LA_GEMM_NT)) {
@@ -1784,6 +1784,7 @@ static void plan_debug_overrides(LaGemmPlan* p, uintptr_t A, int lda, uintptr_t 
   if (p->kernel == LA_GEMM_T256W) {
     if (w4grid && atoi(w4grid) > 0 && atoi(w4grid) < p->grid) p->grid = atoi(w4grid);
     if (stagger) *stg = (atoi(stagger) << 16) | (strchr(stagger, ',') ? atoi(strchr(stagger, ',') + 1) : 0);
+    if (w4mfma && p->direct) p->mfma = atoi(w4mfma) == 16 ? w4_mfma_shape(1, p->epi, p->ragged, 1 << 20, 0) : 0;      // (16: wherever an instance exists)
   }
 }
 #endif
@@ -1795,7 +1796,7 @@ extern "C" int la_gemm_variant(int v) {
 #ifdef LA_DEBUG
   if (v >= 0) la::g_gemm_variant = v;       // bit 8 no stores, bit 10 seam stamps (la_dbg_gemm_stamps), bit 23 no epilogue
 #else
-  if (v >= 0 && v <= 2) la::g_gemm_variant = v;       // the product library only knows the bit-identical main loops
+  if (v >= 0 && (v & ~LA_GEMM_VARIANT_MFMA32) <= 2) la::g_gemm_variant = v;       // the product library only knows the bit-identical main loops
 #endif
   return prev;
 }

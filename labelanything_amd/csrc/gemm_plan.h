@@ -48,6 +48,22 @@ static inline int group_m(int kernel, int N) {
   return kernel == LA_GEMM_T256 || kernel == LA_GEMM_T256P ? 2 : 0;
 }
 
+// MFMA shape of the four-wave main loop (LaGemmPlan.mfma): 1 = v_mfma_f32_16x16x32 instead of 32x32x16 - same sums bit for bit
+// (tests/test_mfma_shape_gpu.py), half the passes per instruction, and a higher clock under the power limit.  Only the direct epilogue
+// has the 16 x 16 accumulator layout; EPI 12 and the ragged EPI 9 instance spill on that shape (hipcc -S: 16 / 8 bytes of scratch, the
+// former reloaded inside the tile loop) and stay as they are.  MEASURED per launch against the parent build (fp16, 393216 rows = whole
+// tiles, three alternations, kept where the median gain exceeds twice the larger min-to-max range; profiles/r12_mfma_shape.md):
+// q | k | v (EPI 1, 8) + 4.5 - 5.6 %, lin1 (EPI 2, 9) + 2.9 - 4.4 %, lin2 (K = 3072; EPI 3, 7, 11) + 4.9 - 5.5 %, the bare 8192^3 + 5.9 %;
+// NOT the short products behind a residual epilogue (proj, N = K = 768: EPI 3 + 1.2 %, plane pairs in place + 1.5 % - inside twice
+// the ranges; the epilogue's HBM round trips bound them), which stay on 32x32x16 below K = 1536.  EXTRAPOLATED from those, not timed
+// (same main loop, an epilogue whose only shape-dependent step is the slab dump): EPI 5 / 6 (the training GELU forms), EPI 10 from
+// K = 1536, every ragged instance (hipcc -S epilogue instruction counts equal to the 32x32x16 twins except ragged EPI 7, + 244 of 5171, and
+// ragged EPI 10, + 49 - both only from K = 1536, where a tile's main loop is ~130 k cycles), and all bf16 instances
+static inline int w4_mfma_shape(int direct, int epi, int ragged, int K, int variant) {
+  const bool res_epi = epi == 3 || epi == 7 || epi == 10 || epi == 11;
+  return direct && epi != 12 && !(epi == 9 && ragged) && !(res_epi && K < 1536) && !(variant & LA_GEMM_VARIANT_MFMA32) ? 1 : 0;
+}
+
 // persistent kernels: one workgroup per CU walks the tiles
 static inline int persistent_grid(long ntiles, int ncu) { return ntiles < ncu ? (int)ntiles : ncu; }
 
@@ -142,12 +158,14 @@ static inline void plan_t256(LaGemmPlan* p, int planes, int M, int N, int K, con
     p->gm |= variant & 0xf500;
     p->direct = e.map == LA_MAP_NONE && !e.vt && !((variant >> 8) & 1);
     p->ragged = p->direct && (M & 255) != 0;
+    p->mfma = w4_mfma_shape(p->direct, p->epi, p->ragged, K, variant);
   }
 }
 
 // the fused epilogues of the four-wave kernel (EPI 5 - 12: direct epilogue only)
 static inline void plan_w4_fused(LaGemmPlan* p, int epi, int M, int N, int K, int ncu, int variant) {
   p->epi = epi, p->direct = 1, p->ragged = (M & 255) != 0;
+  p->mfma = w4_mfma_shape(1, epi, p->ragged, K, variant);
   plan_launch(p, LA_GEMM_T256W, M, N, K, ncu, variant);
 }
 

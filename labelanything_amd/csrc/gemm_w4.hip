@@ -61,16 +61,40 @@ template <> struct MfmaA<bf16_t> {
   }
 };
 
+// The same on v_mfma_f32_16x16x32 (MS = 1: a block of 4 accumulator registers, col = lane & 15, row = 4 (lane >> 4) + reg; operands
+// A[row l & 15][k = 8 (l >> 4) + j]): half the passes per instruction, same FLOP per pass, bit-identical sums
+// (tests/test_mfma_shape_gpu.py) - and a higher sustained clock under the power limit (profiles/r12_mfma_shape.md).
+template <typename T> struct MfmaA16;
+template <> struct MfmaA16<f16_t> {
+  static __device__ __forceinline__ void go(f32x4& c, const u32x4& a, const u32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+  }
+};
+template <> struct MfmaA16<bf16_t> {
+  static __device__ __forceinline__ void go(f32x4& c, const u32x4& a, const u32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+  }
+};
+
 // accumulator := 0, defined in the AGPR class as well (0 . 0 + 0 on the matrix pipe): a v_mov / v_accvgpr_write form makes the loop-carried
 // accumulators VGPR-class values again
 __device__ __forceinline__ void acc_zero(f32x16& c) {
   const u32x4 z = {0u, 0u, 0u, 0u};
   asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %1, 0" : "=a"(c) : "v"(z));
 }
+__device__ __forceinline__ void acc_zero(f32x4& c) {
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %1, 0" : "=a"(c) : "v"(z));
+}
+// a wave's 128 x 128 accumulator block by MFMA shape (MS): 0 - [column half][32-row block][32-column tile in the half] of 16 registers
+// (acc[h] is one epilogue_wave block), 1 - [16-row block][16-column block] of 4
+template <int MS> struct W4Acc { typedef f32x16 type[2][4][2]; };
+template <> struct W4Acc<1> { typedef f32x4 type[8][8]; };
 
 #ifdef LA_DEBUG
 constexpr int LA_W4_NSTAMP = 128;
 __device__ unsigned long long g_w4_stamps[4 * LA_W4_NSTAMP];      // [wave][i] = s_memtime << 8 | tag (workgroup 0 of the last stamped launch)
+__device__ unsigned long long g_w4_rstamps[4 * LA_W4_NSTAMP];     // [wave][i] = s_memrealtime (100 MHz) of the same stamp: cycles / time = the clock held
 #endif
 
 // global memory at an address formed as an integer (a wave-uniform base + a 32-bit lane offset): the address space is stated, a generic
@@ -98,6 +122,12 @@ template <int N> __device__ __forceinline__ void wait_vm_lgkm0() { asm volatile(
   LA_W4_SB
 #define LA_W4_RW(KS, j) if constexpr (!(ABL & 2)) wf[KS][j] = lds_read16(waddr[KS] + (j) * 4096); LA_W4_SB
 #define LA_W4_RA(PAR, ii, i, KS) if constexpr (!(ABL & 2)) af[PAR][ii] = lds_read16(aaddr[KS] + (i) * 4096); LA_W4_SB
+// (MS = 1: fragments of 16 rows, 2048 bytes apart; k-step KS of 32)
+#define LA_W4_MF16(bi, bj, PAR, ii, KS)                                                      \
+  if constexpr (!(ABL & 8)) MfmaA16<T>::go(acc[bi][bj], af[PAR][ii], wf[KS][bj]); \
+  LA_W4_SB
+#define LA_W4_RW16(KS, j) if constexpr (!(ABL & 2)) wf[KS][j] = lds_read16(waddr[KS] + (j) * 2048); LA_W4_SB
+#define LA_W4_RA16(PAR, ii, bi, KS) if constexpr (!(ABL & 2)) af[PAR][ii] = lds_read16(aaddr[KS] + (bi) * 2048); LA_W4_SB
 #define LA_W4_PA0(src, i, bo) if constexpr (!(ABL & 1)) dma_piece<(i) * 1024>(src, soA0[i], dstA + (bo)); LA_W4_SB
 #define LA_W4_PA1(src, i, bo) if constexpr (!(ABL & 1)) dma_piece<8192 + (i) * 1024>(src, soA1[i], dstA + (bo)); LA_W4_SB
 #define LA_W4_PW(src, i, bo) if constexpr (!(ABL & 1)) dma_piece<(i) * 1024>(src, soW[i], dstW + (bo)); LA_W4_SB
@@ -131,8 +161,10 @@ template <int N> __device__ __forceinline__ void wait_vm_lgkm0() { asm volatile(
 // (zero fill, saveexec, branch, exec restore), and the loads of a round can neither be clustered nor hoisted across them.
 // Addresses: one wave-uniform 64-bit base per matrix and tile (an SGPR pair) + ONE 32-bit byte offset per lane and matrix; the rows of a
 // round add the uniform row stride to it and the column half is a constant - no 64-bit multiply-add per access.
-template <typename T, int EPI, bool RAGGED>
-__device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], int row0, int col0, const LaGemmEpilogue& e, int lane, int M, int N) {
+// MS = 1 (16x16x32 accumulator blocks): a block's four registers ARE a slab unit - rows 4 q .. 4 q + 3 of one column, q = 4 (row block & 1)
+// + (lane >> 4), c = 16 (column block & 3) + (lane & 15): 8 stores per round into the same image, everything behind the slab unchanged.
+template <typename T, int EPI, bool RAGGED, int MS = 0>
+__device__ __forceinline__ void epilogue_w4(char* slab, typename W4Acc<MS>::type& acc, int row0, int col0, const LaGemmEpilogue& e, int lane, int M, int N) {
   row0 = __builtin_amdgcn_readfirstlane(row0);
   col0 = __builtin_amdgcn_readfirstlane(col0);
   // (everything derived from the lane is a tile-loop invariant that hipcc would hoist into the main loop's registers and then spill: an
@@ -142,7 +174,10 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
   const int rq = lane >> 3, cg = lane & 7;
   const unsigned sl = lds_addr_of(slab);
   // write address of (g = 0, jj = 0): + g * 2048 (two quads) + jj * 512 (four column groups)
-  const unsigned waddr = sl + (unsigned)((fh * 64 + (fr & ~7) + ((fr & 7) ^ (((fr >> 3) ^ fh) & 7))) << 4);
+  // (MS = 1: the address of (row block 0, column block 0): + bil * 4096 (four quads) + bjl * 256 (two column groups); swizzle term
+  // ((2 bjl + (lane >> 3 & 1)) ^ (4 bil + (lane >> 4))) & 7 = the lane's part ^ (2 bjl) ^ (4 bil))
+  const unsigned waddr = MS ? sl + (unsigned)(((lane >> 4) * 64 + (lane & 8) + ((lane & 7) ^ ((((lane >> 3) & 1) ^ (lane >> 4)) & 7))) << 4)
+                            : sl + (unsigned)((fh * 64 + (fr & ~7) + ((fr & 7) ^ (((fr >> 3) ^ fh) & 7))) << 4);
   // (the swizzle term of tile jj, quad 2 g + fh: ((4 jj + (fr >> 3)) ^ (2 g + fh)) & 7 = ((fr >> 3) ^ fh) ^ (4 jj) ^ (2 g): XOR constants)
   unsigned raddr[8];
 #pragma unroll
@@ -213,15 +248,25 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
   T* out16 = reinterpret_cast<T*>(e.out16);
   auto wr = [&](auto ic, auto jpc) {
     constexpr int i = decltype(ic)::value, jp = decltype(jpc)::value;
+    if constexpr (MS == 1) {
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
+      for (int bil = 0; bil < 2; ++bil)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 v = {acc[jp][i][jj][4 * g], acc[jp][i][jj][4 * g + 1], acc[jp][i][jj][4 * g + 2], acc[jp][i][jj][4 * g + 3]};
-        // XOR constants of the swizzle: units (4 jj) ^ (2 g) inside the 8-unit group -> byte offset ((4 jj ^ 2 g) & 7) * 16
-        const unsigned a = (waddr ^ (unsigned)((((4 * jj) ^ (2 * g)) & 7) << 4)) + (unsigned)(g * 2048 + jj * 512);
-        *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((uintptr_t)a) = v;
-      }
+        for (int bjl = 0; bjl < 4; ++bjl) {
+          const unsigned a = (waddr ^ (unsigned)((((2 * bjl) ^ (4 * bil)) & 7) << 4)) + (unsigned)(bil * 4096 + bjl * 256);
+          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((uintptr_t)a) = acc[2 * i + bil][4 * jp + bjl];
+        }
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 v = {acc[jp][i][jj][4 * g], acc[jp][i][jj][4 * g + 1], acc[jp][i][jj][4 * g + 2], acc[jp][i][jj][4 * g + 3]};
+          // XOR constants of the swizzle: units (4 jj) ^ (2 g) inside the 8-unit group -> byte offset ((4 jj ^ 2 g) & 7) * 16
+          const unsigned a = (waddr ^ (unsigned)((((4 * jj) ^ (2 * g)) & 7) << 4)) + (unsigned)(g * 2048 + jj * 512);
+          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((uintptr_t)a) = v;
+        }
+    }
   };
   f32x4 rd0[8];
   auto rd = [&](f32x4 (&r)[8]) {
@@ -612,11 +657,16 @@ __device__ __forceinline__ void epilogue_w4(char* slab, f32x16 (&acc)[2][4][2], 
 // DIRECT: every tile is interior and unmapped (M % 256 == 0, no output row map, no V^T columns): epilogue_w4 only.  The two epilogues
 // do not share a kernel: with both behind a branch hipcc spills 128 accumulator registers to scratch in front of it.  For the same reason
 // the two forms of epilogue_w4 are two kernels: RAGGED (DIRECT only) is the launch with M % 256 != 0, whose last row tile is partial.
-template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false>
+// MS: the MFMA shape of the main loop - 0 v_mfma_f32_32x32x16 (LA_W4_BLOCK_*), 1 v_mfma_f32_16x16x32 (LA_W4_BLOCK16_*: DIRECT only - the
+// shared epilogue_wave reads the 32 x 32 accumulator layout).  Same tile walk, LDS image, pieces, buffers, waits and barriers.
+template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false, int MS = 0>
 __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict__ A, int lda, const T* __restrict__ Wt, int ldw, int M, int N,
                                                              int K, LaGemmEpilogue e, int gm, int stg) {
+  static_assert(MS == 0 || (MS == 1 && DIRECT), "the 16x16x32 main loop exists with the direct epilogue only");
   constexpr int BK_ = 64;
   constexpr unsigned REG = 32768;                     // one operand of one k-tile
+  constexpr int NKS = MS ? 2 : 4, NWF = MS ? 8 : 4;   // k-steps per k-tile, W fragments per k-step
+  constexpr unsigned FRAG = MS ? 2048 : 4096;         // bytes between the fragments of one k-step (16 / 32 rows)
   constexpr int SEAM = (EPI == 3 || EPI == 5 || EPI == 7 || EPI >= 10) ? 47 : 32;      // epilogue stores per wave that the first two waits of a tile may leave outstanding
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -625,9 +675,10 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
   int stamp_i = 0;
   auto stamp = [&](int tag) {
     if (stamps && stamp_i < LA_W4_NSTAMP) {
-      unsigned long long t_;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");
+      unsigned long long t_, r_;
+      asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "=s"(r_)::"memory");
       if (lane == 0) g_w4_stamps[wave * LA_W4_NSTAMP + stamp_i] = (t_ << 8) | (unsigned)tag;
+      if (lane == 0) g_w4_rstamps[wave * LA_W4_NSTAMP + stamp_i] = r_;
       ++stamp_i;
     }
   };
@@ -655,12 +706,14 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
   if (EPI == 1 && e.map != LA_MAP_NONE) rtab = reinterpret_cast<unsigned*>(slab + 2048);
 
   // ---- per-lane fragment addresses: row * 128 + swizzled chunk; + i * 4096 selects the 32-row fragment -----------------------------
-  unsigned aaddr[4], waddr[4];
+  // (MS = 1: row lane & 15, chunk 4 ks + (lane >> 4); + i * 2048 selects the 16-row fragment - 16 b + r has the swizzle term of r)
+  unsigned aaddr[NKS], waddr[NKS];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const unsigned coff = (unsigned)(((ks * 2 + fh) ^ ((fr >> 1) & 7)) << 4);
-    aaddr[ks] = lds0 + (wr * 128 + fr) * 128 + coff;
-    waddr[ks] = lds0 + 2 * REG + (wc * 128 + fr) * 128 + coff;
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int r_ = MS ? (lane & 15) : fr;
+    const unsigned coff = (unsigned)(((MS ? ks * 4 + (lane >> 4) : ks * 2 + fh) ^ ((r_ >> 1) & 7)) << 4);
+    aaddr[ks] = lds0 + (wr * 128 + r_) * 128 + coff;
+    waddr[ks] = lds0 + 2 * REG + (wc * 128 + r_) * 128 + coff;
   }
   // ---- LDS-DMA: destination bases of this wave's pieces (buffer 0) and per-lane source offsets ------------------------------------
   //   A0 piece i (4): rows (wave >> 1) * 128 + ((wave & 1) * 4 + i) * 8      A1: the same + 64      W piece i (8): rows (wave * 8 + i) * 8
@@ -694,15 +747,26 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
     }
   };
 
-  f32x16 acc[2][4][2];                                // [column half][i][j in half]: acc[h] is one epilogue_wave block
+  typename W4Acc<MS>::type acc;                       // (W4Acc)
+  auto acc_clear = [&]() {
+    if constexpr (MS == 1) {
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
+      for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 8; ++j)
+          acc_zero(acc[i][j]);
+    } else {
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc_zero(acc[h][i][j]);
-  u32x4 wf[4][4], af[2][2];
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc_zero(acc[h][i][j]);
+    }
+  };
+  acc_clear();
+  u32x4 wf[NKS][NWF], af[2][2];
 
   int tile = blockIdx.x;
   plan(tile, m0, n0, soA0, soA1, soW);
@@ -726,9 +790,9 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 #pragma unroll
-  for (int j = 0; j < 4; ++j) wf[0][j] = lds_read16(waddr[0] + j * 4096);
+  for (int j = 0; j < NWF; ++j) wf[0][j] = lds_read16(waddr[0] + j * FRAG);
 #pragma unroll
-  for (int ii = 0; ii < 2; ++ii) af[0][ii] = lds_read16(aaddr[0] + ii * 4096);
+  for (int ii = 0; ii < 2; ++ii) af[0][ii] = lds_read16(aaddr[0] + ii * FRAG);
   // aaddr[0] / waddr[0] point at the buffer their NEXT read comes from: block 3 (A of this k-tile), then block 7 (the next k-tile)
   waddr[0] ^= REG;
 
@@ -750,25 +814,45 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
     const unsigned bo1 = bofs ^ REG;                  // A1(t+1) lands in the OTHER buffer
     // ================= the k-tile: LA_W4_BLOCK_0 .. 7 (gemm_w4_ktile.inc, generated by tools/gen/w4_ktile.py) =========================
     // H1 blocks 0-2 (ks 0-2): reads of ks + 1 in the order of their first use (A_i0, W_0 .. W_3, A_i1), the A1 pieces; block 2 ends in wait + B1
-    LA_W4_BLOCK_0
-    LA_W4_BLOCK_1
-    LA_W4_BLOCK_2
+    // (MS = 1, LA_W4_BLOCK16_*: blocks 0, 1 = k-step 0 of row blocks 0-1, 2-3, blocks 2, 3 = k-step 1; H2 the same on row blocks 4-7)
+    if constexpr (MS == 1) {
+      LA_W4_BLOCK16_0
+      LA_W4_BLOCK16_1
+      LA_W4_BLOCK16_2
+    } else {
+      LA_W4_BLOCK_0
+      LA_W4_BLOCK_1
+      LA_W4_BLOCK_2
+    }
     if (prelast && more) plan(next, m0n, n0n, soA0, soA1n, soW);         // A0W(t+2) is the next tile's first k-tile
     const T* saw = A + a_koff(e, kAW * BK_);
     const T* sww = Wt + kAW * BK_;
 #pragma unroll
-    for (int ks = 1; ks < 4; ++ks) waddr[ks] ^= REG;  // (their next use is H1 of the next k-tile)
-    // block 3 (ks 3): reads of H2 ks 0, A0 pieces 0, 1
-    LA_W4_BLOCK_3
-    aaddr[0] ^= REG;                                  // next use: block 7, the first fragments of k-tile t+1
-    // H2 blocks 4-6 (ks 0-2): reads of ks + 1 (A_2, A_3 only), A0 pieces 2, 3, W pieces 0-6; block 6 ends in wait + B2
-    LA_W4_BLOCK_4
-    LA_W4_BLOCK_5
-    LA_W4_BLOCK_6
+    for (int ks = 1; ks < NKS; ++ks) waddr[ks] ^= REG;  // (their next use is H1 of the next k-tile)
+    if constexpr (MS == 1) {
+      // block 3 (k-step 1 of row blocks 2-3) reads row blocks 4-5 of k-step 0, block 4 row blocks 6-7: then aaddr[0] moves on
+      LA_W4_BLOCK16_3
+      LA_W4_BLOCK16_4
+      aaddr[0] ^= REG;
+      LA_W4_BLOCK16_5
+      LA_W4_BLOCK16_6
+    } else {
+      // block 3 (ks 3): reads of H2 ks 0, A0 pieces 0, 1
+      LA_W4_BLOCK_3
+      aaddr[0] ^= REG;                                  // next use: block 7, the first fragments of k-tile t+1
+      // H2 blocks 4-6 (ks 0-2): reads of ks + 1 (A_2, A_3 only), A0 pieces 2, 3, W pieces 0-6; block 6 ends in wait + B2
+      LA_W4_BLOCK_4
+      LA_W4_BLOCK_5
+      LA_W4_BLOCK_6
+    }
 #pragma unroll
-    for (int ks = 1; ks < 4; ++ks) aaddr[ks] ^= REG;
+    for (int ks = 1; ks < NKS; ++ks) aaddr[ks] ^= REG;
     // block 7 (ks 3): the first fragments of k-tile t+1 (other buffer), W piece 7
-    LA_W4_BLOCK_7
+    if constexpr (MS == 1) {
+      LA_W4_BLOCK16_7
+    } else {
+      LA_W4_BLOCK_7
+    }
     waddr[0] ^= REG;
     bofs ^= REG;
     seam = false;
@@ -780,10 +864,17 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
     // (the empty asm re-defines the accumulators in the AGPR class HERE: without it hipcc hoists the 128 AGPR -> VGPR copies the epilogue
     // needs into the k-tile loop, which then spills its DMA offsets - every reload is an s_waitcnt vmcnt(0) in front of a piece)
     const bool vtile = !DIRECT && EPI == 1 && e.vt != nullptr && n0 >= e.vt_col0;
+    if constexpr (MS == 1) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 8; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(acc[0][i][j]));
+        for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(acc[i][j]));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(acc[0][i][j]));
+    }
     // EPI >= 7 (folded LayerNorm: more live values in the epilogue than the register file has beside the main loop's): the 16 DMA source
     // offsets of the next tile wait out the epilogue in LDS - the wave's own A1 region of the buffer the finished k-tile used (4 KiB, 64 B
     // per lane) is dead from barrier B2 of that k-tile until the next tile's first A1 pieces, which are issued behind the epilogue.
@@ -798,7 +889,9 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
                    : "v"(stash), "v"(q0), "v"(q1), "v"(q2), "v"(q3)
                    : "memory");
     }
-    if constexpr (DIRECT) {
+    if constexpr (MS == 1) {
+      epilogue_w4<T, EPI, RAGGED, 1>(slab, acc, m0 + wr * 128, n0 + wc * 128, e, lane, M, N);
+    } else if constexpr (DIRECT) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -830,13 +923,7 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
         soW[4 + i] = q3[i];
       }
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc_zero(acc[h][i][j]);
+    acc_clear();
     m0 = m0n;
     n0 = n0n;
     tile = next;
@@ -845,18 +932,31 @@ __global__ __launch_bounds__(256, 1) void gemm_t256w_kernel(const T* __restrict_
       // the first fragments of the next tile again (block 7 already read them): 24 registers that are then dead across the epilogue,
       // which needs them for its residual ring - six LDS reads per tile against spills in the epilogue
 #pragma unroll
-      for (int j = 0; j < 4; ++j) wf[0][j] = lds_read16((waddr[0] ^ REG) + j * 4096);
+      for (int j = 0; j < NWF; ++j) wf[0][j] = lds_read16((waddr[0] ^ REG) + j * FRAG);
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii) af[0][ii] = lds_read16((aaddr[0]) + ii * 4096);
+      for (int ii = 0; ii < 2; ++ii) af[0][ii] = lds_read16((aaddr[0]) + ii * FRAG);
     }
     stamp(1);                                          // accumulators cleared: the next tile's main loop starts
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail's surplus requests must have landed before the LDS is released
 }
 
-template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false>
+template <typename T, int EPI, int ABL, bool DIRECT, bool RAGGED = false, int MS = 0>
 static void launch_t256w_abl(const LaGemmPlan& p, const GemmArgs& g, int stg) {
-  launch<T, gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED>>(dim3(p.grid), p, g, p.gm & 0x5ff, stg);
+  launch<T, gemm_t256w_kernel<T, EPI, ABL, DIRECT, RAGGED, MS>>(dim3(p.grid), p, g, p.gm & 0x5ff, stg);
+}
+
+// the direct instances by LaGemmPlan.mfma (gemm_plan.h: w4_mfma_shape says where the 16x16x32 main loop exists and is the faster one;
+// the instances it never picks - EPI 12, ragged EPI 9: hipcc spills there - are not compiled)
+template <typename T, int EPI>
+static void launch_t256w_direct(const LaGemmPlan& p, const GemmArgs& g, int stg) {
+  if constexpr (EPI != 12) {
+    if (p.mfma == 1 && !p.ragged) return launch_t256w_abl<T, EPI, 0, true, false, 1>(p, g, stg);
+    if constexpr (EPI != 9)
+      if (p.mfma == 1) return launch_t256w_abl<T, EPI, 0, true, true, 1>(p, g, stg);
+  }
+  if (!p.ragged) launch_t256w_abl<T, EPI, 0, true>(p, g, stg);
+  else launch_t256w_abl<T, EPI, 0, true, true>(p, g, stg);
 }
 
 template <typename T, int EPI>
@@ -865,16 +965,14 @@ void launch_t256w(const LaGemmPlan& p, const GemmArgs& g, int stg) {
   // la_gemm_variant bits 12-15 = ABL (EPI 1 only)
   if (EPI == 1 && with_int<1, 2, 3, 4, 5, 7, 8, 14>((p.gm >> 12) & 15, [&](auto abl) { launch_t256w_abl<T, 1, LA_V(abl), false>(p, g, stg); })) return;
 #endif
-  if (p.direct && !p.ragged) launch_t256w_abl<T, EPI, 0, true>(p, g, stg);
-  else if (p.direct) launch_t256w_abl<T, EPI, 0, true, true>(p, g, stg);
+  if (p.direct) launch_t256w_direct<T, EPI>(p, g, stg);
   else launch_t256w_abl<T, EPI, 0, false>(p, g, stg);
 }
 
 // EPI 5 / 6 (GELU forward that also keeps the pre-activation; data gradient times gelu' - training only) exist on the direct epilogue alone
 template <typename T, int EPI>
 void launch_t256w_fused(const LaGemmPlan& p, const GemmArgs& g, int stg) {
-  if (!p.ragged) launch_t256w_abl<T, EPI, 0, true>(p, g, stg);
-  else launch_t256w_abl<T, EPI, 0, true, true>(p, g, stg);
+  launch_t256w_direct<T, EPI>(p, g, stg);
 }
 #define LA_W4_FUSED(T, EPI) template void launch_t256w_fused<T, EPI>(const LaGemmPlan&, const GemmArgs&, int);
 LA_W4_FUSED(f16_t, 5) LA_W4_FUSED(f16_t, 6) LA_W4_FUSED(bf16_t, 5) LA_W4_FUSED(bf16_t, 6)
@@ -893,8 +991,13 @@ extern "C" int la_dbg_w4_stamps(unsigned long long* host_out) {
   (void)hipDeviceSynchronize();
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(la::g_w4_stamps), sizeof(unsigned long long) * 4 * la::LA_W4_NSTAMP);
 }
+extern "C" int la_dbg_w4_rstamps(unsigned long long* host_out) {
+  (void)hipDeviceSynchronize();
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(la::g_w4_rstamps), sizeof(unsigned long long) * 4 * la::LA_W4_NSTAMP);
+}
 extern "C" int la_dbg_w4_stamps_clear() {
   static unsigned long long z[4 * la::LA_W4_NSTAMP] = {0};
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(la::g_w4_stamps), z, sizeof(z));
+  const int rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(la::g_w4_stamps), z, sizeof(z));
+  return rc ? rc : (int)hipMemcpyToSymbol(HIP_SYMBOL(la::g_w4_rstamps), z, sizeof(z));
 }
 #endif

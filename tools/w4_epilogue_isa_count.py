@@ -5,7 +5,8 @@
     python tools/w4_epilogue_isa_count.py w4.s
 
 Counted from the seam's ``s_nop 15`` to the first MFMA behind it (the accumulator clear of the next tile).  A compile, not a run.
-Instance tags are the mangled template arguments: DF16_ = fp16, Li<EPI>E, Li0E = no ablation, Lb<DIRECT>E, Lb<RAGGED>E."""
+Instance tags are the mangled template arguments: DF16_ = fp16, Li<EPI>E, Li0E = no ablation, Lb<DIRECT>E, Lb<RAGGED>E, Li<MS>E (1 = the
+16x16x32 main loop).  The last column group also shows scratch instructions: every instance but the mapped EPI 3 one has none."""
 import collections, re, sys
 
 txt = open(sys.argv[1]).read()
