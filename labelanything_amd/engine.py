@@ -14,6 +14,7 @@ from __future__ import annotations
 
 
 import math
+from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -84,6 +85,59 @@ PRECISE_DEFAULT = "auto"
 PRECISE_GROUPS = ("patch", "qkv", "v", "proj", "lin1", "lin2", "neck", "vmean", "projmean")
 
 
+@dataclass(frozen=True)
+class BlockNames:
+    """Where one kind of encoder keeps the tensors of a transformer block: ``prefix.format(i)`` + "." + a name below + ".weight" / ".bias"."""
+    prefix: str
+    norm1: str
+    qkv: Tuple[str, ...]          # one fused q | k | v tensor, or q, k, v
+    proj: str
+    norm2: str
+    lin1: str
+    lin2: str
+    eps: float                    # of every LayerNorm of the stack
+
+
+SAM_BLOCK = BlockNames("image_encoder.blocks.{}", "norm1", ("attn.qkv",), "attn.proj", "norm2", "mlp.lin1", "mlp.lin2", 1e-6)
+HF_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "layernorm_before",
+                      ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.dense",
+                      "layernorm_after", "intermediate.dense", "output.dense", 1e-12)
+
+
+@dataclass(frozen=True)
+class AttnGeo:
+    """Geometry and form of one encoder block's attention, as LamEngine._attn_geo chose them."""
+    pfx: str                      # arena buffers: pfx + ".qkv" + sfx, ".vt", ".ao"
+    sfx: str
+    bn: int                       # images
+    rpg: int                      # tokens per image
+    heads: int
+    hdp: int
+    scale: float
+    g: int                        # side of the image's rel-pos grid; 0: plain attention
+    ws: int                       # window side; 0: global
+    nb: int                       # attention batches (images, or windows of all images)
+    t: int                        # tokens per batch
+    gg: int                       # grid side of a batch
+    tpad: int                     # key slots per batch
+    win16: bool
+    form: str                     # "rows" (la_attn_fwd_rows) | "vt" (V^T epilogue) | "scatter" (V^T epilogue, window-order scatter) | "fp8"
+    arows: int                    # rows of qkv and of the attention output
+    o_chunks: int                 # 128-query blocks per image: column-sum partials of the attention output
+
+    @property
+    def ea(self) -> int:          # width of the q / k / v / attention-output blocks (== the stream's unless the heads are padded)
+        return self.heads * self.hdp
+
+    @property
+    def nwy(self) -> int:
+        return (self.g + self.ws - 1) // self.ws
+
+    @property
+    def parted(self) -> bool:     # qkv and the attention output are in window order
+        return self.ws > 0 and self.form != "rows"
+
+
 _BICUBIC: Dict[tuple, Tensor] = {}
 
 
@@ -117,13 +171,13 @@ def resolve_precise(cfg: LamConfig, precise, dtype: torch.dtype = torch.float16)
 class LamEngine:
     def __init__(self, cfg: LamConfig, weights: Dict[str, Tensor], device: torch.device, dtype: torch.dtype = torch.float16,
                  decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT, fuse_twoway: bool = True,
-                 window_scatter: bool = True, scope: str = "all"):
+                 scope: str = "all"):
         """dtype: MFMA operand type of the image encoder and necks (>99% of the FLOPs).  decoder_dtype: operand type of the
         prompt encoder / mask decoder GEMMs - fp32 by default (exact-fp32 MFMA; ~1% of the FLOPs but the stage where
         16-bit operand rounding would dominate the logit error), or None to follow ``dtype``.  precise: encoder GEMM groups
         that run in split precision (see PRECISE_DEFAULT); () = every encoder GEMM with plain 16-bit operands.
-        fuse_twoway / window_scatter: explicit constructor switches for A/B measurements (tools/) of the fused two-way kernels and of
-        the window-order scatter epilogue; the product never reads the environment.  scope="encoder": only the image encoder's weights
+        fuse_twoway: explicit constructor switch for A/B measurements (tools/) of the fused two-way kernels; the product never reads the
+        environment.  scope="encoder": only the image encoder's weights
         are packed (the trainer-private engine of train_encoder.HfEncoderGraph, re-packed after every optimizer step by
         ``repack_encoder``)."""
         if scope not in ("all", "encoder"):
@@ -154,7 +208,6 @@ class LamEngine:
         # the image side of the two-way transformers runs in the fused kernels (one read / one read + write of the stream per
         # attention, csrc/twoway.hip) for the published decoder geometry; fuse_twoway=False keeps the GEMM + attention + norm chain
         self.fuse_twoway = bool(fuse_twoway) and cfg.embed_dim in (256, 512) and cfg.dec_heads == 8 and decoder_dtype == torch.float32
-        self.window_scatter = bool(window_scatter)
         # attention without V^T copies / window buffers (la_attn_fwd_rows) wherever its forms cover the block: plain attention, the 64 x 64
         # rel-pos grid, 16-slot windows; False keeps the V^T epilogue + window scatter path (A/B, and what the other geometries still use)
         self.attn_rows = True
@@ -172,7 +225,6 @@ class LamEngine:
                           and spec.mlp % 256 == 0 and (3 * spec.heads * 64 * ((spec.head_dim + 63) // 64)) % 256 == 0
                           and not (self.precise & {"qkv", "v", "lin1"}))
         self.norm_fold_packed = self.norm_fold      # (the folded weights exist; Lam.norm_fold = False switches back to the LayerNorm kernels)
-        self._last16 = None
         self.ddt = dtype if decoder_dtype is None else decoder_dtype
         self.ddti = L._DT[self.ddt]
         L.lib()  # fail loudly if the HIP extension is missing
@@ -242,60 +294,69 @@ class LamEngine:
         self.p[key[:-2] + ".cn"] = wf.double().sum(1).float().contiguous()
         self.p[key[:-2] + ".bn"] = (bias.double() + wt.double() @ beta.double()).float().contiguous()
 
-    def _pack_mean(self, pre: str, wv: Tensor, wo: Tensor, gamma: Optional[Tensor] = None) -> None:
-        if gamma is not None and self.norm_fold and self.mean_planes:
-            # the folded form multiplies the token means of the normalised rows BEFORE gamma: the lost plane is that of Wv diag(gamma)
-            cols = []
-            if "vmean" in self.precise:
-                wvg = wv * gamma[None, :]
-                cols.append((wo.double() @ (wvg - wvg.to(self.dt).float()).double()).float())
-            if "projmean" in self.precise:
-                cols.append((wo - wo.to(self.dt).float()).float())
-            self.p[pre + ".mean.w32n"] = torch.cat(cols, dim=1).contiguous()
-        self._pack_mean_plain(pre, wv, wo)
-
-    def _pack_mean_plain(self, pre: str, wv: Tensor, wo: Tensor) -> None:
+    def _pack_mean(self, pre: str, wv: Tensor, wo: Tensor, gamma: Tensor) -> None:
         """fp32 operand of the token-mean corrections of one block: rvec += [mean(x) | mean(o)] . [Wo Wv_lo | Wo_lo]^T, where *_lo is what
         the 16-bit plane of a weight lost (c_v = mean(x) Wv_lo^T belongs on every V row of the image, softmax rows sum to one, so it
         leaves attention unchanged and goes through proj as c_v Wo^T: one [E, E] product formed here, once)."""
-        cols = []
-        if "vmean" in self.precise:
-            v_lo = (wv - wv.to(self.dt).float()).double()                                       # [ea, E]
-            cols.append((wo.double() @ v_lo).float())                                            # [E, E]
-        if "projmean" in self.precise:
-            cols.append((wo - wo.to(self.dt).float()).float())                                   # [E, ea]
-        if cols:
-            self.p[pre + ".mean.w32"] = torch.cat(cols, dim=1).contiguous()
-            self.mean_kx[pre] = cols[0].shape[1] if "vmean" in self.precise else 0
+        def cols(wv):
+            c = []
+            if "vmean" in self.precise:
+                c.append((wo.double() @ (wv - wv.to(self.dt).float()).double()).float())      # [E, ea] . [ea, E]
+            if "projmean" in self.precise:
+                c.append((wo - wo.to(self.dt).float()).float())                                # [E, ea]
+            return c
+
+        if self.norm_fold and self.mean_planes:
+            # the folded form multiplies the token means of the normalised rows BEFORE gamma: the lost plane is that of Wv diag(gamma)
+            self.p[pre + ".mean.w32n"] = torch.cat(cols(wv * gamma[None, :]), dim=1).contiguous()
+        if self.mean_planes:
+            c = cols(wv)
+            self.p[pre + ".mean.w32"] = torch.cat(c, dim=1).contiguous()
+            self.mean_kx[pre] = c[0].shape[1] if "vmean" in self.precise else 0
 
     @property
     def mean_planes(self) -> bool:
         return "vmean" in self.precise or "projmean" in self.precise
 
-    def mean_parts(self, bn: int, rpg: int, e: int, ea: int, o_chunks: int):
+    def mean_parts(self, at: AttnGeo, e: int):
         """Scratch of one block's fused column sums: (LayerNorm partials or None, attention partials or None) - see mean_fix."""
-        xp = self.f32("mean.xpart", (bn * L.ln_cs_chunks(rpg) * e,)) if "vmean" in self.precise else None
-        op = self.f32("mean.opart", (bn * max(o_chunks, _ceil(rpg, 128) // 128) * ea,)) if "projmean" in self.precise else None
+        xp = self.f32("mean.xpart", (at.bn * L.ln_cs_chunks(at.rpg) * e,)) if "vmean" in self.precise else None
+        op = self.f32("mean.opart", (at.bn * max(at.o_chunks, _ceil(at.rpg, 128) // 128) * at.ea,)) if "projmean" in self.precise else None
         return xp, op
 
-    def mean_fix(self, pre: str, xpart, opart, rvec: Tensor, bn: int, rpg: int, o_chunks: int, e: int, ea: int, ao=None, ao_win=(0, 0)) -> None:
-        """rvec[img] += mean(x) (Wo Wv_lo)^T + mean(o) Wo_lo^T for one attention block (see PRECISE_WIDE).  xpart: column sums of the
-        16-bit qkv operand per 128-row chunk, left by the LayerNorm that wrote it (la_layernorm_g); opart: column sums of the attention
-        output per 128-query block (o_chunks per image), left by la_attn_fwd_cs - or, o_chunks == 0, scratch for a separate pass over
-        ao (la_colmean16; ao_win = (ws, g) when ao is window-partitioned).  Chunks are folded in a fixed order: an image's vectors do
-        not depend on the rest of the batch."""
-        wm = self.p[pre + ".mean.w32"]
+    def _mean_bar(self, pre: str, wm: Tensor, at: AttnGeo, e: int, xpart, x_chunks: int, opart, o_chunks: int, ao: Tensor) -> Tensor:
+        """[mean(x) | mean(o)] per image, the left operand of a block's token-mean correction against wm.  xpart: column sums of the 16-bit
+        qkv operand in x_chunks chunks per image, left by the kernel that wrote it; opart: column sums of the attention output per 128-query
+        block (o_chunks per image), left by the attention kernel - or, o_chunks == 0, scratch for a separate pass over ao (la_colmean16,
+        which undoes the window order of ao).  Chunks are folded in a fixed order: an image's vectors do not depend on the rest of the batch."""
+        bn, rpg, kx = at.bn, at.rpg, self.mean_kx[pre]
         bar = self.f32("mean.bar", (bn, wm.shape[1]))
-        kx = self.mean_kx[pre]
         if xpart is not None:
-            L.colsum_fold(xpart, bn, L.ln_cs_chunks(rpg), e, 1.0 / rpg, bar[:, :kx])
+            L.colsum_fold(xpart, bn, x_chunks, e, 1.0 / rpg, bar[:, :kx])
         if opart is not None and o_chunks > 0:
-            L.colsum_fold(opart, bn, o_chunks, ea, 1.0 / rpg, bar[:, kx:])
+            L.colsum_fold(opart, bn, o_chunks, at.ea, 1.0 / rpg, bar[:, kx:])
         elif opart is not None:
-            obar = self.f32("mean.obar", (bn, ea))
-            L.colmean16(ao, bn, rpg, obar, opart, ao_win[0], ao_win[1], ao_win[1])
+            obar = self.f32("mean.obar", (bn, at.ea))
+            ws, g = (at.ws, at.g) if at.parted else (0, 0)
+            L.colmean16(ao, bn, rpg, obar, opart, ws, g, g)
             bar[:, kx:].copy_(obar)
-        L.gemm(bar, wm, res=rvec, out32=rvec)
+        return bar
+
+    def mean_fix(self, pre: str, at: AttnGeo, e: int, xpart, opart, o_chunks: int, ao: Tensor, rvec: Tensor) -> None:
+        """rvec[img] += mean(x) (Wo Wv_lo)^T + mean(o) Wo_lo^T for one attention block (see PRECISE_WIDE); xpart from the LayerNorm that
+        wrote the qkv operand (la_layernorm_g), the rest as in _mean_bar."""
+        wm = self.p[pre + ".mean.w32"]
+        L.gemm(self._mean_bar(pre, wm, at, e, xpart, L.ln_cs_chunks(at.rpg), opart, o_chunks, ao), wm, res=rvec, out32=rvec)
+
+    def _fold_mean(self, pre: str, at: AttnGeo, e: int, xpart, opart, o_chunks: int, ao: Tensor) -> Optional[Tensor]:
+        """The block's token-mean correction as a FRESH per-image vector (the proj GEMM's epilogue adds it to the stream: nothing stays
+        pending): dR[img] = [mean(z) | mean(o)] . [Wo (Wv gamma)_lo | Wo_lo]^T, z = the normalised rows before gamma (la_norm_finalize)."""
+        if not self.mean_planes:
+            return None
+        wm = self.p[pre + ".mean.w32n"]
+        dr = self.f32("mean.dr", (at.bn, e))
+        L.gemm(self._mean_bar(pre, wm, at, e, xpart, L.norm_cs_chunks(at.rpg), opart, o_chunks, ao), wm, out32=dr)
+        return dr
 
     def _hw_qkv(self, key: str, t: Tensor, bias: Tensor, ea: int) -> None:
         """Pack a fused qkv weight [3 ea, K] + bias.  Group "qkv": planes for all rows; group "v": a one-plane [2 ea, K] q/k weight and
@@ -316,19 +377,14 @@ class LamEngine:
         rows of the weight carry a second plane.  rowmap = (map, p): output row map of both (image-order tokens -> window order)."""
         b = self.p[key[:-2] + ".b"]
         mkw = {} if rowmap is None else {"map": rowmap[0], "p": rowmap[1]}
-        if vt is None:          # no V^T copy (la_attn_fwd_rows reads the v columns): every column through the plain row-major epilogue
-            if (key + ".qk") in self.p:
-                L.gemm(x, self.p[key + ".qk"], bias=b[: 2 * ea], out16=qkv[:, : 2 * ea], **mkw)
-                L.gemm(x, self.p[key + ".v"], bias=b[2 * ea:], out16=qkv[:, 2 * ea:], a_kmod=self.kmod.get(key + ".v", 0), **mkw)
-            else:
-                self.gemm_w(x, key, bias=b, out16=qkv, **mkw)
-            return
+        # vt None: no V^T copy (la_attn_fwd_rows reads the v columns), every column through the plain row-major epilogue
         if (key + ".qk") in self.p:
+            vkw = {} if vt is None else dict(vt=vt, vt_col0=0, **vtkw)
             L.gemm(x, self.p[key + ".qk"], bias=b[: 2 * ea], out16=qkv[:, : 2 * ea], **mkw)
-            L.gemm(x, self.p[key + ".v"], bias=b[2 * ea:], out16=qkv[:, 2 * ea:], vt=vt, vt_col0=0, a_kmod=self.kmod.get(key + ".v", 0),
-                   **vtkw, **mkw)
+            L.gemm(x, self.p[key + ".v"], bias=b[2 * ea:], out16=qkv[:, 2 * ea:], a_kmod=self.kmod.get(key + ".v", 0), **vkw, **mkw)
         else:
-            self.gemm_w(x, key, bias=b, out16=qkv, vt=vt, vt_col0=2 * ea, **vtkw, **mkw)
+            vkw = {} if vt is None else dict(vt=vt, vt_col0=2 * ea, **vtkw)
+            self.gemm_w(x, key, bias=b, out16=qkv, **vkw, **mkw)
 
     def _patch_weight(self, pw: Tensor) -> Tensor:
         """Patch-embed weight [dim, 3 p p]: plain 16-bit; or, in the split-precision group "patch", fp16 plane triples
@@ -432,6 +488,26 @@ class LamEngine:
         if "neck" in self.precise and self.dt == torch.float16 and w0.shape[1] % 64 == 0 and w0.shape[0] % 32 == 0:
             self.p[pre + ".0.ws"] = self._split3(w0)
 
+    def _pack_block(self, bp: str, nm: BlockNames) -> None:
+        """One encoder block's GEMM weights under the packed keys both kinds share: ``.qkv.w`` / ``.b`` / ``.pad16`` (q | k | v concatenated,
+        heads zero-padded to head_pad), ``.proj.w``, ``.lin1.w``, ``.lin2.w``, the token-mean operands ``.mean.w32`` / ``.mean.w32n`` and, with
+        norm_fold, the gamma-folded ``.qkv.wn`` / ``.bn`` / ``.cn`` and ``.lin1.wn`` / ``.bn`` / ``.cn``."""
+        w, spec = self.w32, self.cfg.encoder_spec
+        hd, hdp = spec.head_dim, self.head_pad
+        ea = spec.heads * hdp
+        qkv_w = self._pad_heads_out(torch.cat([w[f"{bp}.{n}.weight"] for n in nm.qkv]), 3 * spec.heads, hd, hdp)
+        qkv_b = self._pad_heads_out(torch.cat([w[f"{bp}.{n}.bias"] for n in nm.qkv]), 3 * spec.heads, hd, hdp)
+        proj_w = self._pad_heads_in(w[f"{bp}.{nm.proj}.weight"], spec.heads, hd, hdp)
+        self._hw_qkv(bp + ".qkv.w", qkv_w, qkv_b, ea)
+        self._hw(bp + ".proj.w", proj_w, "proj")
+        self._pack_mean(bp, qkv_w[2 * ea:], proj_w, w[f"{bp}.{nm.norm1}.weight"])
+        if self.norm_fold:
+            self._pack_fold(bp + ".qkv.w", qkv_w, qkv_b, w[f"{bp}.{nm.norm1}.weight"], w[f"{bp}.{nm.norm1}.bias"])
+            self._pack_fold(bp + ".lin1.w", w[f"{bp}.{nm.lin1}.weight"], w[f"{bp}.{nm.lin1}.bias"], w[f"{bp}.{nm.norm2}.weight"],
+                            w[f"{bp}.{nm.norm2}.bias"])
+        self._hw(bp + ".lin1.w", w[f"{bp}.{nm.lin1}.weight"], "lin1")
+        self._hw(bp + ".lin2.w", w[f"{bp}.{nm.lin2}.weight"], "lin2")
+
     def _pack(self) -> None:
         cfg, w, p = self.cfg, self.w32, self.p
         spec = cfg.encoder_spec
@@ -443,18 +519,8 @@ class LamEngine:
             g = spec.img_size // spec.patch
             hd, hdp = spec.head_dim, self.head_pad
             for i in range(spec.depth):
-                bp = f"{pre}.blocks.{i}"
-                self._hw_qkv(bp + ".qkv.w", self._pad_heads_out(w[bp + ".attn.qkv.weight"], 3 * spec.heads, hd, hdp),
-                             self._pad_heads_out(w[bp + ".attn.qkv.bias"], 3 * spec.heads, hd, hdp), spec.heads * hdp)
-                self._hw(bp + ".proj.w", self._pad_heads_in(w[bp + ".attn.proj.weight"], spec.heads, hd, hdp), "proj")
-                self._pack_mean(bp, self._pad_heads_out(w[bp + ".attn.qkv.weight"], 3 * spec.heads, hd, hdp)[2 * spec.heads * hdp:],
-                                self._pad_heads_in(w[bp + ".attn.proj.weight"], spec.heads, hd, hdp), gamma=w[bp + ".norm1.weight"])
-                if self.norm_fold:
-                    self._pack_fold(bp + ".qkv.w", self._pad_heads_out(w[bp + ".attn.qkv.weight"], 3 * spec.heads, hd, hdp),
-                                    self._pad_heads_out(w[bp + ".attn.qkv.bias"], 3 * spec.heads, hd, hdp), w[bp + ".norm1.weight"], w[bp + ".norm1.bias"])
-                    self._pack_fold(bp + ".lin1.w", w[bp + ".mlp.lin1.weight"], w[bp + ".mlp.lin1.bias"], w[bp + ".norm2.weight"], w[bp + ".norm2.bias"])
-                self._hw(bp + ".lin1.w", w[bp + ".mlp.lin1.weight"], "lin1")
-                self._hw(bp + ".lin2.w", w[bp + ".mlp.lin2.weight"], "lin2")
+                bp = SAM_BLOCK.prefix.format(i)
+                self._pack_block(bp, SAM_BLOCK)
                 size = g if i in spec.global_idx else spec.window
                 for ax in ("h", "w"):
                     tab = w[f"{bp}.attn.rel_pos_{ax}"]
@@ -466,25 +532,8 @@ class LamEngine:
             pre = "image_encoder"
             pw = w[pre + ".embeddings.patch_embeddings.projection.weight"].flatten(1)
             p[pre + ".patch.w"] = self._patch_weight(pw)
-            hd, hdp = spec.head_dim, self.head_pad
             for i in range(spec.depth):
-                lp = f"{pre}.encoder.layer.{i}"
-                qkv_w = torch.cat([w[lp + ".attention.attention.query.weight"], w[lp + ".attention.attention.key.weight"],
-                                   w[lp + ".attention.attention.value.weight"]])
-                qkv_b = torch.cat([w[lp + ".attention.attention.query.bias"], w[lp + ".attention.attention.key.bias"],
-                                   w[lp + ".attention.attention.value.bias"]])
-                self._hw_qkv(lp + ".qkv.w", self._pad_heads_out(qkv_w, 3 * spec.heads, hd, hdp),
-                             self._pad_heads_out(qkv_b, 3 * spec.heads, hd, hdp), spec.heads * hdp)
-                self._hw(lp + ".o.w", self._pad_heads_in(w[lp + ".attention.output.dense.weight"], spec.heads, hd, hdp), "proj")
-                self._pack_mean(lp, self._pad_heads_out(w[lp + ".attention.attention.value.weight"], spec.heads, hd, hdp),
-                                self._pad_heads_in(w[lp + ".attention.output.dense.weight"], spec.heads, hd, hdp), gamma=w[lp + ".layernorm_before.weight"])
-                if self.norm_fold:
-                    self._pack_fold(lp + ".qkv.w", self._pad_heads_out(qkv_w, 3 * spec.heads, hd, hdp), self._pad_heads_out(qkv_b, 3 * spec.heads, hd, hdp),
-                                    w[lp + ".layernorm_before.weight"], w[lp + ".layernorm_before.bias"])
-                    self._pack_fold(lp + ".fc1.w", w[lp + ".intermediate.dense.weight"], w[lp + ".intermediate.dense.bias"],
-                                    w[lp + ".layernorm_after.weight"], w[lp + ".layernorm_after.bias"])
-                self._hw(lp + ".fc1.w", w[lp + ".intermediate.dense.weight"], "lin1")
-                self._hw(lp + ".fc2.w", w[lp + ".output.dense.weight"], "lin2")
+                self._pack_block(HF_BLOCK.prefix.format(i), HF_BLOCK)
         if self.scope == "encoder":
             return
         if cfg.lam_neck:
@@ -645,7 +694,7 @@ class LamEngine:
         return out
 
     # ------------------------------------------------------------------------------------------------
-    # SAM ViTDet encoder (image_encoder.py:110-131,179-197,200-255)
+    # image encoders: one transformer block stack (plain or folded) behind a SAM ViTDet and a HuggingFace ViT entry / exit
     # ------------------------------------------------------------------------------------------------
     def _check_encoder_input(self, images: Tensor) -> None:
         spec: EncoderSpec = self.cfg.encoder_spec
@@ -654,184 +703,128 @@ class LamEngine:
             raise ValueError(f"image side {images.shape[-1]} / vit_patch_size {self.cfg.vit_patch_size} do not match the "
                              f"encoder's {spec.patch}x{spec.patch} patches")
 
-    def sam_encoder(self, images: Tensor, want_last_block: bool = False):
+    def _attn_geo(self, pfx: str, bn: int, rpg: int, g: int = 0, ws: int = 0) -> AttnGeo:
+        """Geometry and form of the attention of one block over bn images of rpg tokens.  g: side of the image's rel-pos grid (SAM), 0 =
+        plain attention (HF, CLS row included); ws: window side, 0 = a global block."""
         spec: EncoderSpec = self.cfg.encoder_spec
-        self._check_encoder_input(images)
-        pre = "image_encoder"
-        bn, _, s, _ = images.shape
-        if s != spec.img_size:
-            raise ValueError(f"SAM encoder expects {spec.img_size}x{spec.img_size} inputs, got {s}")
-        e, heads, g, ws = spec.dim, spec.heads, s // spec.patch, spec.window
-        hw = g * g
-        rows = bn * hw
-        scale = spec.head_dim ** -0.5
         hdp = self.head_pad
-        ea = heads * hdp                # width of the q / k / v / attention-output blocks (== e unless the heads are padded)
-        w, p = self.w32, self.p
-        images = images.contiguous()
-        # (the producer epilogue adds the per-image correction to groups of whole row tiles or of >= 128 rows: smaller grids keep the kernels)
-        if self.norm_fold and self.attn_rows and ws <= 16 and (g == 64 or not spec.global_idx) and (hw % 256 == 0 or hw >= 128):
-            return self._sam_encoder_fold(images, want_last_block)
-        a, akw = self.patches("enc.patchA", images, rows, spec.patch)
-        res = self.f32("enc.res", (rows, e))
-        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".patch_embed.proj.bias"], res=p[pre + ".pos"], res_mod=hw, out32=res, **akw)
-        nwy = (g + ws - 1) // ws
-        x16 = self.buf("enc.x16", (rows, e))
-        last16 = None
-        rvec = None
-        if self.mean_planes:           # pending per-image corrections of the single-plane V / proj weights (PRECISE_WIDE)
-            rvec = self.f32("enc.rvec", (bn, e), zero=True)
-            rvec.zero_()
-        rkw = dict(rvec=rvec, rpg=hw) if rvec is not None else {}
-        for i in range(spec.depth):
-            bp = f"{pre}.blocks.{i}"
-            is_global = i in spec.global_idx
-            xpart = opart = None
-            if rvec is not None:
-                o_chunks = _ceil(hw, 128) // 128 if is_global else nwy * nwy * (_ceil(ws * ws, 128) // 128)
-                xpart, opart = self.mean_parts(bn, hw, e, ea, o_chunks)
-            ckw = dict(colsum_part=xpart) if xpart is not None else {}
-            if is_global:
-                nb, t, gg, arows = bn, hw, g, rows
-                xin = x16
-                self.ln(res, bp + ".norm1", 1e-6, out16=xin, **rkw, **ckw)
-            else:
-                nb, t, gg = bn * nwy * nwy, ws * ws, ws
-                arows = nb * t
-            win16 = (not is_global) and gg <= 16      # windows: V^T / K in 16-wide padded slot order (LA_ATTN_RELPOS_WIN16)
-            tpad = _ceil(16 * gg, 64) if win16 else _ceil(t, 64)
-            tag = "g" if is_global else "w"
-            # No V^T copy, no window buffers (la_attn_fwd_rows): the q | k | v GEMM of EVERY block walks the image-order tokens with its plain
-            # row-major epilogue; attention stages V tiles row-major (LDS transpose reads) and, for 14 x 14 windows, addresses the image's
-            # tokens directly (tokens beyond the image are the bias row); its output is in image order, so proj is a plain GEMM as well.
-            # Measured (profiles/r05_notes.md 2): the V^T scatter cost 110 / 275 us of a 1.53 / 1.65 ms launch, the kernels are equal or faster.
-            rows_path = self.attn_rows and ((is_global and gg == 64) or win16)
-            if rows_path:
-                xin = x16
-                if not is_global:
-                    self.ln(res, bp + ".norm1", 1e-6, out16=xin, **rkw, **ckw)
-                qkv = self.buf("enc.qkv.r", (rows, 3 * ea))
-                self.qkv_gemm(xin, bp + ".qkv.w", qkv, None, ea)
-                ao = self.buf("enc.ao.r", (rows, ea))
-                fused_o = opart is not None and (is_global or self.win_fused_cs)
-                if is_global:
-                    L.attn_fwd_rows(qkv, ao, nb, heads, t, tpad, gg, ea, scale, L.ATTN_RELPOS, tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"],
-                                    cspart=opart if fused_o else None)
-                else:
-                    L.attn_fwd_rows(qkv, ao, nb, heads, t, tpad, gg, ea, scale, L.ATTN_RELPOS_WIN16, tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"],
-                                    img_hw=(g, g), padrow=p[bp + ".qkv.pad16"], cspart=opart if fused_o else None)
-                if rvec is not None:
-                    self.mean_fix(bp, xpart, opart, rvec, bn, hw, o_chunks if fused_o else 0, e, ea, ao=ao)
-                self.gemm_w(ao, bp + ".proj.w", bias=w[bp + ".attn.proj.bias"], res=res, out32=res)
-                self._sam_mlp(bp, i, res, x16, rows, spec, w, rvec, rkw)
-                last16 = self._last16 if self._last16 is not None else last16
-                continue
-            # Window blocks whose qkv weight is one plane (at most the V rows carry a second one): the GEMMs walk the REAL tokens in
-            # image order and their epilogue scatters q / k rows and V^T slots into window order (LA_MAP_WINDOW_PART) - the padded
-            # tokens (16 % of the rows at 64 x 64 / 14) are never multiplied.  Their q / k / v are the bias (pad-after-norm), constant
-            # per block: every window block owns its buffers, filled once when they are created.
-            scatter = win16 and "qkv" not in self.precise and arows > rows and self.window_scatter
-            if is_global:
-                pass
-            elif scatter:
-                xin = x16
-                self.ln(res, bp + ".norm1", 1e-6, out16=xin, **rkw, **ckw)
-            else:
-                xin = self.buf("enc.xwin", (arows, e), zero=True)        # padded tokens stay zero
-                self.ln(res, bp + ".norm1", 1e-6, out16=xin, window=ws, H=g, W=g, **rkw, **ckw)
-            if scatter:
-                qb = p[bp + ".qkv.b"]
+        if ws:
+            nwy = (g + ws - 1) // ws
+            nb, t, gg = bn * nwy * nwy, ws * ws, ws
+        else:
+            nb, t, gg = bn, rpg, g
+        win16 = ws > 0 and gg <= 16      # windows: V^T / K in 16-wide padded slot order (LA_ATTN_RELPOS_WIN16)
+        fp8 = not g and self.attn_fp8 and hdp == 64          # (the fp8 QK^T kernel keeps its V^T operand)
+        # No V^T copy, no window buffers (la_attn_fwd_rows): the q | k | v GEMM of EVERY block walks the image-order tokens with its plain
+        # row-major epilogue; attention stages V tiles row-major (LDS transpose reads) and, for 14 x 14 windows, addresses the image's
+        # tokens directly (tokens beyond the image are the bias row); its output is in image order, so proj is a plain GEMM as well.
+        # Measured (profiles/r05_notes.md 2): the V^T scatter cost 110 / 275 us of a 1.53 / 1.65 ms launch, the kernels are equal or faster.
+        rows_path = self.attn_rows and not fp8 and (not g or (not ws and gg == 64) or win16)
+        # Window blocks whose qkv weight is one plane (at most the V rows carry a second one): the GEMMs walk the REAL tokens in
+        # image order and their epilogue scatters q / k rows and V^T slots into window order (LA_MAP_WINDOW_PART) - the padded
+        # tokens (16 % of the rows at 64 x 64 / 14) are never multiplied.  Their q / k / v are the bias (pad-after-norm), constant
+        # per block: every window block owns its buffers, filled once when they are created.
+        scatter = win16 and "qkv" not in self.precise and nb * t > bn * rpg
+        form = "rows" if rows_path else "fp8" if fp8 else "scatter" if scatter else "vt"
+        sfx = "" if not g else ".r" if rows_path else ".w" if ws else ".g"       # (SAM: the forms and block kinds differ in buffer shapes)
+        return AttnGeo(pfx=pfx, sfx=sfx, bn=bn, rpg=rpg, heads=spec.heads, hdp=hdp, scale=spec.head_dim ** -0.5, g=g, ws=ws, nb=nb, t=t,
+                       gg=gg, tpad=_ceil(16 * gg, 64) if win16 else _ceil(t, 64), win16=win16, form=form,
+                       arows=bn * rpg if rows_path else nb * t, o_chunks=nb // bn * (_ceil(t, 128) // 128))
 
-                def fill_qk(tq, qb=qb):
-                    tq[:, : 2 * ea] = qb[: 2 * ea].to(tq.dtype)
-
-                def fill_v(tv, qb=qb):
-                    tv.zero_()
-                    tv.view(nb, heads, hdp, tpad)[..., : 16 * gg].view(nb, heads, hdp, gg, 16)[..., :gg] = \
-                        qb[2 * ea:].view(1, heads, hdp, 1, 1).to(tv.dtype)
-
-                qkv = self.arena.get(f"enc.qkv.w{i}", (arows, 3 * ea), self.dt, False, fill_qk)
-                vt = self.arena.get(f"enc.vt.w{i}", (nb * heads, hdp, tpad), self.dt, False, fill_v)
-                self.qkv_gemm(xin, bp + ".qkv.w", qkv, vt, ea, rowmap=(L.MAP_WINDOW_PART, (ws, nwy, nwy, g, g)), vt_T=t, vt_Tpad=tpad,
-                              vt_hd=hdp, vt_heads=heads, vt_ws=gg)
+    def _qkv(self, bp: str, i: int, at: AttnGeo, x: Tensor, mr: Optional[Tensor] = None):
+        """The q | k | v GEMM of block i in the layout its attention reads; returns (qkv, V^T or None).  mr: the (mean, rstd) rows of a
+        folded LayerNorm - the gamma-folded weight, normalised in the epilogue (rows form only)."""
+        p, ea, heads, hdp = self.p, at.ea, at.heads, at.hdp
+        if at.form == "rows":
+            qkv = self.buf(f"{at.pfx}.qkv{at.sfx}", (at.arows, 3 * ea))
+            if mr is not None:
+                L.gemm(x, p[bp + ".qkv.wn"], bias=p[bp + ".qkv.bn"], out16=qkv, nstat_in=mr, ncol=p[bp + ".qkv.cn"])
             else:
-                qkv = self.buf("enc.qkv." + tag, (arows, 3 * ea))
-                vt = self.buf("enc.vt." + tag, (nb * heads, hdp, tpad), zero=True)
-                self.qkv_gemm(xin, bp + ".qkv.w", qkv, vt, ea, vt_T=t, vt_Tpad=tpad, vt_hd=hdp, vt_heads=heads, vt_ws=gg if win16 else 0)
-            ao = self.buf("enc.ao." + tag, (arows, ea))
+                self.qkv_gemm(x, bp + ".qkv.w", qkv, None, ea)
+            return qkv, None
+        vtkw = dict(vt_T=at.t, vt_Tpad=at.tpad, vt_hd=hdp, vt_heads=heads, vt_ws=at.gg if at.win16 else 0)
+        if at.form == "scatter":
+            qb, nwy = p[bp + ".qkv.b"], at.nwy
+
+            def fill_qk(tq):
+                tq[:, : 2 * ea] = qb[: 2 * ea].to(tq.dtype)
+
+            def fill_v(tv):
+                tv.zero_()
+                tv.view(at.nb, heads, hdp, at.tpad)[..., : 16 * at.gg].view(at.nb, heads, hdp, at.gg, 16)[..., :at.gg] = \
+                    qb[2 * ea:].view(1, heads, hdp, 1, 1).to(tv.dtype)
+
+            qkv = self.arena.get(f"enc.qkv.w{i}", (at.arows, 3 * ea), self.dt, False, fill_qk)
+            vt = self.arena.get(f"enc.vt.w{i}", (at.nb * heads, hdp, at.tpad), self.dt, False, fill_v)
+            self.qkv_gemm(x, bp + ".qkv.w", qkv, vt, ea, rowmap=(L.MAP_WINDOW_PART, (at.ws, nwy, nwy, at.g, at.g)), **vtkw)
+        else:
+            qkv = self.buf(f"{at.pfx}.qkv{at.sfx}", (at.arows, 3 * ea))
+            vt = self.buf(f"{at.pfx}.vt{at.sfx}", (at.nb * heads, hdp, at.tpad), zero=True)
+            self.qkv_gemm(x, bp + ".qkv.w", qkv, vt, ea, **vtkw)
+        return qkv, vt
+
+    def _attention(self, bp: str, at: AttnGeo, qkv: Tensor, vt: Optional[Tensor], opart: Optional[Tensor]):
+        """softmax(q k^T [+ rel-pos]) v of one block in the form ``_attn_geo`` chose.  Returns (output, chunks): the output in image order
+        (rows form) or in the order of qkv, and the column-sum partials per image the attention kernel left in opart (0: none)."""
+        p, nb, heads, t, tpad, gg, ea, scale = self.p, at.nb, at.heads, at.t, at.tpad, at.gg, at.ea, at.scale
+        tabs = dict(tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"]) if at.g else {}
+        mode = L.ATTN_RELPOS_WIN16 if at.win16 else L.ATTN_RELPOS if at.g else L.ATTN_PLAIN
+        ao = self.buf(f"{at.pfx}.ao{at.sfx}", (at.arows, ea))
+        if at.form == "rows":
+            fused_o = opart is not None and (not at.ws or self.win_fused_cs)
+            wkw = dict(img_hw=(at.g, at.g), padrow=p[bp + ".qkv.pad16"]) if at.ws else {}
+            L.attn_fwd_rows(qkv, ao, nb, heads, t, tpad, gg, ea, scale, mode, cspart=opart if fused_o else None, **tabs, **wkw)
+        elif at.form == "fp8":
+            fused_o = False
+            qk8 = self.arena.get("hf.qk8", (at.arows, 2 * ea), torch.uint8, False)
+            L.qk_fp8(qkv, ea, qk8)
+            L.attn_fwd_fp8(qk8, vt, ao, nb, heads, t, tpad, ea, scale)
+        else:
             # column sums of the attention output from the attention kernel itself where that is cheaper than a pass over the output:
             # 260 VALU operations per wave at the end of >= 15 key tiles (global blocks: +2 %), not of a window's 4 (+30 %, measured)
-            fused_o = opart is not None and not win16 and gg > 16
-            okw = dict(cspart=opart) if fused_o else None
-
-            def attn(relh, relw, mode, **tk):
-                if okw is not None:
-                    L.attn_fwd_cs(qkv, vt, ao, relh, relw, nb, heads, t, tpad, gg, ea, scale, mode, **okw, **tk)
-                else:
-                    L.attn_fwd(qkv, vt, ao, relh, relw, nb, heads, t, tpad, gg, ea, scale, mode, **tk)
-
-            if win16:
-                attn(None, None, L.ATTN_RELPOS_WIN16, tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"])
-            elif gg <= 16 or gg == 64:      # rel-pos terms are computed inside the attention kernel
-                attn(None, None, L.ATTN_RELPOS, tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"])
-            else:
-                relh = self.f32("enc.relh." + tag, (nb * heads, t, gg))
-                relw = self.f32("enc.relw." + tag, (nb * heads, t, gg))
+            fused_o = opart is not None and (not at.g or (not at.win16 and gg > 16))
+            relh = relw = None
+            if not (at.win16 or gg <= 16 or gg == 64):      # (else the rel-pos terms are computed inside the attention kernel)
+                relh = self.f32(f"enc.relh{at.sfx}", (nb * heads, t, gg))
+                relw = self.f32(f"enc.relw{at.sfx}", (nb * heads, t, gg))
                 L.relpos_terms(qkv, nb, heads, gg, ea, p[bp + ".tabh"], p[bp + ".tabw"], relh, relw)
-                attn(relh, relw, L.ATTN_RELPOS)
-            if rvec is not None:
-                self.mean_fix(bp, xpart, opart, rvec, bn, hw, o_chunks if fused_o else 0, e, ea, ao=ao,
-                              ao_win=(0, 0) if is_global else (ws, g))
-            if is_global:
-                self.gemm_w(ao, bp + ".proj.w", bias=w[bp + ".attn.proj.bias"], res=res, out32=res)
-            else:       # window_unpartition as a row gather on the A operand: again only the real tokens are computed
-                self.gemm_w(ao, bp + ".proj.w", bias=w[bp + ".attn.proj.bias"], res=res, out32=res, M=rows,
-                            amap=L.MAP_WINDOW_PART, p=(ws, nwy, nwy, g, g))
-            self._sam_mlp(bp, i, res, x16, rows, spec, w, rvec, rkw)
-            last16 = self._last16 if self._last16 is not None else last16
-        xs = None
-        split_neck = self.cfg.use_vit_sam_neck and (pre + ".neck.0.ws") in p
-        if split_neck:                 # the stream's last pass also leaves it as fp16 plane pairs: the neck's 1 x 1 conv operand
-            # (range: the pair [hi | lo] holds |x| <= 131008 - la_add_rowvec_split saturates beyond, it never emits inf / NaN; SAM
-            # checkpoints keep the un-normalised stream three orders of magnitude below that)
-            xs = self.buf("enc.res_split", (rows, 2 * e), torch.float16)
-            L.add_rowvec_split(res, rvec, hw, xs)
-        elif rvec is not None:         # the stream leaves the block stack: fold the pending corrections in
-            L.add_rowvec(res, rvec, hw)
-        if rvec is not None and not (self.cfg.use_vit_sam_neck and "neck" in self.precise):
-            last16 = self.buf("enc.last16", (rows, e))
-            L.add_cast(res, out16=last16, dt=self.dti)
-        if not self.cfg.use_vit_sam_neck:
-            return (res, last16, e) if not want_last_block else ((res, last16, e), res)
-        out = self.conv_neck(pre + ".neck", last16, bn, g, "enc.neck", x32=res, xs=xs)
-        if want_last_block:
-            return (out, None, spec.out_chans), res
-        return out, None, spec.out_chans
+                tabs = {}
+            if fused_o:
+                L.attn_fwd_cs(qkv, vt, ao, relh, relw, nb, heads, t, tpad, gg, ea, scale, mode, opart, **tabs)
+            else:
+                L.attn_fwd(qkv, vt, ao, relh, relw, nb, heads, t, tpad, gg, ea, scale, mode, **tabs)
+        return ao, at.o_chunks if fused_o else 0
+
+    def _block_plain(self, i: int, nm: BlockNames, at: AttnGeo, res: Tensor, x16: Tensor, rvec: Optional[Tensor], want16: bool = False):
+        """Block i, a pre-LN transformer block, on the fp32 stream ``res`` with the LayerNorm kernels: norm1, q | k | v, attention, token-mean
+        correction (into the pending rvec), proj, norm2, lin1 (GELU), lin2.  x16: the 16-bit operand buffer of the GEMMs.  want16: lin2 also
+        writes - and the block returns - a 16-bit copy of the stream."""
+        w, bp, rpg = self.w32, nm.prefix.format(i), at.rpg
+        rows, e = res.shape
+        xpart, opart = self.mean_parts(at, e)
+        ckw = dict(colsum_part=xpart) if xpart is not None else {}
+        xin, wkw = x16, {}
+        if at.parted and at.form != "scatter":       # the LayerNorm partitions the rows into windows; padded tokens stay zero
+            xin, wkw = self.buf("enc.xwin", (at.arows, e), zero=True), dict(window=at.ws, H=at.g, W=at.g)
+        self.ln(res, f"{bp}.{nm.norm1}", nm.eps, rvec, rpg, out16=xin, **wkw, **ckw)
+        qkv, vt = self._qkv(bp, i, at, xin)
+        ao, o_chunks = self._attention(bp, at, qkv, vt, opart)
+        if rvec is not None:
+            self.mean_fix(bp, at, e, xpart, opart, o_chunks, ao, rvec)
+        # (window order: window_unpartition as a row gather on the A operand - again only the real tokens are computed)
+        ukw = dict(M=rows, amap=L.MAP_WINDOW_PART, p=(at.ws, at.nwy, at.nwy, at.g, at.g)) if at.parted else {}
+        self.gemm_w(ao, bp + ".proj.w", bias=w[f"{bp}.{nm.proj}.bias"], res=res, out32=res, **ukw)
+        self.ln(res, f"{bp}.{nm.norm2}", nm.eps, rvec, rpg, out16=x16)
+        hbuf = self.buf(at.pfx + ".mlp", (rows, self.cfg.encoder_spec.mlp))
+        self.gemm_w(x16, bp + ".lin1.w", bias=w[f"{bp}.{nm.lin1}.bias"], out16=hbuf, act=L.ACT_GELU)
+        last16 = self.buf("enc.last16", (rows, e)) if want16 else None
+        self.gemm_w(hbuf, bp + ".lin2.w", bias=w[f"{bp}.{nm.lin2}.bias"], res=res, out32=res, out16=last16)
+        return last16
 
     # ---- LayerNorm folded into its neighbour GEMMs (norm_fold) -------------------------------------------------------------------------
     def _fold_bufs(self, tag: str, rows: int, e: int):
         """(partial row sums of the producer GEMMs, (mean, rstd) rows of the consumer GEMMs - padded to whole 256-row tiles)."""
         return self.f32(tag + ".npart", (rows, e // 64, 2)), self.f32(tag + ".nmr", (_ceil(rows, 256), 2), zero=True)
-
-    def _fold_mean(self, pre: str, xpart, opart, bn: int, rpg: int, o_chunks: int, e: int, ea: int, ao) -> Optional[Tensor]:
-        """The block's token-mean correction as a FRESH per-image vector (the proj GEMM's epilogue adds it to the stream: nothing stays
-        pending): dR[img] = [mean(z) | mean(o)] . [Wo (Wv gamma)_lo | Wo_lo]^T, z = the normalised rows before gamma (la_norm_finalize)."""
-        if not self.mean_planes:
-            return None
-        wm = self.p[pre + ".mean.w32n"]
-        bar = self.f32("mean.bar", (bn, wm.shape[1]))
-        kx = self.mean_kx[pre]
-        if xpart is not None:
-            L.colsum_fold(xpart, bn, L.norm_cs_chunks(rpg), e, 1.0 / rpg, bar[:, :kx])
-        if opart is not None and o_chunks > 0:
-            L.colsum_fold(opart, bn, o_chunks, ea, 1.0 / rpg, bar[:, kx:])
-        elif opart is not None:
-            obar = self.f32("mean.obar", (bn, ea))
-            L.colmean16(ao, bn, rpg, obar, opart, 0, 0, 0)
-            bar[:, kx:].copy_(obar)
-        dr = self.f32("mean.dr", (bn, e))
-        L.gemm(bar, wm, out32=dr)
-        return dr
 
     def _planes_to_f32(self, xs: Tensor, name: str) -> Tensor:
         """hi + lo of a plane-pair stream as an fp32 matrix (the callers that leave the folded path: final LayerNorm, un-split necks)."""
@@ -841,96 +834,110 @@ class LamEngine:
         out.add_(xs[:, e:])
         return out
 
-    def _sam_encoder_fold(self, images: Tensor, want_last_block: bool = False):
-        """sam_encoder without LayerNorm passes (image_encoder.py:110-131,179-197): every residual GEMM is the PRODUCER of the next
-        LayerNorm's input, q | k | v and lin1 are its CONSUMERS (gamma-folded weights, normalisation in the epilogue); the token-mean
-        correction of a block joins the stream in the proj epilogue.  The residual stream itself is a pair of fp16 planes [hi | lo]
-        (same bytes as fp32, ~22 mantissa bits): the producers read-modify-write it in place and the hi plane IS the consumers' operand -
-        no separate 16-bit copy (a producer epilogue is bound by HBM round trips: the copy's 2 E bytes per row were + 20 % on proj,
-        + 8 % on lin2) - and the neck's 1 x 1 convolution takes the pair as it stands."""
+    def _block_fold(self, i: int, nm: BlockNames, at: AttnGeo, xs: Tensor, part: Tensor, mr: Tensor, have_mr: bool) -> None:
+        """_block_plain without LayerNorm passes (image_encoder.py:110-131,179-197; transformers ViTLayer): every residual GEMM is the
+        PRODUCER of the next LayerNorm's input, q | k | v and lin1 are its CONSUMERS (gamma-folded weights, normalisation in the epilogue);
+        the token-mean correction of a block joins the stream in the proj epilogue.  The residual stream itself is a pair of fp16 planes
+        xs = [hi | lo] (same bytes as fp32, ~22 mantissa bits): the producers read-modify-write it in place and the hi plane IS the
+        consumers' operand - no separate 16-bit copy (a producer epilogue is bound by HBM round trips: the copy's 2 E bytes per row were
+        + 20 % on proj, + 8 % on lin2).  part / mr: _fold_bufs; have_mr: the stack's entry already left this block's (mean, rstd) in mr."""
+        w, p, bp, rpg = self.w32, self.p, nm.prefix.format(i), at.rpg
+        rows, e = xs.shape[0], xs.shape[1] // 2
+        hi, lo = xs[:, :e], xs[:, e:]
+        xpart, opart = self.mean_parts(at, e)
+        vm = xpart is not None
+        if vm or not have_mr:
+            L.norm_finalize(None if have_mr else part, rows, e, nm.eps, mr, x16=hi if vm else None, rpg=rpg, cs_part=xpart)
+        qkv, _ = self._qkv(bp, i, at, hi, mr)
+        ao, o_chunks = self._attention(bp, at, qkv, None, opart)
+        dr = self._fold_mean(bp, at, e, xpart, opart, o_chunks, ao)
+        L.gemm(ao, p[bp + ".proj.w"], bias=w[f"{bp}.{nm.proj}.bias"], out16=hi, aux16=lo, nstat_out=part, rvec=dr,
+               rvec_rpg=rpg if dr is not None else 0, a_kmod=self.kmod.get(bp + ".proj.w", 0))
+        L.norm_finalize(part, rows, e, nm.eps, mr)
+        hbuf = self.buf(at.pfx + ".mlp", (rows, self.cfg.encoder_spec.mlp))
+        L.gemm(hi, p[bp + ".lin1.wn"], bias=p[bp + ".lin1.bn"], out16=hbuf, act=L.ACT_GELU, nstat_in=mr, ncol=p[bp + ".lin1.cn"])
+        L.gemm(hbuf, p[bp + ".lin2.w"], bias=w[f"{bp}.{nm.lin2}.bias"], out16=hi, aux16=lo, nstat_out=part,
+               a_kmod=self.kmod.get(bp + ".lin2.w", 0))
+
+    # ---- SAM ViTDet encoder (image_encoder.py:110-131,179-197,200-255) ------------------------------------------------------------------
+    def sam_encoder(self, images: Tensor, want_last_block: bool = False):
         spec: EncoderSpec = self.cfg.encoder_spec
-        pre = "image_encoder"
+        self._check_encoder_input(images)
+        pre, nm = "image_encoder", SAM_BLOCK
         bn, _, s, _ = images.shape
-        e, heads, g, ws = spec.dim, spec.heads, s // spec.patch, spec.window
+        if s != spec.img_size:
+            raise ValueError(f"SAM encoder expects {spec.img_size}x{spec.img_size} inputs, got {s}")
+        e, g, ws = spec.dim, s // spec.patch, spec.window
         hw = g * g
         rows = bn * hw
-        scale = spec.head_dim ** -0.5
-        hdp = self.head_pad
-        ea = heads * hdp
         w, p = self.w32, self.p
+        images = images.contiguous()
+        geo = {True: self._attn_geo("enc", bn, hw, g), False: self._attn_geo("enc", bn, hw, g, ws)}      # by "is a global block"
         a, akw = self.patches("enc.patchA", images, rows, spec.patch)
-        xs = self.buf("enc.xs", (rows, 2 * e), torch.float16)          # the stream: [hi | lo]
-        hi, lo = xs[:, :e], xs[:, e:]
-        part, mr = self._fold_bufs("enc", rows, e)
-        have_mr = False
-        if hw % 256 == 0:      # (plane pairs straight from the patch embedding's epilogue: no fp32 matrix is written at all)
-            L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".patch_embed.proj.bias"], res=p[pre + ".pos"], res_mod=hw, out16=hi, aux16=lo,
-                   nstat_out=part, **akw)
-        else:       # (a position table that is not whole row tiles: planes and statistics from a pass each, once)
-            res32 = self.f32("enc.res", (rows, e))
-            L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".patch_embed.proj.bias"], res=p[pre + ".pos"], res_mod=hw, out32=res32, **akw)
-            L.add_rowvec_split(res32, None, hw, xs)
-            L.norm_stats(res32, 1e-6, self.buf("enc.x16", (rows, e)), mr)
-            have_mr = True
-        nwy = (g + ws - 1) // ws
-        vm, pm = "vmean" in self.precise, "projmean" in self.precise
+        pkw = dict(bias=w[pre + ".patch_embed.proj.bias"], res=p[pre + ".pos"], res_mod=hw, **akw)
+        # (the producer epilogue adds the per-image correction to groups of whole row tiles or of >= 128 rows: smaller grids keep the kernels)
+        if self.norm_fold and self.attn_rows and ws <= 16 and (g == 64 or not spec.global_idx) and (hw % 256 == 0 or hw >= 128):
+            xs = self.buf("enc.xs", (rows, 2 * e), torch.float16)          # the stream: [hi | lo]
+            part, mr = self._fold_bufs("enc", rows, e)
+            have_mr = hw % 256 != 0
+            if not have_mr:     # (plane pairs straight from the patch embedding's epilogue: no fp32 matrix is written at all)
+                L.gemm(a, p[pre + ".patch.w"], out16=xs[:, :e], aux16=xs[:, e:], nstat_out=part, **pkw)
+            else:       # (a position table that is not whole row tiles: planes and statistics from a pass each, once)
+                res32 = self.f32("enc.res", (rows, e))
+                L.gemm(a, p[pre + ".patch.w"], out32=res32, **pkw)
+                L.add_rowvec_split(res32, None, hw, xs)
+                L.norm_stats(res32, nm.eps, self.buf("enc.x16", (rows, e)), mr)
+            for i in range(spec.depth):
+                self._block_fold(i, nm, geo[i in spec.global_idx], xs, part, mr, have_mr and i == 0)
+            return self._sam_exit(bn, g, want_last_block, xs=xs)
+        res = self.f32("enc.res", (rows, e))
+        L.gemm(a, p[pre + ".patch.w"], out32=res, **pkw)
+        x16 = self.buf("enc.x16", (rows, e))
+        last16 = rvec = None
+        if self.mean_planes:           # pending per-image corrections of the single-plane V / proj weights (PRECISE_WIDE)
+            rvec = self.f32("enc.rvec", (bn, e), zero=True)
+            rvec.zero_()
         for i in range(spec.depth):
-            bp = f"{pre}.blocks.{i}"
-            is_global = i in spec.global_idx
-            o_chunks = _ceil(hw, 128) // 128 if is_global else nwy * nwy * (_ceil(ws * ws, 128) // 128)
-            xpart = self.f32("mean.xpart", (bn * L.ln_cs_chunks(hw) * e,)) if vm else None
-            opart = self.f32("mean.opart", (bn * max(o_chunks, _ceil(hw, 128) // 128) * ea,)) if pm else None
-            if vm or not have_mr:
-                L.norm_finalize(None if have_mr else part, rows, e, 1e-6, mr, x16=hi if vm else None, rpg=hw, cs_part=xpart)
-            have_mr = False
-            qkv = self.buf("enc.qkv.r", (rows, 3 * ea))
-            L.gemm(hi, p[bp + ".qkv.wn"], bias=p[bp + ".qkv.bn"], out16=qkv, nstat_in=mr, ncol=p[bp + ".qkv.cn"])
-            ao = self.buf("enc.ao.r", (rows, ea))
-            fused_o = opart is not None and (is_global or self.win_fused_cs)
-            if is_global:
-                L.attn_fwd_rows(qkv, ao, bn, heads, hw, _ceil(hw, 64), g, ea, scale, L.ATTN_RELPOS, tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"],
-                                cspart=opart if fused_o else None)
-            else:
-                L.attn_fwd_rows(qkv, ao, bn * nwy * nwy, heads, ws * ws, _ceil(16 * ws, 64), ws, ea, scale, L.ATTN_RELPOS_WIN16,
-                                tabh=p[bp + ".tabh"], tabw=p[bp + ".tabw"], img_hw=(g, g), padrow=p[bp + ".qkv.pad16"],
-                                cspart=opart if fused_o else None)
-            dr = self._fold_mean(bp, xpart, opart, bn, hw, o_chunks if fused_o else 0, e, ea, ao)
-            L.gemm(ao, p[bp + ".proj.w"], bias=w[bp + ".attn.proj.bias"], out16=hi, aux16=lo, nstat_out=part, rvec=dr,
-                   rvec_rpg=hw if dr is not None else 0, a_kmod=self.kmod.get(bp + ".proj.w", 0))
-            L.norm_finalize(part, rows, e, 1e-6, mr)
-            hbuf = self.buf("enc.mlp", (rows, spec.mlp))
-            L.gemm(hi, p[bp + ".lin1.wn"], bias=p[bp + ".lin1.bn"], out16=hbuf, act=L.ACT_GELU, nstat_in=mr, ncol=p[bp + ".lin1.cn"])
-            L.gemm(hbuf, p[bp + ".lin2.w"], bias=w[bp + ".mlp.lin2.bias"], out16=hi, aux16=lo, nstat_out=part,
-                   a_kmod=self.kmod.get(bp + ".lin2.w", 0))
-        split_neck = self.cfg.use_vit_sam_neck and (pre + ".neck.0.ws") in p
-        res = None
-        if want_last_block or not split_neck:
-            res = self._planes_to_f32(xs, "enc.res")
-        if not self.cfg.use_vit_sam_neck:
-            last16 = self.buf("enc.last16", (rows, e))
-            last16.copy_(hi)
-            return (res, last16, e) if not want_last_block else ((res, last16, e), res)
-        out = self.conv_neck(pre + ".neck", hi, bn, g, "enc.neck", x32=res, xs=xs if split_neck else None)
-        if want_last_block:
-            return (out, None, spec.out_chans), res
-        return out, None, spec.out_chans
+            want16 = i == spec.depth - 1 and not (self.cfg.use_vit_sam_neck and "neck" in self.precise) and rvec is None
+            last16 = self._block_plain(i, nm, geo[i in spec.global_idx], res, x16, rvec, want16)
+        return self._sam_exit(bn, g, want_last_block, res=res, rvec=rvec, last16=last16)
 
-    def _sam_mlp(self, bp: str, i: int, res: Tensor, x16: Tensor, rows: int, spec, w, rvec, rkw) -> None:
-        """norm2 + lin1 (GELU) + lin2 (residual) of one SAM block; the last block may leave a 16-bit copy of the stream in ``self._last16``."""
-        e = spec.dim
-        self.ln(res, bp + ".norm2", 1e-6, out16=x16, **rkw)
-        hbuf = self.buf("enc.mlp", (rows, spec.mlp))
-        self.gemm_w(x16, bp + ".lin1.w", bias=w[bp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_GELU)
-        self._last16 = None
-        if i == spec.depth - 1 and not (self.cfg.use_vit_sam_neck and "neck" in self.precise) and rvec is None:
-            self._last16 = self.buf("enc.last16", (rows, e))
-            self.gemm_w(hbuf, bp + ".lin2.w", bias=w[bp + ".mlp.lin2.bias"], res=res, out32=res, out16=self._last16)
+    def _sam_exit(self, bn: int, g: int, want_last_block: bool, res: Optional[Tensor] = None, rvec: Optional[Tensor] = None,
+                  last16: Optional[Tensor] = None, xs: Optional[Tensor] = None):
+        """The stream leaves the SAM block stack - fp32 ``res`` with the pending ``rvec`` and, where lin2 wrote one, its 16-bit copy, or the
+        folded stack's planes ``xs`` - through the neck (or as it is).  Returns (out32, out16, channels), with want_last_block also the
+        last block's fp32 output."""
+        spec: EncoderSpec = self.cfg.encoder_spec
+        pre, e, hw = "image_encoder", spec.dim, g * g
+        neck = self.cfg.use_vit_sam_neck
+        split_neck = neck and (pre + ".neck.0.ws") in self.p
+        if xs is not None:             # folded stack: hi is the 16-bit copy, and the neck's 1 x 1 convolution takes the pair as it stands
+            last16 = xs[:, :e]
+            if want_last_block or not split_neck:
+                res = self._planes_to_f32(xs, "enc.res")
+            if not neck:
+                last16 = self.buf("enc.last16", last16.shape)
+                last16.copy_(xs[:, :e])
+            if not split_neck:
+                xs = None
         else:
-            self.gemm_w(hbuf, bp + ".lin2.w", bias=w[bp + ".mlp.lin2.bias"], res=res, out32=res)
+            if split_neck:             # the stream's last pass also leaves it as fp16 plane pairs: the neck's 1 x 1 conv operand
+                # (range: the pair [hi | lo] holds |x| <= 131008 - la_add_rowvec_split saturates beyond, it never emits inf / NaN; SAM
+                # checkpoints keep the un-normalised stream three orders of magnitude below that)
+                xs = self.buf("enc.res_split", (res.shape[0], 2 * e), torch.float16)
+                L.add_rowvec_split(res, rvec, hw, xs)
+            elif rvec is not None:     # the stream leaves the block stack: fold the pending corrections in
+                L.add_rowvec(res, rvec, hw)
+            if rvec is not None and not (neck and "neck" in self.precise):
+                last16 = self.buf("enc.last16", res.shape)
+                L.add_cast(res, out16=last16, dt=self.dti)
+        if neck:
+            out = (self.conv_neck(pre + ".neck", last16, bn, g, "enc.neck", x32=res, xs=xs), None, spec.out_chans)
+        else:
+            out = (res, last16, e)
+        return (out, res) if want_last_block else out
 
-    # ------------------------------------------------------------------------------------------------
-    # HuggingFace plain ViT encoder (transformers ViTModel maths; build_encoder.py:83-100)
-    # ------------------------------------------------------------------------------------------------
+    # ---- HuggingFace plain ViT encoder (transformers ViTModel maths; build_encoder.py:83-100) -------------------------------------------
     def _hf_pos(self, g: int) -> Tensor:
         t = self._hfpos_cache.get(g)
         if t is None:
@@ -951,9 +958,9 @@ class LamEngine:
     def hf_encoder(self, images: Tensor):
         spec: EncoderSpec = self.cfg.encoder_spec
         self._check_encoder_input(images)
-        pre = "image_encoder"
+        pre, nm = "image_encoder", HF_BLOCK
         bn, _, s, _ = images.shape
-        e, heads, g = spec.dim, spec.heads, s // spec.patch
+        e, g = spec.dim, s // spec.patch
         hw = g * g
         t = hw + 1
         rows = bn * t
@@ -966,101 +973,28 @@ class LamEngine:
         res.view(bn, t, e)[:, 0].copy_(cls_row)      # CLS row = cls_token + pos[0] (weights only; plain copy)
         L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".embeddings.patch_embeddings.projection.bias"], res=pos, res_mod=t,
                out32=res, map=L.MAP_GROUP, p=(hw, t, 1, 0, 0), **akw)
-        tpad = _ceil(t, 64)
         x16 = self.buf("hf.x16", (rows, e))
-        hdp = self.head_pad
-        ea = heads * hdp
-        qkv = self.buf("hf.qkv", (rows, 3 * ea))
-        fp8 = self.attn_fp8 and hdp == 64          # (the fp8 QK^T kernel keeps its V^T operand)
-        rows_path = self.attn_rows and not fp8     # no V^T copy: la_attn_fwd_rows
-        if self.norm_fold and rows_path and t >= 128:       # (per-image groups of the producer epilogue: >= 128 rows)
-            return self._hf_fold_blocks(res, bn, t, hw, e, heads, hdp, ea, spec, qkv)
-        vt = None if rows_path else self.buf("hf.vt", (bn * heads, hdp, tpad), zero=True)
-        ao = self.buf("hf.ao", (rows, ea))
-        hbuf = self.buf("hf.mlp", (rows, spec.mlp))
-        scale = spec.head_dim ** -0.5
+        at = self._attn_geo("hf", bn, t)
         rvec = None
-        if self.mean_planes:
-            rvec = self.f32("hf.rvec", (bn, e), zero=True)
-            rvec.zero_()
-        rkw = dict(rvec=rvec, rpg=t) if rvec is not None else {}
-        xpart = opart = None
-        o_chunks = _ceil(t, 128) // 128
-        if rvec is not None:
-            xpart, opart = self.mean_parts(bn, t, e, ea, o_chunks)
-        ckw = dict(colsum_part=xpart) if xpart is not None else {}
-        for i in range(spec.depth):
-            lp = f"{pre}.encoder.layer.{i}"
-            self.ln(res, lp + ".layernorm_before", 1e-12, out16=x16, **rkw, **ckw)
-            if rows_path:
-                self.qkv_gemm(x16, lp + ".qkv.w", qkv, None, ea)
-            else:
-                self.qkv_gemm(x16, lp + ".qkv.w", qkv, vt, ea, vt_T=t, vt_Tpad=tpad, vt_hd=hdp, vt_heads=heads)
-            fused_o = opart is not None and not fp8
-            if rows_path:
-                L.attn_fwd_rows(qkv, ao, bn, heads, t, tpad, 0, ea, scale, L.ATTN_PLAIN, cspart=opart if fused_o else None)
-            elif self.attn_fp8 and hdp == 64:
-                qk8 = self.arena.get("hf.qk8", (rows, 2 * ea), torch.uint8, False)
-                L.qk_fp8(qkv, ea, qk8)
-                L.attn_fwd_fp8(qk8, vt, ao, bn, heads, t, tpad, ea, scale)
-            elif fused_o:
-                L.attn_fwd_cs(qkv, vt, ao, None, None, bn, heads, t, tpad, 0, ea, scale, L.ATTN_PLAIN, opart)
-            else:
-                L.attn_fwd(qkv, vt, ao, None, None, bn, heads, t, tpad, 0, ea, scale, L.ATTN_PLAIN)
-            if rvec is not None:
-                self.mean_fix(lp, xpart, opart, rvec, bn, t, o_chunks if fused_o else 0, e, ea, ao=ao)
-            self.gemm_w(ao, lp + ".o.w", bias=w[lp + ".attention.output.dense.bias"], res=res, out32=res)
-            self.ln(res, lp + ".layernorm_after", 1e-12, out16=x16, **rkw)
-            self.gemm_w(x16, lp + ".fc1.w", bias=w[lp + ".intermediate.dense.bias"], out16=hbuf, act=L.ACT_GELU)
-            self.gemm_w(hbuf, lp + ".fc2.w", bias=w[lp + ".output.dense.bias"], res=res, out32=res)
+        if self.norm_fold and at.form == "rows" and t >= 128:       # (per-image groups of the producer epilogue: >= 128 rows)
+            # The stream enters through a row map (CLS gap), so its planes and first statistics come from one pass each; the final
+            # ``layernorm`` is the LayerNorm kernel on hi + lo.
+            xs = self.buf("hf.xs", (rows, 2 * e), torch.float16)
+            part, mr = self._fold_bufs("hf", rows, e)
+            L.add_rowvec_split(res, None, t, xs)
+            L.norm_stats(res, nm.eps, x16, mr)
+            for i in range(spec.depth):
+                self._block_fold(i, nm, at, xs, part, mr, i == 0)
+            res = self._planes_to_f32(xs, "hf.res")
+        else:
+            if self.mean_planes:
+                rvec = self.f32("hf.rvec", (bn, e), zero=True)
+                rvec.zero_()
+            for i in range(spec.depth):
+                self._block_plain(i, nm, at, res, x16, rvec)
         fin = self.f32("hf.final", (rows, e))
         fin16 = self.buf("hf.final16", (rows, e))
-        self.ln(res, pre + ".layernorm", 1e-12, out32=fin, out16=fin16, **rkw)
-        out32 = self.f32("hf.out32", (bn * hw, e))
-        out16 = self.buf("hf.out16", (bn * hw, e))
-        out32.view(bn, hw, e).copy_(fin.view(bn, t, e)[:, 1:])          # drop CLS (plain strided copy)
-        out16.view(bn, hw, e).copy_(fin16.view(bn, t, e)[:, 1:])
-        return out32, out16, e
-
-    def _hf_fold_blocks(self, res: Tensor, bn: int, t: int, hw: int, e: int, heads: int, hdp: int, ea: int, spec, qkv: Tensor):
-        """The HF block stack without LayerNorm passes (transformers ViTLayer: layernorm_before / layernorm_after folded into the q | k | v
-        and fc1 GEMMs; eps 1e-12) on a plane-pair stream: see _sam_encoder_fold.  The stream enters through a row map (CLS gap), so its
-        planes and first statistics come from one pass each; the final ``layernorm`` is the LayerNorm kernel on hi + lo."""
-        pre = "image_encoder"
-        rows = bn * t
-        w, p = self.w32, self.p
-        xs = self.buf("hf.xs", (rows, 2 * e), torch.float16)
-        hi, lo = xs[:, :e], xs[:, e:]
-        part, mr = self._fold_bufs("hf", rows, e)
-        L.add_rowvec_split(res, None, t, xs)
-        L.norm_stats(res, 1e-12, self.buf("hf.x16", (rows, e)), mr)
-        have_mr = True
-        ao = self.buf("hf.ao", (rows, ea))
-        hbuf = self.buf("hf.mlp", (rows, spec.mlp))
-        scale = spec.head_dim ** -0.5
-        tpad = _ceil(t, 64)
-        vm, pm = "vmean" in self.precise, "projmean" in self.precise
-        o_chunks = _ceil(t, 128) // 128
-        xpart = self.f32("mean.xpart", (bn * L.ln_cs_chunks(t) * e,)) if vm else None
-        opart = self.f32("mean.opart", (bn * o_chunks * ea,)) if pm else None
-        for i in range(spec.depth):
-            lp = f"{pre}.encoder.layer.{i}"
-            if vm or not have_mr:
-                L.norm_finalize(None if have_mr else part, rows, e, 1e-12, mr, x16=hi if vm else None, rpg=t, cs_part=xpart)
-            have_mr = False
-            L.gemm(hi, p[lp + ".qkv.wn"], bias=p[lp + ".qkv.bn"], out16=qkv, nstat_in=mr, ncol=p[lp + ".qkv.cn"])
-            L.attn_fwd_rows(qkv, ao, bn, heads, t, tpad, 0, ea, scale, L.ATTN_PLAIN, cspart=opart)
-            dr = self._fold_mean(lp, xpart, opart, bn, t, o_chunks, e, ea, ao)
-            L.gemm(ao, p[lp + ".o.w"], bias=w[lp + ".attention.output.dense.bias"], out16=hi, aux16=lo, nstat_out=part, rvec=dr,
-                   rvec_rpg=t if dr is not None else 0, a_kmod=self.kmod.get(lp + ".o.w", 0))
-            L.norm_finalize(part, rows, e, 1e-12, mr)
-            L.gemm(hi, p[lp + ".fc1.wn"], bias=p[lp + ".fc1.bn"], out16=hbuf, act=L.ACT_GELU, nstat_in=mr, ncol=p[lp + ".fc1.cn"])
-            L.gemm(hbuf, p[lp + ".fc2.w"], bias=w[lp + ".output.dense.bias"], out16=hi, aux16=lo, nstat_out=part,
-                   a_kmod=self.kmod.get(lp + ".fc2.w", 0))
-        res = self._planes_to_f32(xs, "hf.res")
-        fin = self.f32("hf.final", (rows, e))
-        fin16 = self.buf("hf.final16", (rows, e))
-        self.ln(res, pre + ".layernorm", 1e-12, out32=fin, out16=fin16)
+        self.ln(res, pre + ".layernorm", nm.eps, rvec, t, out32=fin, out16=fin16)
         out32 = self.f32("hf.out32", (bn * hw, e))
         out16 = self.buf("hf.out16", (bn * hw, e))
         out32.view(bn, hw, e).copy_(fin.view(bn, t, e)[:, 1:])          # drop CLS (plain strided copy)

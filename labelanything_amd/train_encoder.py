@@ -171,19 +171,19 @@ class HfEncoderGraph:
             sv["lse"] = torch.full((bn * heads, tpad), 1e30, device=dev)
             L.attn_fwd_lse(sv["qkv"], vt, sv["ao"], sv["lse"], bn, heads, t, tpad, ea, scale)
             x_mid = torch.empty(rows, e, device=dev)
-            eng.gemm_w(sv["ao"], lp + ".o.w", bias=w[lp + ".attention.output.dense.bias"], res=res, out32=x_mid)
+            eng.gemm_w(sv["ao"], lp + ".proj.w", bias=w[lp + ".attention.output.dense.bias"], res=res, out32=x_mid)
             sv["x_mid"] = x_mid
             x16b = torch.empty(rows, e, device=dev, dtype=dt)
             sv["xnb"] = x16b
             eng.ln(x_mid, lp + ".layernorm_after", 1e-12, out16=x16b)
             sv["post"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
             sv["pre"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-            self._fc1_fwd(eng, x16b, lp + ".fc1.w", w[lp + ".intermediate.dense.bias"], sv["pre"], sv["post"])
+            self._fc1_fwd(eng, x16b, lp + ".lin1.w", w[lp + ".intermediate.dense.bias"], sv["pre"], sv["post"])
             # fused / unfused is decided ONCE per graph, here, for the backward half too (la_gemm_fused_act_ok reads the library's
             # mutable kernel selection: an A/B tool that toggles it between forward and backward must not mix the two forms)
             sv["fuse_fc2_bwd"] = bool(self.fused_gelu and L.gemm_fused_act_ok(rows, spec.mlp, e))
             res = torch.empty(rows, e, device=dev)
-            eng.gemm_w(sv["post"], lp + ".fc2.w", bias=w[lp + ".output.dense.bias"], res=x_mid, out32=res)
+            eng.gemm_w(sv["post"], lp + ".lin2.w", bias=w[lp + ".output.dense.bias"], res=x_mid, out32=res)
             layers.append(sv)
         fin = torch.empty(rows, e, device=dev)
         eng.ln(res, pre + ".layernorm", 1e-12, out32=fin)

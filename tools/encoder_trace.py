@@ -1,0 +1,195 @@
+#!/usr/bin/env python
+"""Launch trace of the image-encoder driver, on the CPU.
+
+Every public function of ``labelanything_amd._lib`` is replaced by a recorder, so ``LamEngine.encode_images`` runs without a GPU and
+leaves one line per launch: the function and every argument that is not at its default, under the name the launcher's signature gives
+it (a positional and a keyword spelling of one argument are the same launch); for a tensor its shape, dtype, strides, storage (numbered
+by first appearance in the trace) and storage offset.  A last line holds what the encoder returned.  Two drivers with the same trace
+launch the same kernels with the same arguments, in the same order, on the same buffers and aliases - what
+tests/test_encoder_trace_cpu.py pins for the matrix below.
+
+  python tools/encoder_trace.py --table             name, number of calls, sha256 of the trace for the whole matrix
+  python tools/encoder_trace.py --print NAME        one trace
+  python tools/encoder_trace.py --packed NAME       key, shape, dtype, sha256 of the bytes of every packed weight of NAME's engine
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import inspect
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from labelanything_amd import _lib as L                                            # noqa: E402
+from labelanything_amd.config import EncoderSpec, LamConfig, register_encoder     # noqa: E402
+
+# host arithmetic only (or never reached by the encoder): these keep working
+PURE = ("ln_cs_chunks", "norm_cs_chunks", "conv3x3_split_ok", "extract_pool_plan", "twoway_part_size", "dt_of")
+LAUNCHERS = {n: inspect.signature(f) for n, f in vars(L).items()
+             if not n.startswith("_") and n not in PURE and inspect.isfunction(f) and f.__module__ == L.__name__}
+# the ``**epilogue`` keywords of gemm / gemm_plan are those of _gemm_epilogue, defaults included
+EPILOGUE = {k: v.default for k, v in inspect.signature(L._gemm_epilogue).parameters.items() if v.kind is v.KEYWORD_ONLY}
+
+
+def _is_default(v, default) -> bool:
+    return not isinstance(v, torch.Tensor) and type(v) is type(default) and v == default
+
+
+class Recorder:
+    """Stands in for the library: ``patch(setattr)`` replaces every public function of ``_lib`` with one that appends a line here."""
+
+    def __init__(self):
+        self.lines = []
+        self._storages = {}
+        self._keep = []          # a freed storage's address would be reused and renumber the trace: hold every tensor seen
+
+    def _fmt(self, v) -> str:
+        if isinstance(v, torch.Tensor):
+            self._keep.append(v)
+            n = self._storages.setdefault(v.untyped_storage().data_ptr(), len(self._storages))
+            return f"T({tuple(v.shape)},{str(v.dtype)[6:]},{tuple(v.stride())},s{n}+{v.storage_offset()})"
+        if isinstance(v, (tuple, list)):
+            return "(" + ",".join(self._fmt(x) for x in v) + ")"
+        return repr(v)
+
+    def _stub(self, name: str):
+        def call(*args, **kw):
+            # arguments by the NAME the launcher gives them, so that a positional and a keyword spelling, or a default written out and
+            # one left out, record the same launch: signature order, then the other keywords sorted; defaults are not printed
+            named = LAUNCHERS[name].bind(*args, **kw).arguments
+            extra = named.pop("epilogue", {})
+            parts = [f"{k}={self._fmt(v)}" for k, v in named.items() if not _is_default(v, LAUNCHERS[name].parameters[k].default)]
+            parts += [f"{k}={self._fmt(extra[k])}" for k in sorted(extra) if not _is_default(extra[k], EPILOGUE[k])]
+            self.lines.append(f"{name} " + " ".join(parts))
+            return args[0] if name == "twoway_pe_layout" else None
+        return call
+
+    def patch(self, setattr_) -> None:
+        """setattr_(module, name, value): ``monkeypatch.setattr`` in the tests (restored afterwards), plain ``setattr`` in the tool."""
+        for name in LAUNCHERS:
+            setattr_(L, name, (lambda: None) if name == "lib" else self._stub(name))
+
+    def digest(self):
+        return len(self.lines), hashlib.sha256("\n".join(self.lines).encode()).hexdigest()
+
+
+def _wide(kind: str, depth: int, **kw) -> EncoderSpec:
+    return EncoderSpec(kind, dim=768, depth=depth, heads=12, mlp=3072, **kw)
+
+
+def _specs() -> None:
+    import tests.cases          # noqa: F401  (registers sam_tiny, hf_tiny)
+    for s in (1024, 448, 256):
+        register_encoder(f"trace_sam_{s}", _wide("sam", 3, img_size=s, global_idx=(2,), window=14))
+    register_encoder("trace_sam_640_w20", _wide("sam", 3, img_size=640, global_idx=(2,), window=20))
+    register_encoder("trace_sam_hd80", EncoderSpec("sam", dim=160, depth=2, heads=2, mlp=320, img_size=448, global_idx=(1,), window=14,
+                                                   out_chans=64))
+    register_encoder("trace_hf", _wide("hf", 2, img_size=224))
+    register_encoder("trace_hf_hd32", EncoderSpec("hf", dim=128, depth=2, heads=4, mlp=256, img_size=224))
+
+
+def _sam(size: int, enc=None, ctor=None, attrs=None, last=False, **cfg):
+    cfg.setdefault("image_embed_dim", 256)
+    return dict(cfg=dict(encoder=enc or f"trace_sam_{size}", image_size=size, embed_dim=64, **cfg), ctor=ctor or {}, attrs=attrs or {},
+                last=last)
+
+
+def _hf(size: int, enc="trace_hf", attrs=None, dim=768):
+    return dict(cfg=dict(encoder=enc, image_size=size, image_embed_dim=dim, embed_dim=64), ctor={}, attrs=attrs or {}, last=False)
+
+
+def matrix() -> dict:
+    """name -> configuration.  Two images each; see the module docstring of tests/test_encoder_trace_cpu.py for what each row reaches."""
+    from labelanything_amd.engine import PRECISE_WIDE_PLANES
+    nofold = {"norm_fold": False}
+    return {
+        "sam 1024 default": _sam(1024),
+        "sam 1024 nofold": _sam(1024, attrs=nofold),
+        "sam 1024 nofold norows nocs": _sam(1024, attrs={"norm_fold": False, "attn_rows": False, "win_fused_cs": False}),
+        "sam 1024 planes": _sam(1024, ctor={"precise": PRECISE_WIDE_PLANES}),
+        "sam 1024 planes norows": _sam(1024, ctor={"precise": PRECISE_WIDE_PLANES}, attrs={"attn_rows": False}),
+        "sam 1024 imprecise": _sam(1024, ctor={"precise": ()}),
+        "sam 1024 bf16": _sam(1024, ctor={"dtype": torch.bfloat16}),
+        "sam 1024 no neck": _sam(1024, use_vit_sam_neck=False, image_embed_dim=768),
+        "sam 1024 last block": _sam(1024, last=True),
+        "sam 1024 last block nofold": _sam(1024, attrs=nofold, last=True),
+        "sam 448 default": _sam(448),
+        "sam 448 norows": _sam(448, attrs={"attn_rows": False}),
+        "sam 256 default": _sam(256),
+        "sam 640 window 20": _sam(640, enc="trace_sam_640_w20"),
+        "sam_tiny": _sam(224, enc="sam_tiny", image_embed_dim=96),
+        "sam_tiny norows": _sam(224, enc="sam_tiny", image_embed_dim=96, attrs={"attn_rows": False}),
+        "sam hd80 448": _sam(448, enc="trace_sam_hd80", image_embed_dim=64),
+        "hf 224 default": _hf(224),
+        "hf 224 nofold": _hf(224, attrs=nofold),
+        "hf 224 nofold norows": _hf(224, attrs={"norm_fold": False, "attn_rows": False}),
+        "hf 224 fp8": _hf(224, attrs={"attn_fp8": True}),
+        "hf 96 default": _hf(96),
+        "hf_tiny 240": _hf(240, enc="hf_tiny", dim=128),
+        "hf hd32 160": _hf(160, enc="trace_hf_hd32", dim=128),
+    }
+
+
+def engine(row: dict):
+    """The engine of one row, built on the CPU (call under a patched ``_lib``)."""
+    from labelanything_amd.engine import LamEngine
+    from labelanything_amd.weights import init_state_dict
+    _specs()
+    cfg = LamConfig(spatial_convs=3, custom_preprocess=False, **row["cfg"])
+    eng = LamEngine(cfg, init_state_dict(cfg, 0), torch.device("cpu"), **row["ctor"])
+    for k, v in row["attrs"].items():
+        assert hasattr(eng, k), k
+        setattr(eng, k, v)
+    return eng
+
+
+def trace(row: dict, setattr_=setattr) -> Recorder:
+    """Run one row's encoder under a fresh recorder."""
+    rec = Recorder()
+    rec.patch(setattr_)
+    eng = engine(row)
+    s = row["cfg"]["image_size"]
+    images = torch.zeros(2, 3, s, s)
+    out = eng.sam_encoder(images, want_last_block=True) if row["last"] else eng.encode_images(images)
+    rec.lines.append("return " + rec._fmt(out))          # which buffers the caller gets
+    return rec
+
+
+def _sha_entries(key: str, v):
+    if isinstance(v, torch.Tensor):
+        raw = v.detach().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()
+        yield key, tuple(v.shape), str(v.dtype)[6:], hashlib.sha256(raw).hexdigest()
+    else:
+        for i, x in enumerate(v):
+            yield from _sha_entries(f"{key}[{i}]", x)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--print", dest="show", metavar="NAME")
+    g.add_argument("--table", action="store_true")
+    g.add_argument("--packed", metavar="NAME")
+    a = ap.parse_args()
+    rows = matrix()
+    if a.table:
+        for name, row in rows.items():
+            n, h = trace(row).digest()
+            print(f"{name!r}: ({n}, {h!r}),")
+    elif a.show:
+        print("\n".join(trace(rows[a.show]).lines))
+    else:
+        Recorder().patch(setattr)
+        for k, v in sorted(engine(rows[a.packed]).p.items()):
+            for ent in _sha_entries(k, v):
+                print(*ent)
+
+
+if __name__ == "__main__":
+    main()
