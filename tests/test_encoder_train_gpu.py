@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from labelanything_amd import _lib as L
+from tests.test_multi_embedding_gpu import NAN, check_guards, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -329,28 +330,34 @@ def test_weight_gradient_from_row_major_16bit_operands_matches_torch(shape):
     r, n, k = shape[:3]
     dt = torch.bfloat16 if "bf16" in shape else torch.float16
     g = torch.Generator().manual_seed(r + n)
-    dy_wide = torch.randn(r, n + 64, generator=g).to(dt).cuda()
-    x_wide = torch.randn(r, k + 8, generator=g).to(dt).cuda()
+    dy_wide = torch.full((r, n + 64), NAN, dtype=dt, device="cuda")          # the parents' other columns hold NaN
+    x_wide = torch.full((r, k + 8), NAN, dtype=dt, device="cuda")
+    dy_wide[:, 64:] = torch.randn(r, n, generator=g).to(dt).cuda()
+    x_wide[:, :k] = torch.randn(r, k, generator=g).to(dt).cuda()
     dy, x = dy_wide[:, 64:], x_wide[:, :k]
     db0 = torch.randn(n, generator=g).cuda()
-    db = db0.clone()
+    db_buf, db = guarded(n)                                                  # dW and db between NaN guards
+    db.copy_(db0)
     ref = dy.double().t() @ x.double()
     if "group" in shape:
         e, apart = n // 3, n // 3 + 5                  # E weight rows, then 5 rows of something else (the bias and alignment) before the next block
         buf0 = torch.randn(3 * apart, k, generator=g).cuda()
-        buf = buf0.clone()
+        buf_buf, buf = guarded(3 * apart, k)
+        buf.copy_(buf0)
         L.gemm_tn16(dy, x, buf[:e], db=db, gsize=e, gstride=apart)
-        torch.cuda.synchronize()
+        check_guards(buf_buf, buf)
         for j in range(3):
             got = buf[j * apart: j * apart + e].double() - buf0[j * apart: j * apart + e].double()
             assert float((got - ref[j * e:(j + 1) * e]).abs().max() / ref.abs().max()) < 1e-5, j
             assert torch.equal(buf[j * apart + e:(j + 1) * apart], buf0[j * apart + e:(j + 1) * apart])         # rows in between untouched
     else:
         dw0 = torch.randn(n, k, generator=g).cuda()
-        dw = dw0.clone()
+        dw_buf, dw = guarded(n, k)
+        dw.copy_(dw0)
         L.gemm_tn16(dy, x, dw, db=db)
-        torch.cuda.synchronize()
+        check_guards(dw_buf, dw)
         assert float((dw.double() - dw0.double() - ref).abs().max() / ref.abs().max()) < 1e-5      # fp32 accumulation of exactly representable products
+    check_guards(db_buf, db)
     want = db0.double() + dy.double().sum(0)
     assert float((db.double() - want).abs().max()) <= 2e-5 * float(dy.double().abs().sum(0).max()), "fused column sums"
 

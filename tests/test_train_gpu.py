@@ -14,6 +14,7 @@ from oracle import lam_oracle as O
 from oracle import loss_oracle as LO
 from tests.cases import CASES, geometry_for
 from tests.helpers import GOLDEN, load_golden, rel_err
+from tests.test_multi_embedding_gpu import NAN, check_guards, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -258,18 +259,25 @@ def test_weight_gradient_gemm_tn_matches_torch(mnk):
     dy = torch.randn(m, n, generator=g).cuda()
     x = torch.randn(m, k, generator=g).cuda()
     dw0 = torch.randn(n, k, generator=g).cuda()
-    dw = dw0.clone()
+    dw_buf, dw = guarded(n, k)                                   # dW between NaN guards: a tail tile must not store past it
+    dw.copy_(dw0)
     L.gemm_tn(dy, x, dw)
-    torch.cuda.synchronize()
+    check_guards(dw_buf, dw)
     ref = dw0.double() + dy.double().t() @ x.double()
     assert float((dw.double() - ref).abs().max() / ref.abs().max()) < 2e-6
-    # with the bias gradient, on column slices (row stride = the parent's width)
-    wide_dy = torch.randn(m, n + 8, generator=g).cuda()
-    wide_x = torch.randn(m, k + 4, generator=g).cuda()
+    # with the bias gradient, on column slices (row stride = the parent's width; the parent's other columns hold NaN)
+    wide_dy = torch.full((m, n + 8), NAN, device="cuda")
+    wide_x = torch.full((m, k + 4), NAN, device="cuda")
+    wide_dy[:, 4:4 + n] = torch.randn(m, n, generator=g).cuda()
+    wide_x[:, 4:4 + k] = torch.randn(m, k, generator=g).cuda()
     dys, xs = wide_dy[:, 4:4 + n], wide_x[:, 4:4 + k]
-    dw, db = dw0.clone(), torch.ones(n, device="cuda")
+    dw_buf, dw = guarded(n, k)
+    dw.copy_(dw0)
+    db_buf, db = guarded(n)
+    db.fill_(1.0)
     L.gemm_tn(dys, xs, dw, db)
-    torch.cuda.synchronize()
+    check_guards(dw_buf, dw)
+    check_guards(db_buf, db)
     ref = dw0.double() + dys.double().t() @ xs.double()
     assert float((dw.double() - ref).abs().max() / ref.abs().max()) < 2e-6
     refb = 1.0 + dys.double().sum(0)
