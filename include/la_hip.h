@@ -246,6 +246,19 @@ int la_mask_embed(const float* masks, const int* flags, int P, int C, int Hm, in
                   const float* support, const float* class_enc, const float* pe, float* src32, void* src16, void* srcpe16,
                   int dt, void* stream);
 
+/* Dense prompts of the TokenPool prompt encoder (PromptImagePoolEncoder.forward, prompt_encoder.py:880-896): ONE slab per support image,
+ *   src32[s, pix, :] = support[s, pix, :] + sum_c (dense[s, c, pix, :] + class_enc[c, :]),
+ * where dense[s, c] is what la_mask_embed computes for the pair (s, c) before its support and class terms: the resampled mask
+ * embedding, not_a_mask where flags[s*C + c] == 0, no_mask without mask prompts.  masks fp32 [S*C, Hm, Hm] or NULL; flags int32 [S*C] or
+ * NULL; w: the 12 pointers of la_mask_embed; support fp32 [S, g*g, D] or NULL; class_enc fp32 [C, D] or NULL; pe fp32 [g*g, D].
+ * Outputs [S*g*g, D]: src32, and src16 / srcpe16 (or NULL) in the storage forms of la_mask_embed.  fp32 throughout; the 16-channel
+ * hidden maps of the VALID classes are summed in ascending c before the 1x1 convolution (which commutes with the resample and the
+ * sum), so the D-wide work is done once per support pixel; no atomics: a support gives the same bits alone and inside a batch.
+ * Shape constraints of la_mask_embed, C >= 1, S <= 65535; anything else is refused and nothing is written. */
+int la_mask_embed_pooled(const float* masks, const int* flags, int S, int C, int Hm, int g, int D, const float* const* w,
+                         const float* support, const float* class_enc, const float* pe, float* src32, void* src16, void* srcpe16,
+                         int dt, void* stream);
+
 /* Decoder attention core after the q/k/v projections (common.py:126-144): softmax(q k^T / sqrt(hd)) v in fp32.
  * q [B,Nq,ldq], k/v [B,Nk,ld*] fp32, head h at column h*hd; hd in {4,8,16,32,64}.  Output [B,Nq,ldo] 16-bit and/or fp32. */
 int la_attn_small(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int Nq, int Nk, int heads,

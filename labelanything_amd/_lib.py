@@ -74,6 +74,7 @@ EXPORTS = [
     "la_proto_kernels", "la_proto_kernels_bwd", "la_classify_conv", "la_classify_conv_bwd",
     "la_extract_pool_plan", "la_extract_pool", "la_extract_fold", "la_extract_unfold",
     "la_mfma_shape_probe",
+    "la_mask_embed_pooled",
 ]
 
 
@@ -319,6 +320,15 @@ def mask_embed(masks, flags, p: int, c: int, hm: int, g: int, d: int, wlist, sup
     _check(lib().la_mask_embed(_ptr(masks), _ptr(flags), C.c_int(p), C.c_int(c), C.c_int(hm), C.c_int(g), C.c_int(d), arr,
                                _ptr(support), _ptr(class_enc), _ptr(pe), _ptr(src32), _ptr(src16), _ptr(srcpe16), C.c_int(dt),
                                _stream()), "la_mask_embed")
+
+
+def mask_embed_pooled(masks, flags, s: int, c: int, hm: int, g: int, d: int, wlist, support, class_enc, pe, src32, src16, srcpe16,
+                      dt: int) -> None:
+    """la_mask_embed_pooled: one [g*g, D] slab per support image, the dense prompts of its ``c`` classes summed (TokenPool)."""
+    arr = (C.c_void_p * 12)(*[w.data_ptr() for w in wlist])
+    _check(lib().la_mask_embed_pooled(_ptr(masks), _ptr(flags), C.c_int(s), C.c_int(c), C.c_int(hm), C.c_int(g), C.c_int(d), arr,
+                                      _ptr(support), _ptr(class_enc), _ptr(pe), _ptr(src32), _ptr(src16), _ptr(srcpe16), C.c_int(dt),
+                                      _stream()), "la_mask_embed_pooled")
 
 
 def attn_small(q, k, v, b: int, nq: int, nk: int, heads: int, hd: int, *, out16=None, out32=None, dt: int = LA_F16) -> None:

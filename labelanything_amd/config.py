@@ -66,7 +66,7 @@ class LamConfig:
     """Keyword surface of ``LabelAnything.__init__`` (build_lam.py:470-498), on-path subset.
 
     Off-path switches (few_type=Affinity, OneWay/Identity fusion, binary, pyramids,
-    class_embedding_dim, TokenPool) are accepted only at their default value; anything else raises NotImplementedError.
+    class_embedding_dim) are accepted only at their default value; anything else raises NotImplementedError.
     ``embedding_extraction`` takes None and "cross_attention"; every other value ("pooler" ...) raises NotImplementedError.
     """
 
@@ -109,6 +109,11 @@ class LamConfig:
     # prompt_encoder.py:280-313,719-724; parameters/validation/Pascal/mae_cross.yaml).  Adds 37 tensors under
     # prompt_encoder.embedding_extraction.; the three merge attentions are not run.  embeddings_per_example need not be a square.
     embedding_extraction: Optional[str] = None
+    # "TokenPool": PromptImagePoolEncoder (prompt_encoder.py:830-915; parameters/trainval/{pascal,coco20i}/mae_pool.yaml).  The dense
+    # prompts of a support's C classes are summed into ONE slab per support image, the two-way transformer runs over B M slabs with the
+    # C Ns tokens of the support, and an example's embedding is the mean of its class's OUTPUT tokens - so final_attn_token_to_image and
+    # norm_final_attn, dead in the plain prompt encoder, are live.  Adds no parameters.
+    prompt_encoder: Optional[str] = None
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -158,7 +163,6 @@ _OFF_PATH_DEFAULTS = dict(
     fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
     dropout=0.0, binary=False,
-    prompt_encoder=None,
 )
 
 
@@ -225,6 +229,26 @@ def check_classification(rate, conv_classification, segment_example_logits, leve
                                   "is not built: no reference recipe combines them")
 
 
+def check_prompt_encoder(prompt_encoder, segment_example_logits, embedding_extraction, levels, conv_classification) -> None:
+    """The one check of ``prompt_encoder`` (config_from_kwargs and Lam), on the RESOLVED segment_example_logits."""
+    if prompt_encoder is None:
+        return
+    if prompt_encoder != "TokenPool":
+        raise ValueError(f"prompt_encoder={prompt_encoder!r}: None (the plain prompt encoder) or 'TokenPool' (build_lam.py:121,181)")
+    if embedding_extraction is not None:
+        raise NotImplementedError("prompt_encoder='TokenPool' together with embedding_extraction is not built: the token means replace "
+                                  "the stream's embeddings, and no reference recipe combines them")
+    if segment_example_logits:
+        raise NotImplementedError("prompt_encoder='TokenPool' together with segment_example_logits / embeddings_per_example is not built: "
+                                  "no reference recipe combines them")
+    if levels == 2:
+        raise NotImplementedError("prompt_encoder='TokenPool' together with classification_levels=2 is not built: no reference recipe "
+                                  "combines them")
+    if conv_classification:
+        raise NotImplementedError("prompt_encoder='TokenPool' together with conv_classification is not built: no reference recipe "
+                                  "combines them")
+
+
 def config_from_kwargs(**kw) -> LamConfig:
     """Build a LamConfig from reference-style kwargs, rejecting off-path ablation switches."""
     kw = dict(kw)
@@ -242,6 +266,8 @@ def config_from_kwargs(**kw) -> LamConfig:
         raise TypeError(f"unexpected LabelAnything arguments: {unknown}")
     kw["segment_example_logits"], kw["embeddings_per_example"] = resolve_examples(kw.get("segment_example_logits", False),
                                                                                   kw.get("embeddings_per_example"))
+    check_prompt_encoder(kw.get("prompt_encoder"), kw["segment_example_logits"], kw.get("embedding_extraction"),
+                         kw.get("classification_levels", 1), bool(kw.get("conv_classification", False)))
     check_extraction(kw.get("embedding_extraction"), kw["embeddings_per_example"], kw.get("embed_dim", 256))
     check_levels(kw.get("classification_levels", 1), kw["segment_example_logits"])
     kw["conv_classification"] = bool(kw.get("conv_classification", False))

@@ -234,6 +234,116 @@ __global__ __launch_bounds__(256) void mask_embed_kernel(MaskEmbedArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// la_mask_embed_pooled: the dense prompts of a support's C classes summed into ONE slab per support image
+// (PromptImagePoolEncoder.forward, prompt_encoder.py:880-896).  a.P = S * C pairs, a block owns ME_PIX pixels of support blockIdx.y.
+// The 1x1 conv commutes with the resample AND with the class sum: the 16-channel resampled hidden maps of the valid classes are
+// summed first (ascending c, in registers: a fixed order, no atomics), W6 is applied once per pixel, and everything that does not
+// depend on the pixel - n_valid b6 + n_invalid not_a_mask + sum_c class_enc[c] - is one D-vector per support.  With C = 1 every
+// operation is la_mask_embed's, in its order.
+// ---------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void mask_embed_pooled_kernel(MaskEmbedArgs a) {
+  __shared__ float hb[ME_PIX][4][16];
+  const int hw = a.g * a.g;
+  const int sup = blockIdx.y;
+  const int pix0 = blockIdx.x * ME_PIX;
+  const int tid = threadIdx.x;
+  const bool have_mask = a.masks != nullptr;
+  const int hg = a.Hm >> 2;
+  int nvalid = 0;                                      // block-uniform: the flags of this support's C classes
+  if (have_mask)
+    for (int c = 0; c < a.C; ++c) nvalid += (a.flags == nullptr || a.flags[sup * a.C + c] != 0) ? 1 : 0;
+  if (nvalid > 0 && tid < ME_PIX * 4) {
+    const int pl = tid >> 2, tap = tid & 3;
+    const int pix = pix0 + pl;
+    float wgt = 0.f;
+    int iy = 0, ix = 0;
+    if (pix < hw) {                                    // the taps are the same for every class
+      const int oy = pix / a.g, ox = pix % a.g;
+      if (hg == a.g) {
+        wgt = tap == 0 ? 1.f : 0.f;
+        iy = oy; ix = ox;
+      } else {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        bilinear_tap(oy, hg, a.g, y0, y1, ly);
+        bilinear_tap(ox, hg, a.g, x0, x1, lx);
+        iy = (tap & 2) ? y1 : y0;
+        ix = (tap & 1) ? x1 : x0;
+        wgt = ((tap & 2) ? ly : 1.f - ly) * ((tap & 1) ? lx : 1.f - lx);
+      }
+    }
+    float acc[16];
+#pragma unroll
+    for (int o = 0; o < 16; ++o) acc[o] = 0.f;
+    if (wgt != 0.f)
+      for (int c = 0; c < a.C; ++c) {
+        const int p = sup * a.C + c;
+        if (a.flags != nullptr && a.flags[p] == 0) continue;
+        float h[16];
+        mask_hidden16(a, a.masks + (size_t)p * a.Hm * a.Hm, iy, ix, h);
+#pragma unroll
+        for (int o = 0; o < 16; ++o) acc[o] += h[o] * wgt;
+      }
+#pragma unroll
+    for (int o = 0; o < 16; ++o) hb[pl][tap][o] = acc[o];
+  }
+  __syncthreads();
+  if (nvalid > 0)
+    for (int i = tid; i < ME_PIX * 16; i += 256) {
+      const int pl = i >> 4, o = i & 15;
+      hb[pl][0][o] = (hb[pl][0][o] + hb[pl][1][o]) + (hb[pl][2][o] + hb[pl][3][o]);
+    }
+  __syncthreads();
+  T* s16 = reinterpret_cast<T*>(a.src16);
+  T* spe16 = reinterpret_cast<T*>(a.srcpe16);
+  const int ninvalid = have_mask ? a.C - nvalid : 0;
+  for (int d = tid; d < a.D; d += 256) {
+    float w6r[16];
+    // the per-support vector, in this order: n_valid b6, + n_invalid not_a_mask (or C no_mask without mask prompts), + class_enc[0],
+    // + class_enc[1], ...
+    float v0 = 0.f;
+    if (nvalid > 0) {
+      v0 = (float)nvalid * a.b6[d];
+#pragma unroll
+      for (int o = 0; o < 16; ++o) w6r[o] = a.w6[d * 16 + o];
+    } else {
+#pragma unroll
+      for (int o = 0; o < 16; ++o) w6r[o] = 0.f;
+    }
+    if (!have_mask) v0 = (float)a.C * a.no_mask[d];
+    else if (ninvalid > 0) v0 += (float)ninvalid * a.not_a_mask[d];
+    float sv[ME_PIX];                                  // requested up front, as in mask_embed_kernel
+#pragma unroll
+    for (int pl = 0; pl < ME_PIX; ++pl)
+      sv[pl] = (a.support && pix0 + pl < hw) ? a.support[((size_t)sup * hw + pix0 + pl) * a.D + d] : 0.f;
+    if (a.class_enc)
+      for (int c = 0; c < a.C; ++c) v0 += a.class_enc[c * a.D + d];
+#pragma unroll
+    for (int pl = 0; pl < ME_PIX; ++pl) {
+      const int pix = pix0 + pl;
+      if (pix >= hw) continue;
+      float v = v0;
+      if (nvalid > 0) {
+#pragma unroll
+        for (int o = 0; o < 16; ++o) v += w6r[o] * hb[pl][0][o];
+      }
+      v += sv[pl];
+      const size_t o = ((size_t)sup * hw + pix) * a.D + d;
+      a.src32[o] = v;
+      if (a.split) {
+        const size_t r2 = ((size_t)sup * hw + pix) * 2 * a.D;
+        if (s16) store_split<T>(s16 + r2, a.D, d, v);
+        if (spe16) store_split<T>(spe16 + r2, a.D, d, v + a.pe[(size_t)pix * a.D + d]);
+      } else {
+        if (s16) s16[o] = (T)v;
+        if (spe16) spe16[o] = (T)(v + a.pe[(size_t)pix * a.D + d]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // small attentions of the decoder (common.py:57-148): fp32, head dims 4..64, one side tiny.
 //   q [B, Nq, ldq] (head h at column h*HD), k/v [B, Nk, ld], out16/out32 [B, Nq, ldo].
 // ---------------------------------------------------------------------------------------------------------
@@ -680,6 +790,28 @@ extern "C" int la_mask_embed(const float* masks, const int* flags, int P, int C,
   else if (dt == LA_F32) hipLaunchKernelGGL(mask_embed_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else LA_CHECK_ARG(false, "la_mask_embed: bad dtype %d", dt);
   LA_CHECK_LAUNCH("la_mask_embed");
+  return 0;
+}
+
+extern "C" int la_mask_embed_pooled(const float* masks, const int* flags, int S, int C, int Hm, int g, int D, const float* const* w,
+                                    const float* support, const float* class_enc, const float* pe, float* src32, void* src16,
+                                    void* srcpe16, int dt, void* stream) {
+  LA_CHECK_ARG(w && pe && src32, "la_mask_embed_pooled: null pointer");
+  LA_CHECK_ARG(S > 0 && S <= 65535 && C >= 1 && g > 0 && D > 0, "la_mask_embed_pooled: bad shape (S %d, C %d, g %d, D %d)", S, C, g, D);
+  LA_CHECK_ARG(!masks || (Hm > 0 && (Hm % 4) == 0), "la_mask_embed_pooled: mask side %d must be a multiple of 4", Hm);
+  LA_CHECK_ARG(dt == LA_F16 || dt == LA_F16X2 || dt == LA_BF16 || dt == LA_F32, "la_mask_embed_pooled: bad dtype %d", dt);
+  MaskEmbedArgs a;
+  a.masks = masks; a.flags = flags; a.P = S * C; a.C = C; a.Hm = Hm; a.g = g; a.D = D;
+  a.w0 = w[0]; a.b0 = w[1]; a.g1 = w[2]; a.be1 = w[3]; a.w3 = w[4]; a.b3 = w[5]; a.g4 = w[6]; a.be4 = w[7]; a.w6 = w[8]; a.b6 = w[9];
+  a.not_a_mask = w[10]; a.no_mask = w[11];
+  a.support = support; a.class_enc = class_enc; a.pe = pe; a.src32 = src32; a.src16 = src16; a.srcpe16 = srcpe16;
+  a.split = dt == LA_F16X2 ? 1 : 0;
+  const int hw = g * g;
+  dim3 grid((hw + ME_PIX - 1) / ME_PIX, S);
+  if (dt == LA_F16 || dt == LA_F16X2) hipLaunchKernelGGL(mask_embed_pooled_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (dt == LA_BF16) hipLaunchKernelGGL(mask_embed_pooled_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(mask_embed_pooled_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  LA_CHECK_LAUNCH("la_mask_embed_pooled");
   return 0;
 }
 

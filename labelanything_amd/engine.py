@@ -1204,7 +1204,8 @@ class LamEngine:
                        selected_rows: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """support32: [B*M*hw, D] NHWC fp32.  Returns class_embeddings (B,C,D), class_examples_embeddings (B,M,C,D),
         class_examples_src (P, hw, D) NHWC.  With cfg.pool_side = k > 1 the examples are the M k k region means and ``flag_examples``
-        comes back repeated to (B, M k k, C), as the reference's result dictionary carries it."""
+        comes back repeated to (B, M k k, C), as the reference's result dictionary carries it.  With cfg.prompt_encoder = "TokenPool" the
+        stream has one slab per support image and class_examples_src is (B*M, hw, D) (``_token_pool``)."""
         cfg, w, p = self.cfg, self.w32, self.p
         pe_ = "prompt_encoder"
         d = cfg.embed_dim
@@ -1229,6 +1230,8 @@ class LamEngine:
             sp2 = self.f32("pe.sparse_ce", (pcount * ns, d))
             L.add_cast(sp, ce_rows, c * ns, out32=sp2, dt=self.ddti)
             sp = sp2
+        if cfg.prompt_encoder == "TokenPool":
+            return self._token_pool(support32, sp, class_enc, b, m, c, ns, g, masks, flag_examples)
         # dense stream
         pe32 = self.dense_pe(g)
         src32 = self.f32("pe.src32", (pcount * hw, d))
@@ -1266,6 +1269,14 @@ class LamEngine:
         else:
             emb = self.f32("pe.emb", (pcount, d))
             L.colmean(src32, pcount, hw, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
+        emb, cls = self._merge_and_class_mean(emb, fe, b, m, c)
+        return {"flag_examples": flag_examples, "class_embeddings": cls,
+                "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(pcount, hw, d)}
+
+    def _merge_and_class_mean(self, emb: Tensor, fe: Tensor, b: int, m: int, c: int):
+        """prompt_class_information_merge (the three optional merge attentions) and the flag-masked mean over the M examples
+        (prompt_encoder.py:693-745) -> (emb [B*M*C, D], class_embeddings (B, C, D))."""
+        cfg, d, pe_ = self.cfg, self.cfg.embed_dim, "prompt_encoder"
         if cfg.class_attention:
             emb = self.attention_mlp_block(pe_ + ".class_attention", emb, b * m, c, "pe.ca")
         if cfg.example_attention:
@@ -1276,8 +1287,41 @@ class LamEngine:
             emb = self.attention_mlp_block(pe_ + ".class_example_attention", emb, b, m * c, "pe.cea")
         cls = torch.empty(b, c, d, device=self.dev, dtype=torch.float32)
         L.class_mean(emb, fe, b, m, c, d, cls)
+        return emb, cls
+
+    def _token_pool(self, support32: Tensor, sp: Tensor, class_enc: Optional[Tensor], b: int, m: int, c: int, ns: int, g: int, masks,
+                    flag_examples: Tensor) -> Dict[str, Tensor]:
+        """prompt_encoder = "TokenPool" (PromptImagePoolEncoder.forward, prompt_encoder.py:880-915).  sp: the sparse tokens [B*M*C*Ns, D]
+        in (c, n) order per support, class rows added.  ONE stream slab per support image - support + the class sum of the dense prompts
+        (la_mask_embed_pooled) - goes through the two-way transformer with the C Ns tokens of the support; BOTH outputs are used: an
+        example's embedding is the mean of its class's Ns output tokens, and class_examples_src is the image side, (B*M, hw, D)."""
+        cfg, p, pe_ = self.cfg, self.p, "prompt_encoder"
+        d, hw, s, nt, pcount = cfg.embed_dim, g * g, b * m, c * ns, b * m * c
+        pe32 = self.dense_pe(g)
+        src32 = self.f32("pe.src32", (s * hw, d))
+        fused = self.fused_ok(nt)           # above 32 tokens a support the unfused chain runs, on the GEMM-operand copies
+        src16 = None if fused else self.ibuf("pe.src16", s * hw, d)
+        srcpe16 = None if fused else self.ibuf("pe.srcpe16", s * hw, d)
+        mk = mf = None
+        hm = 0
+        if masks is not None:
+            mk, mf = masks
+            if mk.shape[-1] != mk.shape[-2]:
+                raise ValueError("prompt masks must be square")
+            hm = mk.shape[-1]
+            mk = self.h2d(mk, torch.float32).reshape(pcount, hm, hm).contiguous()
+            mf = self.h2d(mf.reshape(pcount), torch.int32).contiguous()
+        L.mask_embed_pooled(mk, mf, s, c, hm, g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16, srcpe16, self.idti)
+        t32, _ = self.two_way(pe_ + ".transformer", sp, s, nt, src32, src16, srcpe16, hw, pe32, "pe.tw", want_tokens=True)
+        if ns == 1:
+            emb = t32
+        else:                               # "(b m) (c n) d -> b m c d", mean over n
+            emb = self.f32("pe.emb", (pcount, d))
+            L.colmean(t32, pcount, ns, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
+        fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
+        emb, cls = self._merge_and_class_mean(emb, fe, b, m, c)
         return {"flag_examples": flag_examples, "class_embeddings": cls,
-                "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(pcount, hw, d)}
+                "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(s, hw, d)}
 
     def extract_embeddings(self, src32: Tensor, b: int, m: int, c: int, hw: int) -> Tensor:
         """embedding_extraction = "cross_attention" (EmbeddingTransformer.forward, prompt_encoder.py:289-313): n learned queries per (b, c)

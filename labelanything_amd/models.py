@@ -21,7 +21,8 @@ from typing import Any, Dict, Optional
 import torch
 from torch import nn
 
-from .config import LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_levels, config_from_kwargs, resolve_examples
+from .config import (LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_levels, check_prompt_encoder, config_from_kwargs,
+                     resolve_examples)
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
 from . import _lib as L
@@ -84,13 +85,17 @@ class Lam(nn.Module):
                  decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT,
                  segment_example_logits: Optional[bool] = None, embeddings_per_example: Optional[int] = None,
                  classification_levels: Optional[int] = None, classification_layer_downsample_rate: Optional[int] = None,
-                 conv_classification: Optional[bool] = None, embedding_extraction: Optional[str] = None):
+                 conv_classification: Optional[bool] = None, embedding_extraction: Optional[str] = None,
+                 prompt_encoder: Optional[str] = None):
         """segment_example_logits / embeddings_per_example: the per-example family on top of ``cfg`` (resolved as build_lam.py:145-148
         does); classification_levels: 2 adds the two-level head (mask_decoder.py:204,345-362); classification_layer_downsample_rate /
         conv_classification: the decoder's channel widths and the 5 x 5 prototype kernels (mask_decoder.py:198-271,299-307);
         embedding_extraction: "cross_attention" reads the per-example embeddings out of the stream with learned queries
-        (prompt_encoder.py:280-313).  Left at None they keep what ``cfg`` says."""
+        (prompt_encoder.py:280-313); prompt_encoder: "TokenPool" sums a support's dense prompts over its classes and takes the example
+        embeddings from the output tokens (prompt_encoder.py:830-915).  Left at None they keep what ``cfg`` says."""
         super().__init__()
+        if prompt_encoder is not None:
+            cfg = dataclasses.replace(cfg, prompt_encoder=prompt_encoder)
         if embedding_extraction is not None:
             cfg = dataclasses.replace(cfg, embedding_extraction=embedding_extraction)
         if classification_layer_downsample_rate is not None:
@@ -108,6 +113,8 @@ class Lam(nn.Module):
         if cfg.embedding_extraction is not None and not cfg.segment_example_logits:     # (a cfg built by hand: resolve as the builder does)
             seg, epe = resolve_examples(True, cfg.embeddings_per_example)
             cfg = dataclasses.replace(cfg, segment_example_logits=seg, embeddings_per_example=epe)
+        check_prompt_encoder(cfg.prompt_encoder, cfg.segment_example_logits, cfg.embedding_extraction, cfg.classification_levels,
+                             cfg.conv_classification)
         check_extraction(cfg.embedding_extraction, cfg.embeddings_per_example, cfg.embed_dim)
         check_levels(cfg.classification_levels, cfg.segment_example_logits)
         check_classification(cfg.classification_layer_downsample_rate, cfg.conv_classification, cfg.segment_example_logits,
@@ -739,9 +746,10 @@ class LabelAnything(nn.Module, PyTorchModelHubMixin):
                  fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
                  transformer_keys_are_images=True, transformer_feature_size=None, class_encoder=None,
                  segment_example_logits=False, dropout: float = 0.0, binary=False, custom_preprocess=True,
-                 classification_levels: int = 1, conv_classification: bool = False, embedding_extraction: Optional[str] = None):
-        """classification_levels, conv_classification and embedding_extraction are not arguments of the reference's class (its builders
-        take them, build_lam.py:118-127,251): they are accepted here so that such a model round-trips through config.json.  Like the
+                 classification_levels: int = 1, conv_classification: bool = False, embedding_extraction: Optional[str] = None,
+                 prompt_encoder: Optional[str] = None):
+        """classification_levels, conv_classification, embedding_extraction and prompt_encoder are not arguments of the reference's class
+        (its builders take them, build_lam.py:118-127,251): they are accepted here so that such a model round-trips through config.json.  Like the
         reference's class this one takes segment_example_logits only, so embedding_extraction comes with one learned query here; the
         build_lam functions and Lam take embeddings_per_example."""
         super().__init__()

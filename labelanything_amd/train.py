@@ -10,7 +10,8 @@ encoder, mask decoder, class encoder = 10.14 M parameters for the MAE-480 geomet
 mask_decoder.py:316-363, lam.py:383-453) as a composition of ``autograd_ops`` - every arithmetic node runs a HIP kernel in both
 directions, torch.autograd records the graph and moves data.  The image encoder runs through the inference engine without a graph.
 Parameters that the forward never touches (``prompt_encoder.transformer.final_attn_token_to_image``, ``norm_final_attn``: dead in
-the reference too, which therefore needs ``find_unused_parameters``) keep the zeros of the flat gradient buffer.
+the reference too, which therefore needs ``find_unused_parameters``) keep the zeros of the flat gradient buffer.  With
+``prompt_encoder="TokenPool"`` the example embeddings are that transformer's output tokens and both are live.
 """
 from __future__ import annotations
 
@@ -247,6 +248,17 @@ class DecoderGraph:
             dense = self.mask_embedding(mk.reshape(p, mk.shape[-2], mk.shape[-1]), mf, p, g)
         else:
             dense = self.w[pe_ + ".no_mask_embed.weight"].view(1, d).expand(p * hw, d)
+        if cfg.prompt_encoder == "TokenPool":
+            # PromptImagePoolEncoder (prompt_encoder.py:880-915): one slab per support = support + the class sum of (dense + class row);
+            # the C Ns tokens of a support run together and an example's embedding is the mean of its class's output tokens.  The sum
+            # is taken on the D-wide maps: mask_embedding hands out nothing narrower (the fused forward kernel sums the 16-channel maps)
+            dense = dense.contiguous()
+            if ce is not None:
+                dense = _AddPerGroup.apply(dense, ce.repeat(b * m, 1), p, hw)
+            src = A.add_rows(support, dense.view(b * m, c, hw, d).sum(dim=1).reshape(b * m * hw, d))
+            toks, keys = self.two_way(pe_ + ".transformer", src, self.dense_pe(g), sp, b * m, c * ns, hw, want_tokens=True)
+            emb = A.mean_rows(toks, p, ns) if ns > 1 else toks
+            return self._merge_and_class_mean(emb, keys, flag_examples, b, m, c)
         sup = support.view(b * m, 1, hw, d).expand(b * m, c, hw, d).reshape(p * hw, d)                      # every class sees its support
         src = A.add_rows(sup, dense.contiguous())
         if ce is not None:
@@ -262,6 +274,11 @@ class DecoderGraph:
             flag_examples = flag_examples.reshape(b, m // (k * k), c).repeat_interleave(k * k, dim=1)
         else:
             emb = A.mean_rows(keys, p, hw)
+        return self._merge_and_class_mean(emb, keys, flag_examples, b, m, c)
+
+    def _merge_and_class_mean(self, emb: Tensor, keys: Tensor, flag_examples: Tensor, b: int, m: int, c: int) -> Dict[str, Tensor]:
+        """prompt_class_information_merge and the flag-masked mean over the examples (prompt_encoder.py:693-745)."""
+        cfg, pe_, d, p = self.cfg, "prompt_encoder", self.cfg.embed_dim, b * m * c
         if cfg.class_attention:
             emb = self.attention_mlp_block(pe_ + ".class_attention", emb, b * m, c)
         if cfg.example_attention:
@@ -427,6 +444,8 @@ class LamTrainer:
         # tensors the forward never reaches (dead in the reference too, prompt_encoder.py:683) go to the tail of the flat buffer so
         # that the per-step "received a gradient" spans of FlatAdamW.step stay one contiguous run
         dead = ("prompt_encoder.transformer.final_attn_token_to_image.", "prompt_encoder.transformer.norm_final_attn.")
+        if lam.cfg.prompt_encoder == "TokenPool":       # the example embeddings are the transformer's OUTPUT tokens: both are live
+            dead = ()
         if isinstance(loss, LabelAnythingLoss):
             loss.to(lam._device())
             loss_named = [("loss." + k, p) for k, p in loss.named_parameters()]
