@@ -480,6 +480,16 @@ int la_twoway_i2t(float* img, const void* wq_hi, const void* wq_lo, const float*
                   const void* wo_lo, const float* bo, const float* gamma, const float* beta, float eps, int G, int hw, int nt, int D,
                   int heads, void* stream);
 
+/* ---- fused stream MLP of the OneWayTransformer's block (models/transformer.py:149-152, MLPBlock common.py:19-37), IN PLACE on the fp32
+ * stream:  x <- LN(x + relu(x W1^T + b1) W2^T + b2).  x fp32 [rows, D]; W1 planes fp16 [H, D], W2 planes fp16 [D, H] (hi = rn(W),
+ * lo = rn(W - hi), as the two-way kernels'); b1 [H], b2 / gamma / beta [D] fp32.  x and the hidden activations are split into fp16 planes
+ * on the fly (hi.hi + lo.hi + hi.lo, fp32 accumulation); the hidden layer stays on chip.  An output row depends on its own input row and
+ * the weights only - not on its position, the row count or the workgroup that takes it; no atomics.  D = 256, H a multiple of 128 from 128
+ * to 4096, rows >= 1 (any tail): la_stream_mlp_ok(D, H) says whether a shape is taken; everything else is refused before any write. ---- */
+int la_stream_mlp_ok(int D, int H);
+int la_stream_mlp(float* x, const void* w1_hi, const void* w1_lo, const float* b1, const void* w2_hi, const void* w2_lo, const float* b2,
+                  const float* gamma, const float* beta, float eps, long rows, int D, int H, void* stream);
+
 /* ---- image-encoder backward (SURVEY 8f row 1 with a TRAINABLE backbone: parameters/trainval/coco20i/mae_noembs.yaml has no
  * freeze_backbone, so models/lam.py:321-347 hands every ViT parameter to the optimizer).  Plain HF ViT attention, head_dim 64. ---- */
 

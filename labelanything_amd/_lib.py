@@ -75,6 +75,7 @@ EXPORTS = [
     "la_extract_pool_plan", "la_extract_pool", "la_extract_fold", "la_extract_unfold",
     "la_mfma_shape_probe",
     "la_mask_embed_pooled",
+    "la_stream_mlp", "la_stream_mlp_ok",
 ]
 
 
@@ -792,6 +793,24 @@ def twoway_i2t(img, wq, peq, k, v, wo, bo, gamma, beta, eps: float, groups: int,
     _check(lib().la_twoway_i2t(_ptr(img), _ptr(wq[0]), _ptr(wq[1]), _ptr(peq), _ptr(k), _ptr(v), _ptr(wo[0]), _ptr(wo[1]), _ptr(bo),
                                _ptr(gamma), _ptr(beta), C.c_float(eps), C.c_int(groups), C.c_int(hw), C.c_int(nt), C.c_int(img.shape[1]),
                                C.c_int(heads), _stream()), "la_twoway_i2t")
+
+
+def stream_mlp_ok(d: int, h: int) -> bool:
+    return bool(lib().la_stream_mlp_ok(C.c_int(d), C.c_int(h)))
+
+
+def stream_mlp(x, w1, b1, w2, b2, gamma, beta, eps: float, rows: Optional[int] = None, d: Optional[int] = None,
+               h: Optional[int] = None) -> None:
+    """x <- LN(x + relu(x W1^T + b1) W2^T + b2) in place on the fp32 stream x [rows, D].  w1 / w2: (hi, lo) fp16 plane pairs [H, D] /
+    [D, H].  rows / d / h default to the tensors' shapes (the refusal tests pass them)."""
+    for t in (x, b1, b2, gamma, beta):
+        if t is not None:
+            _f32c(t)
+    rows = (x.shape[0] if x is not None else 0) if rows is None else rows
+    d = x.shape[1] if d is None else d
+    h = b1.shape[0] if h is None else h
+    _check(lib().la_stream_mlp(_ptr(x), _ptr(w1[0]), _ptr(w1[1]), _ptr(b1), _ptr(w2[0]), _ptr(w2[1]), _ptr(b2), _ptr(gamma), _ptr(beta),
+                               C.c_float(eps), C.c_long(rows), C.c_int(d), C.c_int(h), _stream()), "la_stream_mlp")
 
 
 # ---- image-encoder backward ---------------------------------------------------------------------------

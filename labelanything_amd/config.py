@@ -65,8 +65,9 @@ def register_encoder(name: str, spec: EncoderSpec) -> None:
 class LamConfig:
     """Keyword surface of ``LabelAnything.__init__`` (build_lam.py:470-498), on-path subset.
 
-    Off-path switches (few_type=Affinity, OneWay/Identity fusion, binary, pyramids,
+    Off-path switches (few_type=Affinity, Identity fusion, binary, pyramids,
     class_embedding_dim) are accepted only at their default value; anything else raises NotImplementedError.
+    ``fusion_transformer`` takes "TwoWayTransformer" and, for models without an image encoder, "OneWayTransformer".
     ``embedding_extraction`` takes None and "cross_attention"; every other value ("pooler" ...) raises NotImplementedError.
     """
 
@@ -114,6 +115,12 @@ class LamConfig:
     # C Ns tokens of the support, and an example's embedding is the mean of its class's OUTPUT tokens - so final_attn_token_to_image and
     # norm_final_attn, dead in the plain prompt encoder, are live.  Adds no parameters.
     prompt_encoder: Optional[str] = None
+    # "OneWayTransformer": the mask decoder's transformer (and only it: the prompt encoder's two-way transformer is hard-wired,
+    # build_lam.py:198-205,238-275) leaves the class tokens as they are and runs, per layer, image -> token cross attention + norm1 and a
+    # dec_mlp-wide ReLU MLP + norm2 on EVERY pixel row (transformer.py:26-154; parameters/trainval/Ablations/mae_transformer.yaml).
+    # mask_decoder.transformer.* is then 36 tensors; norm3 of a block is a parameter its forward never applies.  Built for models
+    # without an image encoder (use_vit=False), which is what every reference recipe with this switch builds.
+    fusion_transformer: str = "TwoWayTransformer"
     # fixed in the reference for this path
     dec_heads: int = 8
     dec_mlp: int = 2048
@@ -144,6 +151,10 @@ class LamConfig:
         return ENCODER_SPECS[self.encoder]
 
     @property
+    def one_way(self) -> bool:
+        return self.fusion_transformer == "OneWayTransformer"
+
+    @property
     def pool_side(self) -> int:
         """k of the k x k adaptive average pool: floor(sqrt(embeddings_per_example)) (prompt_encoder.py:727); 1 = the plain mean."""
         e = self.embeddings_per_example
@@ -160,7 +171,7 @@ _OFF_PATH_DEFAULTS = dict(
     class_embedding_dim=None,
     encoder_attention_downsample_rate=2, decoder_attention_downsample_rate=2,
     use_support_features_in_prompt_encoder=True,
-    fusion_transformer="TwoWayTransformer", few_type="Prototype", class_fusion="sum",
+    few_type="Prototype", class_fusion="sum",
     transformer_keys_are_images=True, transformer_feature_size=None,
     dropout=0.0, binary=False,
 )
@@ -249,6 +260,32 @@ def check_prompt_encoder(prompt_encoder, segment_example_logits, embedding_extra
                                   "combines them")
 
 
+def check_fusion_transformer(fusion_transformer, has_image_encoder, segment_example_logits, embedding_extraction, levels,
+                             conv_classification, rate, prompt_encoder) -> None:
+    """The one check of ``fusion_transformer`` (config_from_kwargs and Lam), on the RESOLVED segment_example_logits."""
+    if fusion_transformer == "TwoWayTransformer":
+        return
+    if fusion_transformer != "OneWayTransformer":
+        # IdentityTransformer included: the reference's MaskDecoderLam.forward calls its transformer with four arguments and
+        # IdentityTransformer.forward takes three (transformer.py:21), so the reference itself cannot run it
+        raise NotImplementedError(f"fusion_transformer={fusion_transformer!r} is an off-path ablation of the reference; only "
+                                  f"'TwoWayTransformer' and 'OneWayTransformer' are built")
+    if has_image_encoder:
+        raise NotImplementedError("fusion_transformer='OneWayTransformer' is built for models without an image encoder (use_vit=False, "
+                                  "the reference's lam_no_vit, which every reference recipe with this switch builds); with an image "
+                                  "encoder in the model it is an off-path ablation still")
+    pairs = (("segment_example_logits / embeddings_per_example", segment_example_logits),
+             ("embedding_extraction", embedding_extraction is not None),
+             ("classification_levels=2", levels == 2),
+             ("conv_classification", conv_classification),
+             (f"classification_layer_downsample_rate={rate}", rate != 8),
+             (f"prompt_encoder={prompt_encoder!r}", prompt_encoder is not None))
+    for name, on in pairs:
+        if on:
+            raise NotImplementedError(f"fusion_transformer='OneWayTransformer' together with {name} is not built: no reference recipe "
+                                      f"combines them")
+
+
 def config_from_kwargs(**kw) -> LamConfig:
     """Build a LamConfig from reference-style kwargs, rejecting off-path ablation switches."""
     kw = dict(kw)
@@ -268,6 +305,10 @@ def config_from_kwargs(**kw) -> LamConfig:
                                                                                   kw.get("embeddings_per_example"))
     check_prompt_encoder(kw.get("prompt_encoder"), kw["segment_example_logits"], kw.get("embedding_extraction"),
                          kw.get("classification_levels", 1), bool(kw.get("conv_classification", False)))
+    check_fusion_transformer(kw.get("fusion_transformer", "TwoWayTransformer"),
+                             bool(kw.get("use_vit", True)) and kw.get("encoder", "vit_b") is not None, kw["segment_example_logits"],
+                             kw.get("embedding_extraction"), kw.get("classification_levels", 1), bool(kw.get("conv_classification", False)),
+                             kw.get("classification_layer_downsample_rate", 8), kw.get("prompt_encoder"))
     check_extraction(kw.get("embedding_extraction"), kw["embeddings_per_example"], kw.get("embed_dim", 256))
     check_levels(kw.get("classification_levels", 1), kw["segment_example_logits"])
     kw["conv_classification"] = bool(kw.get("conv_classification", False))

@@ -171,13 +171,14 @@ def resolve_precise(cfg: LamConfig, precise, dtype: torch.dtype = torch.float16)
 class LamEngine:
     def __init__(self, cfg: LamConfig, weights: Dict[str, Tensor], device: torch.device, dtype: torch.dtype = torch.float16,
                  decoder_dtype: Optional[torch.dtype] = torch.float32, precise=PRECISE_DEFAULT, fuse_twoway: bool = True,
-                 scope: str = "all"):
+                 scope: str = "all", fuse_oneway: bool = True):
         """dtype: MFMA operand type of the image encoder and necks (>99% of the FLOPs).  decoder_dtype: operand type of the
         prompt encoder / mask decoder GEMMs - fp32 by default (exact-fp32 MFMA; ~1% of the FLOPs but the stage where
         16-bit operand rounding would dominate the logit error), or None to follow ``dtype``.  precise: encoder GEMM groups
         that run in split precision (see PRECISE_DEFAULT); () = every encoder GEMM with plain 16-bit operands.
         fuse_twoway: explicit constructor switch for A/B measurements (tools/) of the fused two-way kernels; the product never reads the
-        environment.  scope="encoder": only the image encoder's weights
+        environment.  fuse_oneway: the same for the OneWayTransformer of the mask decoder (la_twoway_i2t + la_stream_mlp per layer; False
+        keeps the GEMM + attention + norm chain).  scope="encoder": only the image encoder's weights
         are packed (the trainer-private engine of train_encoder.HfEncoderGraph, re-packed after every optimizer step by
         ``repack_encoder``)."""
         if scope not in ("all", "encoder"):
@@ -208,6 +209,8 @@ class LamEngine:
         # the image side of the two-way transformers runs in the fused kernels (one read / one read + write of the stream per
         # attention, csrc/twoway.hip) for the published decoder geometry; fuse_twoway=False keeps the GEMM + attention + norm chain
         self.fuse_twoway = bool(fuse_twoway) and cfg.embed_dim in (256, 512) and cfg.dec_heads == 8 and decoder_dtype == torch.float32
+        # fusion_transformer = "OneWayTransformer": per layer la_twoway_i2t (with norm1) + la_stream_mlp (with norm2), where both take the shape
+        self.fuse_oneway = bool(fuse_oneway) and self.fuse_twoway and cfg.one_way and L.stream_mlp_ok(cfg.embed_dim, cfg.dec_mlp)
         # attention without V^T copies / window buffers (la_attn_fwd_rows) wherever its forms cover the block: plain attention, the 64 x 64
         # rel-pos grid, 16-slot windows; False keeps the V^T epilogue + window scatter path (A/B, and what the other geometries still use)
         self.attn_rows = True
@@ -472,6 +475,21 @@ class LamEngine:
             self._pack_mlp(lp + ".mlp")
         self._pack_attn(pre + ".final_attn_token_to_image", "none")
 
+    def _pack_one_way(self, pre: str) -> None:
+        """OneWayTransformer (transformer.py:26-154): per layer the image -> token attention and the stream MLP.  norm3 is never read."""
+        w, p = self.w32, self.p
+        for l in range(2):
+            lp = f"{pre}.layers.{l}"
+            self._pack_attn(lp + ".cross_attn_image_to_token", "none")
+            self._pack_mlp(lp + ".mlp")
+            for n in ("lin1", "lin2"):
+                wt = w[f"{lp}.mlp.{n}.weight"]
+                if self.isplit:
+                    p[f"{lp}.mlp.{n}.ws"] = self._split3(wt)
+                if self.fuse_oneway:                # fp16 plane pair of la_stream_mlp (csrc/stream_mlp.hip)
+                    hi = wt.to(torch.float16).contiguous()
+                    p[f"{lp}.mlp.{n}.planes"] = (hi, (wt - hi.float()).to(torch.float16).contiguous())
+
     def _pack_conv_neck(self, pre: str) -> None:
         w = self.w32
         cast = (lambda t: t.contiguous()) if "neck" in self.precise else self._h
@@ -554,7 +572,10 @@ class LamEngine:
         if cfg.embedding_extraction == "cross_attention":
             self._pack_extraction(pe + ".embedding_extraction")
         md = "mask_decoder"
-        self._pack_two_way(md + ".transformer")
+        if cfg.one_way:
+            self._pack_one_way(md + ".transformer")
+        else:
+            self._pack_two_way(md + ".transformer")
         for i in range(3):
             p[f"{md}.class_mlp.{i}.w"] = self._hd(w[f"{md}.class_mlp.layers.{i}.weight"])
         # ConvTranspose2d weight (Cin, Cout, 2, 2) -> GEMM weight [(ky, kx, cout), cin]
@@ -1159,6 +1180,74 @@ class LamEngine:
         self.dln(tnew, pre + ".norm_final_attn", 1e-5, out32=t32, out16=t16)
         return t32, t16
 
+    # la_stream_mlp against the lin1 -> lin2 (+ residual) -> LayerNorm chain on the same buffers (tools/bench_oneway.py, part (a);
+    # profiles/r12_oneway.md has the table).  A 128-row tile takes 223 us whatever the row count up to 32 768 rows (one workgroup per CU);
+    # the chain takes 186 us at 900 rows, 212 us at 4 096, 253 us at 7 200 (kernel 1.14x faster, spreads apart), 610 us at 32 768 (2.5x).
+    # The fused kernel is used from the smallest measured row count at which it wins, the chain below.
+    ONEWAY_MLP_MIN_ROWS = 7200
+
+    def oneway_fused(self, nt: int) -> bool:
+        return self.fuse_oneway and self.fused_ok(nt)
+
+    def oneway_mlp_fused(self, nt: int, rows: int) -> bool:
+        return self.oneway_fused(nt) and rows >= self.ONEWAY_MLP_MIN_ROWS
+
+    def one_way(self, pre: str, tok32: Tensor, groups: int, nt: int, img32: Tensor, img16, imgpe16, hw: int, pe32: Tensor, tag: str):
+        """OneWayTransformer (transformer.py:26-154).  tok32 [groups*nt, D] fp32: the tokens pass through untouched and are keys and values
+        of both layers WITHOUT a positional encoding and without a key mask (OneWayTransformer.forward never passes one on).  The image
+        side [groups*hw, D] is the fp32 stream, updated in place; per layer
+            img = norm1(img + attn(q = img + pe, k = v = tokens));    img = norm2(img + lin2(relu(lin1(img))))
+        Fused (``oneway_fused(nt)``): la_twoway_i2t + la_stream_mlp, two launches a layer - the MLP half on the chain below
+        ONEWAY_MLP_MIN_ROWS rows.  Otherwise the chain on the GEMM-operand copies img16 (x) and imgpe16 (x + pe), which the last norm
+        leaves up to date.  norm3 is never applied.  Returns (tokens32, tokens16) for class_mlp: the class embeddings themselves."""
+        w, p, cfg = self.w32, self.p, self.cfg
+        d = cfg.embed_dim
+        di = d // 2
+        r, ri = groups * nt, groups * hw
+        fused = self.oneway_fused(nt)
+        mlp_fused = self.oneway_mlp_fused(nt, ri)
+        t16 = self.dbuf(tag + ".t16", (r, d))
+        L.add_cast(tok32, out16=t16, dt=self.ddti)
+        if fused and not mlp_fused:
+            img16 = self.ibuf(tag + ".x16", ri, d)
+        for l in range(2):
+            lp = f"{pre}.layers.{l}"
+            ca = lp + ".cross_attn_image_to_token"
+            kt = self.f32(f"{tag}.tk{l}", (r, di))           # the tokens never change: k / v of both layers depend on the class embeddings alone
+            vtok = self.f32(f"{tag}.tv{l}", (r, di))
+            L.gemm(t16, p[ca + ".k_proj.w"], bias=w[ca + ".k_proj.bias"], out32=kt)
+            L.gemm(t16, p[ca + ".v_proj.w"], bias=w[ca + ".v_proj.bias"], out32=vtok)
+            if fused:       # q_proj + attention + out_proj + residual + norm1: one read and one write of the stream
+                L.twoway_i2t(img32, p[ca + ".q_proj.planes"], self.pe_table(ca + ".q_proj", pe32), kt, vtok, p[ca + ".out_proj.planes"],
+                             w[ca + ".out_proj.bias"], w[lp + ".norm1.weight"], w[lp + ".norm1.bias"], 1e-5, groups, hw, nt, cfg.dec_heads)
+            else:
+                qi = self.f32(tag + ".iq", (ri, di))
+                self.igemm(imgpe16, ca + ".q_proj.w", bias=w[ca + ".q_proj.bias"], out32=qi)
+                oi16 = self._attn_core(qi, kt, vtok, groups, hw, nt, di, tag + ".i2t", image_side=True)
+                self.igemm(oi16, ca + ".out_proj.w", bias=w[ca + ".out_proj.bias"], res=img32, out32=img32)
+                L.layernorm(img32, w[lp + ".norm1.weight"], w[lp + ".norm1.bias"], 1e-5, out32=img32, out16=img16, dt=self.idti)
+            if mlp_fused:   # lin1 + ReLU + lin2 + residual + norm2: the 2048-wide hidden layer never leaves the chip
+                L.stream_mlp(img32, p[lp + ".mlp.lin1.planes"], w[lp + ".mlp.lin1.bias"], p[lp + ".mlp.lin2.planes"], w[lp + ".mlp.lin2.bias"],
+                             w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5)
+                continue
+            if fused:
+                L.add_cast(img32, out16=img16, dt=self.idti)
+            if self.isplit:     # (a GEMM writes no plane pairs: the hidden layer goes through fp32)
+                h32 = self.f32(tag + ".mlp32", (ri, cfg.dec_mlp))
+                self.igemm(img16, lp + ".mlp.lin1.w", bias=w[lp + ".mlp.lin1.bias"], out32=h32, act=L.ACT_RELU)
+                hbuf = self.ibuf(tag + ".mlp", ri, cfg.dec_mlp)
+                L.add_cast(h32, out16=hbuf, dt=self.idti)
+            else:
+                hbuf = self.dbuf(tag + ".mlp", (ri, cfg.dec_mlp))
+                self.igemm(img16, lp + ".mlp.lin1.w", bias=w[lp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_RELU)
+            self.igemm(hbuf, lp + ".mlp.lin2.w", bias=w[lp + ".mlp.lin2.bias"], res=img32, out32=img32)
+            if fused:
+                L.layernorm(img32, w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5, out32=img32, dt=self.idti)
+            else:
+                L.layernorm(img32, w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5, out32=img32, out16=img16, out16_pe=imgpe16, pe=pe32,
+                            pe_mod=hw, dt=self.idti)
+        return tok32, t16
+
     # ------------------------------------------------------------------------------------------------
     # prompt encoder (prompt_encoder.py:564-827)
     # ------------------------------------------------------------------------------------------------
@@ -1394,7 +1483,7 @@ class LamEngine:
         c = class_emb.shape[1]
         pe32 = self.dense_pe(g)
         img32 = self.f32("md.img32", (b * hw, d))
-        fused = self.fused_ok(c)
+        fused = self.oneway_fused(c) if cfg.one_way else self.fused_ok(c)
         img16 = imgpe16 = None
         if fused:
             L.add_cast(query32, out32=img32, dt=L.LA_F32)
@@ -1404,7 +1493,10 @@ class LamEngine:
             L.add_cast(query32, out32=img32, out16=img16, dt=self.idti)
             L.add_cast(query32, pe32, hw, out16=imgpe16, dt=self.idti)
         tok = self.h2d(class_emb, torch.float32).reshape(b * c, d).contiguous()
-        t32, t16 = self.two_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.tw", want_tokens=True)
+        if cfg.one_way:
+            t32, t16 = self.one_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.ow")
+        else:
+            t32, t16 = self.two_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.tw", want_tokens=True)
         levels = cfg.classification_levels == 2
         if levels:
             # coarse level (mask_decoder.py:345-346): the transformer's fp32 tokens before class_mlp against the fp32 D-channel stream

@@ -21,7 +21,8 @@ from typing import Any, Dict, Optional
 import torch
 from torch import nn
 
-from .config import (LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_levels, check_prompt_encoder, config_from_kwargs,
+from .config import (LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_fusion_transformer, check_levels, check_prompt_encoder,
+                     config_from_kwargs,
                      resolve_examples)
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
@@ -86,14 +87,17 @@ class Lam(nn.Module):
                  segment_example_logits: Optional[bool] = None, embeddings_per_example: Optional[int] = None,
                  classification_levels: Optional[int] = None, classification_layer_downsample_rate: Optional[int] = None,
                  conv_classification: Optional[bool] = None, embedding_extraction: Optional[str] = None,
-                 prompt_encoder: Optional[str] = None):
+                 prompt_encoder: Optional[str] = None, fusion_transformer: Optional[str] = None):
         """segment_example_logits / embeddings_per_example: the per-example family on top of ``cfg`` (resolved as build_lam.py:145-148
         does); classification_levels: 2 adds the two-level head (mask_decoder.py:204,345-362); classification_layer_downsample_rate /
         conv_classification: the decoder's channel widths and the 5 x 5 prototype kernels (mask_decoder.py:198-271,299-307);
         embedding_extraction: "cross_attention" reads the per-example embeddings out of the stream with learned queries
         (prompt_encoder.py:280-313); prompt_encoder: "TokenPool" sums a support's dense prompts over its classes and takes the example
-        embeddings from the output tokens (prompt_encoder.py:830-915).  Left at None they keep what ``cfg`` says."""
+        embeddings from the output tokens (prompt_encoder.py:830-915); fusion_transformer: "OneWayTransformer" replaces the mask decoder's
+        transformer (transformer.py:26-154; models without an image encoder).  Left at None they keep what ``cfg`` says."""
         super().__init__()
+        if fusion_transformer is not None:
+            cfg = dataclasses.replace(cfg, fusion_transformer=fusion_transformer)
         if prompt_encoder is not None:
             cfg = dataclasses.replace(cfg, prompt_encoder=prompt_encoder)
         if embedding_extraction is not None:
@@ -115,6 +119,9 @@ class Lam(nn.Module):
             cfg = dataclasses.replace(cfg, segment_example_logits=seg, embeddings_per_example=epe)
         check_prompt_encoder(cfg.prompt_encoder, cfg.segment_example_logits, cfg.embedding_extraction, cfg.classification_levels,
                              cfg.conv_classification)
+        check_fusion_transformer(cfg.fusion_transformer, cfg.encoder_spec is not None, cfg.segment_example_logits, cfg.embedding_extraction,
+                                 cfg.classification_levels, cfg.conv_classification, cfg.classification_layer_downsample_rate,
+                                 cfg.prompt_encoder)
         check_extraction(cfg.embedding_extraction, cfg.embeddings_per_example, cfg.embed_dim)
         check_levels(cfg.classification_levels, cfg.segment_example_logits)
         check_classification(cfg.classification_layer_downsample_rate, cfg.conv_classification, cfg.segment_example_logits,

@@ -11,7 +11,8 @@ mask_decoder.py:316-363, lam.py:383-453) as a composition of ``autograd_ops`` - 
 directions, torch.autograd records the graph and moves data.  The image encoder runs through the inference engine without a graph.
 Parameters that the forward never touches (``prompt_encoder.transformer.final_attn_token_to_image``, ``norm_final_attn``: dead in
 the reference too, which therefore needs ``find_unused_parameters``) keep the zeros of the flat gradient buffer.  With
-``prompt_encoder="TokenPool"`` the example embeddings are that transformer's output tokens and both are live.
+``prompt_encoder="TokenPool"`` the example embeddings are that transformer's output tokens and both are live.  With
+``fusion_transformer="OneWayTransformer"`` the mask decoder's ``norm3`` tensors are dead in the same way.
 """
 from __future__ import annotations
 
@@ -180,6 +181,18 @@ class DecoderGraph:
                      A.add_rows(qs, self.attn(fin, A.add_rows(qs, tpe), None, None, groups, nt, hw, k=k_img, v=v_img)), 1e-5)
         return qs, keys
 
+    def one_way(self, pre: str, img: Tensor, pe: Tensor, tok: Tensor, groups: int, nt: int, hw: int):
+        """OneWayTransformer (transformer.py:26-154): img [groups*hw, D], pe [hw, D] (no grad), tok [groups*nt, D].  The tokens pass through
+        untouched and are the keys and values of both layers (no positional encoding, no key mask); norm3 is never applied."""
+        keys = img
+        for l in range(2):
+            lp = f"{pre}.layers.{l}"
+            ca = lp + ".cross_attn_image_to_token"
+            keys = self.ln(lp + ".norm1", A.add_rows(keys, self.attn(ca, A.add_rows(keys, pe), tok, tok, groups, hw, nt)), 1e-5)
+            m = self.lin(lp + ".mlp.lin2", A.relu(self.lin(lp + ".mlp.lin1", keys)))
+            keys = self.ln(lp + ".norm2", A.add_rows(keys, m), 1e-5)
+        return tok, keys
+
     # ---- prompt encoder (prompt_encoder.py:564-827) ----------------------------------------------------------------------------
     def mask_embedding(self, masks: Tensor, flags: Tensor, p: int, g: int) -> Tensor:
         """mask_downscaling (conv2x2s2 -> LN2d -> GELU -> conv2x2s2 -> LN2d -> GELU -> conv1x1) as patch GEMMs, bilinear resize to the
@@ -313,7 +326,10 @@ class DecoderGraph:
             nex, ncls = examples.shape[1], examples.shape[2]
             class_emb = examples.reshape(b, nex * ncls, d)
         c = class_emb.shape[1]
-        toks, keys = self.two_way(md + ".transformer", query, self.dense_pe(g), class_emb.reshape(b * c, d), b, c, hw, want_tokens=True)
+        if cfg.one_way:
+            toks, keys = self.one_way(md + ".transformer", query, self.dense_pe(g), class_emb.reshape(b * c, d), b, c, hw)
+        else:
+            toks, keys = self.two_way(md + ".transformer", query, self.dense_pe(g), class_emb.reshape(b * c, d), b, c, hw, want_tokens=True)
         cls1 = None
         if cfg.classification_levels == 2:   # coarse level: tokens before class_mlp, stream before the upscaler (mask_decoder.py:345-346)
             cls1 = A.classify_wide(keys, toks, b, hw, c)
@@ -446,6 +462,8 @@ class LamTrainer:
         dead = ("prompt_encoder.transformer.final_attn_token_to_image.", "prompt_encoder.transformer.norm_final_attn.")
         if lam.cfg.prompt_encoder == "TokenPool":       # the example embeddings are the transformer's OUTPUT tokens: both are live
             dead = ()
+        if lam.cfg.one_way:         # norm3 of a OneWayAttentionBlock is a parameter its forward never applies (transformer.py:138,140-154)
+            dead = dead + tuple(f"mask_decoder.transformer.layers.{l}.norm3." for l in range(2))
         if isinstance(loss, LabelAnythingLoss):
             loss.to(lam._device())
             loss_named = [("loss." + k, p) for k, p in loss.named_parameters()]

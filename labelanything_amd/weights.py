@@ -50,6 +50,21 @@ def _two_way_shapes(s: Shapes, pre: str, d: int, mlp: int, depth: int = 2) -> No
     _ln_shapes(s, pre + ".norm_final_attn", d)
 
 
+def _one_way_shapes(s: Shapes, pre: str, d: int, mlp: int, depth: int = 2) -> None:
+    """OneWayTransformer = depth x OneWayAttentionBlock (transformer.py:26-66,129-138), in the reference's registration order.  norm3 is
+    a parameter of the block that its forward never applies: held, saved and loaded, never read."""
+    for l in range(depth):
+        lp = f"{pre}.layers.{l}"
+        _attn_shapes(s, lp + ".cross_attn_image_to_token", d, d // 2)
+        _ln_shapes(s, lp + ".norm1", d)
+        s[lp + ".mlp.lin1.weight"] = (mlp, d)
+        s[lp + ".mlp.lin1.bias"] = (mlp,)
+        s[lp + ".mlp.lin2.weight"] = (d, mlp)
+        s[lp + ".mlp.lin2.bias"] = (d,)
+        _ln_shapes(s, lp + ".norm2", d)
+        _ln_shapes(s, lp + ".norm3", d)
+
+
 def _attn_mlp_block_shapes(s: Shapes, pre: str, d: int, internal: int, mlp: int) -> None:
     _ln_shapes(s, pre + ".norm", d)
     _attn_shapes(s, pre + ".attn", d, internal)
@@ -148,7 +163,10 @@ def decoder_shapes(cfg: LamConfig) -> Shapes:
     if cfg.example_attention:
         _attn_mlp_block_shapes(s, pe + ".example_attention", d, d // 2, mlp)
     md = "mask_decoder"
-    _two_way_shapes(s, md + ".transformer", d, mlp)
+    if cfg.one_way:
+        _one_way_shapes(s, md + ".transformer", d, mlp)
+    else:
+        _two_way_shapes(s, md + ".transformer", d, mlp)
     c1, cf = cfg.up_mid, cfg.class_width                          # D // 4 and D // 8 at the default downsample rate of 8
     s[md + ".output_upscaling.0.weight"] = (d, c1, 2, 2)          # ConvTranspose2d: (Cin, Cout, kh, kw)
     s[md + ".output_upscaling.0.bias"] = (c1,)

@@ -1,0 +1,201 @@
+"""GPU: la_stream_mlp, the fused stream MLP of the OneWayTransformer's block, called directly.
+
+    x <- LayerNorm(x + relu(x W1^T + b1) W2^T + b2)        in place, x fp32 [rows, D], hidden width H
+
+The reference is the definition in fp64 torch on the CPU from the same fp32 inputs (the weight planes hi = rn(W), lo = rn(W - hi) are built
+from the fp32 weights, and hi + lo carries more bits than the 2e-5 bound looks at).  Helpers and the guard convention are those of
+tests/test_decoder_ops_gpu.py: the stream is a view into a larger allocation whose guard elements hold NaN.
+
+Shapes (rows, D, H) - the smallest that reach each way of going wrong: one row; a tail inside the first 32-row tile; one row past a
+128-row workgroup; the recipes' hidden width with a tail; more than one workgroup with 16 hidden chunks and a 4-row tail.
+"""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests.test_decoder_ops_gpu import check_guards, guarded, rint, rnd, untouched
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 256, 384), (50, 256, 256), (129, 256, 128), (200, 256, 2048), (900, 256, 2048)]
+EPS = 1e-5
+BOUND = 2e-5                 # the bound tests/test_ops_gpu.py holds la_twoway_i2t to: same operand splitting, same LayerNorm epilogue
+
+
+@pytest.fixture(scope="module")
+def L():
+    from labelanything_amd import _lib
+    _lib.lib()
+    return _lib
+
+
+def planes(w):
+    hi = w.to(torch.float16)
+    return hi.contiguous(), (w - hi.float()).to(torch.float16).contiguous()
+
+
+def definition(x, w1, b1, w2, b2, gamma, beta, dtype):
+    x, w1, b1, w2, b2, gamma, beta = (t.detach().to("cpu", dtype) for t in (x, w1, b1, w2, b2, gamma, beta))
+    y = x + torch.relu(x @ w1.t() + b1) @ w2.t() + b2
+    return F.layer_norm(y, (x.shape[1],), gamma, beta, EPS)
+
+
+def maxnorm(got, ref64):
+    """max|got - ref| / max|ref|, in fp64."""
+    return float((got.detach().double().cpu() - ref64).abs().max() / ref64.abs().max().clamp_min(1e-30))
+
+
+@functools.lru_cache(maxsize=None)
+def case(rows, d, h):
+    """Inputs on the device and the fp64 / fp32 CPU references of one shape: computed once, shared, never written."""
+    s = rows + h
+    x = rnd(rows, d, seed=s)
+    w1, w2 = rnd(h, d, seed=s + 1) / d ** 0.5, rnd(d, h, seed=s + 2) / h ** 0.5
+    b1, b2 = 0.1 * rnd(h, seed=s + 3), 0.1 * rnd(d, seed=s + 4)
+    gamma, beta = 1 + 0.1 * rnd(d, seed=s + 5), 0.1 * rnd(d, seed=s + 6)
+    args = (x, w1, b1, w2, b2, gamma, beta)
+    return args, definition(*args, torch.float64), definition(*args, torch.float32)
+
+
+def run(L, x, w1, b1, w2, b2, gamma, beta):
+    """The kernel on a guarded copy of x; returns (allocation, view)."""
+    buf, out = guarded(*x.shape)
+    out.copy_(x)
+    L.stream_mlp(out, planes(w1), b1, planes(w2), b2, gamma, beta, EPS)
+    return buf, out
+
+
+@pytest.mark.parametrize("rows,d,h", SHAPES)
+def test_against_the_fp64_definition_in_place_on_a_guarded_allocation(L, rows, d, h):
+    """la_stream_mlp against the fp64 definition from the same fp32 inputs, max-norm 2e-5; guards intact and no sentinel left (tails
+    included).  The same op sequence in fp32 torch on the CPU gives e32, printed beside the kernel's error."""
+    args, ref64, ref32 = case(rows, d, h)
+    assert L.stream_mlp_ok(d, h)
+    buf, out = run(L, *args)
+    check_guards(buf, out)
+    e32, err = maxnorm(ref32, ref64), maxnorm(out, ref64)
+    print(f"[measured] stream_mlp rows={rows} D={d} H={h}: e32 {e32:.3e}  kernel {err:.3e}  bound {BOUND:.1e}")
+    assert err <= BOUND, (err, BOUND)
+
+
+def _fixed(rows, d, seed):
+    x = rint(rows, d, seed=seed)
+    return x, 1 + 0.1 * rnd(d, seed=seed + 1), 0.1 * rnd(d, seed=seed + 2)
+
+
+@pytest.mark.parametrize("rows,h", [(129, 128), (200, 2048)])
+def test_zero_second_layer_gives_the_layer_norm_of_x(L, rows, h):
+    """la_stream_mlp with W2 = 0, b2 = 0: LN(x), within 1e-6 of fp64."""
+    d = 256
+    x, gamma, beta = _fixed(rows, d, 11)
+    w1, b1 = rnd(h, d, seed=12) / 16, rnd(h, seed=13)
+    w2, b2 = torch.zeros(d, h, device="cuda"), torch.zeros(d, device="cuda")
+    buf, out = run(L, x, w1, b1, w2, b2, gamma, beta)
+    check_guards(buf, out)
+    ref = F.layer_norm(x.double().cpu(), (d,), gamma.double().cpu(), beta.double().cpu(), EPS)
+    assert maxnorm(out, ref) <= 1e-6
+
+
+@pytest.mark.parametrize("rows,h", [(1, 384), (129, 128), (200, 2048), (50, 4096)])
+def test_every_hidden_chunk_is_counted_once(L, rows, h):
+    """la_stream_mlp with W1 = 0, b1 = 1, W2[d, h] = (d mod 3) - 1, b2 = 0 and small-integer x: every hidden unit is exactly 1, the
+    pre-norm row is exactly x[d] + H ((d mod 3) - 1).  The column pattern keeps a dropped or doubled chunk of 128 hidden units from being
+    a constant shift, which the norm would hide; what is left of it after the norm is the changed weight of x against the pattern, O(1) at
+    H = 128 and still 6e-5 at H = 4096 (asserted below on the reference), against the 1e-6 the kernel is held to."""
+    d = 256
+    x, gamma, beta = _fixed(rows, d, 21)
+    w1, b1 = torch.zeros(h, d, device="cuda"), torch.ones(h, device="cuda")
+    col = (torch.arange(d) % 3 - 1).float().cuda()
+    w2, b2 = col[:, None].expand(d, h).contiguous(), torch.zeros(d, device="cuda")
+    buf, out = run(L, x, w1, b1, w2, b2, gamma, beta)
+    check_guards(buf, out)
+    pre = x.double().cpu() + h * col.double().cpu()
+    ref = F.layer_norm(pre, (d,), gamma.double().cpu(), beta.double().cpu(), EPS)
+    wrong = F.layer_norm(x.double().cpu() + (h - 128) * col.double().cpu(), (d,), gamma.double().cpu(), beta.double().cpu(), EPS)
+    assert maxnorm(wrong, ref) > 1e-5      # what one dropped chunk would cost, from the reference alone: at least 10 x the bound below
+    assert maxnorm(out, ref) <= 1e-6
+
+
+def test_closed_relu_gate_gives_the_layer_norm_of_x_plus_b2(L):
+    """la_stream_mlp with b1 = -1e4: no hidden unit opens, the result is LN(x + b2)."""
+    rows, d, h = 200, 256, 384
+    x, gamma, beta = _fixed(rows, d, 31)
+    w1, b1 = rnd(h, d, seed=32) / 16, torch.full((h,), -1e4, device="cuda")
+    w2, b2 = rnd(d, h, seed=33), rint(d, seed=34)
+    buf, out = run(L, x, w1, b1, w2, b2, gamma, beta)
+    check_guards(buf, out)
+    ref = F.layer_norm((x + b2).double().cpu(), (d,), gamma.double().cpu(), beta.double().cpu(), EPS)
+    assert maxnorm(out, ref) <= 1e-6
+
+
+def test_the_lo_planes_of_both_weights_are_used(L):
+    """la_stream_mlp on weights s (1 +- 2^-12): fp16 rounds every entry to s, so the WHOLE difference between entries sits in the lo
+    planes.  Without them the result is off by far more than the 2e-5 bound (asserted on the reference itself)."""
+    rows, d, h = 129, 256, 256
+    g = torch.Generator().manual_seed(41)
+    sg1 = (torch.randint(0, 2, (h, d), generator=g) * 2 - 1).float()
+    sg2 = (torch.randint(0, 2, (d, h), generator=g) * 2 - 1).float()
+    sign2 = (torch.randint(0, 2, (d, h), generator=g) * 2 - 1).float()
+    w1 = (2.0 ** -4 * (1 + 2.0 ** -12 * sg1)).cuda()
+    w2 = (2.0 ** -4 * sign2 * (1 + 2.0 ** -12 * sg2)).cuda()
+    for w in (w1, w2):
+        assert bool((w.half().float().abs() == 2.0 ** -4).all()) and bool(((w - w.half().float()).abs() == 2.0 ** -16).all())
+    x = rnd(rows, d, seed=42)
+    b1, b2 = 0.1 * rnd(h, seed=43), 0.1 * rnd(d, seed=44)
+    gamma, beta = 1 + 0.1 * rnd(d, seed=45), 0.1 * rnd(d, seed=46)
+    ref = definition(x, w1, b1, w2, b2, gamma, beta, torch.float64)
+    for dropped in ((w1.half().float(), w2), (w1, w2.half().float())):
+        assert maxnorm(definition(x, dropped[0], b1, dropped[1], b2, gamma, beta, torch.float64), ref) > 5 * BOUND
+    buf, out = run(L, x, w1, b1, w2, b2, gamma, beta)
+    check_guards(buf, out)
+    err = maxnorm(out, ref)
+    print(f"[measured] stream_mlp lo planes: kernel {err:.3e}")
+    assert err <= BOUND
+
+
+def test_rows_are_independent_and_runs_repeat_bit_for_bit(L):
+    """la_stream_mlp: a permutation of the rows permutes the output bit for bit, the first 64 rows run alone equal their bits in the
+    batch, and two runs are bit-identical (no atomics, no split of the hidden dimension across workgroups)."""
+    (x, *rest), _, _ = case(900, 256, 2048)
+    _, out = run(L, x, *rest)
+    _, again = run(L, x, *rest)
+    assert torch.equal(out, again)
+    perm = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(5)).cuda()
+    _, outp = run(L, x[perm].contiguous(), *rest)
+    assert torch.equal(outp, out[perm])
+    _, head = run(L, x[:64].contiguous(), *rest)
+    assert torch.equal(head, out[:64])
+    _, one = run(L, x[899:900].contiguous(), *rest)
+    assert torch.equal(one, out[899:900])
+
+
+def test_refusals_write_nothing(L):
+    """la_stream_mlp refuses D = 128, H = 100, H = 0, H = 4224, rows = 0 and every null pointer with the entry point's name in the
+    message, before anything is written; la_stream_mlp_ok agrees on the shapes."""
+    rows, d, h = 70, 256, 256
+    w1, w2 = planes(rnd(h, d, seed=1)), planes(rnd(d, h, seed=2))
+    b1, b2, gamma, beta = rnd(h, seed=3), rnd(d, seed=4), rnd(d, seed=5), rnd(d, seed=6)
+    buf, x = guarded(rows, d)
+
+    def refused(**kw):
+        a = dict(x=x, w1=w1, b1=b1, w2=w2, b2=b2, gamma=gamma, beta=beta, rows=rows, d=d, h=h)
+        a.update(kw)
+        with pytest.raises(RuntimeError, match="la_stream_mlp"):
+            L.stream_mlp(a["x"], a["w1"], a["b1"], a["w2"], a["b2"], a["gamma"], a["beta"], EPS, rows=a["rows"], d=a["d"], h=a["h"])
+        assert untouched(buf)
+
+    assert L.stream_mlp_ok(256, 256) and L.stream_mlp_ok(256, 128) and L.stream_mlp_ok(256, 4096)
+    for dd, hh in [(128, 256), (256, 100), (256, 0), (256, 4224), (64, 2048), (256, -128)]:
+        assert not L.stream_mlp_ok(dd, hh)
+        refused(d=dd, h=hh)
+    refused(rows=0)
+    refused(rows=-5)
+    refused(x=None)
+    refused(w1=(None, w1[1]))
+    refused(w1=(w1[0], None))
+    refused(w2=(None, w2[1]))
+    refused(w2=(w2[0], None))
+    for name in ("b1", "b2", "gamma", "beta"):
+        refused(**{name: None})
