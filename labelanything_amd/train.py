@@ -422,7 +422,8 @@ class LamTrainer:
         pieces, each followed by its AdamW launch (``parallel.BucketedGradReducer``); the decoder-side gradients (40 MB) are one more
         bucket, launched from inside the backward pass - they are final when the encoder backward starts.
         train_encoder=True: every parameter trains, as with parameters/trainval/coco20i/mae_noembs.yaml (no
-        ``freeze_backbone``: models/lam.py:347 returns ``self.parameters()``); needs an HF ViT encoder (train_encoder.py).
+        ``freeze_backbone``: models/lam.py:347 returns ``self.parameters()``); needs a model with an image encoder, HF ViT or SAM ViTDet
+        (train_encoder.py: ``HfEncoderGraph`` / ``SamEncoderGraph``).
         loss: ``FocalLossDevice`` (default: focal, weight 1, class weighting) or a ``loss.LabelAnythingLoss``; the latter is moved to the
         model's device and its parameters (prompt_contrastive's t_prime / bias) train with the decoder's learning rate and weight
         decay, as ``WrapperModule.get_learnable_params`` appends them to the optimizer (experiment/utils.py:290-295)."""
@@ -453,7 +454,7 @@ class LamTrainer:
         # the saved-activation forward of train_encoder.py runs the plain GEMM sequence, without the inference engine's token-mean
         # corrections of V / proj: what those recover (logits 9.5e-4 -> 6e-4) is far below the 16-bit backward's own error (1e-3 ... 1e-2
         # on the gradients), and second weight planes in their place cost 2.5 ms of the step.  That choice lives in the
-        # trainer's PRIVATE encoder engine (HfEncoderGraph): ``lam.precise`` - what validation / inference on the same model use - is
+        # trainer's PRIVATE encoder engine (EncoderGraph.engine): ``lam.precise`` - what validation / inference on the same model use - is
         # left alone.
         self.train_precise = tuple(gname for gname in lam.precise if gname not in ("vmean", "projmean"))
         named = [(k, p) for k, p in lam.named_parameters() if self.train_encoder or "image_encoder" not in k]

@@ -2,6 +2,11 @@
 backward on HIP kernels of the HF ViT stack (``HfEncoderGraph``: transformers ViTModel under models/build_encoder.py:83-100) and of the
 SAM ViTDet stack (``SamEncoderGraph``: models/image_encoder.py:110-376).
 
+One block stack for both: ``EncoderGraph.forward`` / ``_backward_scaled`` walk ``spec.depth`` transformer blocks whose tensor names and
+LayerNorm eps come from ``engine.HF_BLOCK`` / ``engine.SAM_BLOCK`` and whose attention follows a per-block ``BlockGeo`` (plain and global,
+or windows as row gathers and / or the decomposed rel-pos terms).  What a kind adds is how the stream is entered and left (``_enter`` /
+``_leave`` and their backwards) and ``_block_geo``; the q | k | v parameter gradient goes by the number of Linears the kind's names list.
+
 Which configuration this is: ``parameters/trainval/coco20i/mae_noembs.yaml`` has no ``freeze_backbone``, so
 ``Lam.get_learnable_params`` (models/lam.py:321-347) returns ``self.parameters()`` - the ViT-B backbone (85.8 M parameters) trains
 together with neck, prompt encoder and mask decoder.  (``mae.yaml`` is the decoder-only training on precomputed embeddings.)
@@ -34,11 +39,13 @@ grid: get_rel_pos's resampling is applied as its fixed linear map and that map's
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib as L
+from .engine import HF_BLOCK, SAM_BLOCK, BlockNames
 
 Tensor = torch.Tensor
 
@@ -47,11 +54,44 @@ def _ceil(a: int, b: int) -> int:
     return (a + b - 1) // b * b
 
 
-class HfEncoderGraph:
-    """One trainable HF ViT encoder.  ``grads``: parameter name (``image_encoder....``) -> fp32 tensor the gradient is ADDED to."""
+@dataclass(frozen=True)
+class BlockGeo:
+    """Attention geometry of one block.  Hashable: the backward keeps one set of work buffers per distinct geometry."""
+    nb: int                       # attention batches (images, or windows of all images)
+    gg: int                       # grid side of a batch (the G of the rel-pos terms)
+    t: int                        # tokens per batch
+    tpad: int                     # key slots per batch
+    arows: int                    # rows of qkv and of the attention output: nb * t
+    windowed: bool                # attention runs in zero-padded window order: row gathers in front of qkv and behind proj
+    relpos: bool                  # scores carry the decomposed rel-pos terms
+
+
+@dataclass
+class _Saved:
+    """What the backward of one block needs of its forward."""
+    geo: BlockGeo
+    x_in: Tensor                  # fp32 stream in front of the block (never updated in place: every residual GEMM writes a new buffer)
+    xa: Tensor                    # 16-bit LayerNorm output the q | k | v GEMMs saw, in attention order
+    qkv: Tensor
+    ao: Tensor
+    lse: Tensor
+    relh: Optional[Tensor]        # la_relpos_terms (relpos blocks)
+    relw: Optional[Tensor]
+    x_mid: Tensor                 # fp32 stream between the two halves
+    xnb: Tensor                   # 16-bit LayerNorm output fc1 saw
+    pre: Tensor                   # fc1's pre-activation | GELU of it
+    post: Tensor
+    fuse_fc2_bwd: bool            # gelu' in the epilogue of fc2's data gradient (decided with the forward)
+
+
+class EncoderGraph:
+    """One trainable encoder: patch embedding, ``spec.depth`` transformer blocks, the kind's exit.  ``grads``: parameter name
+    (``image_encoder....``) -> fp32 tensor the gradient is ADDED to.  A kind sets ``KIND`` / ``NAMES`` and provides ``_enter``, ``_leave``,
+    their backwards and ``_block_geo``; one that answers windowed / relpos geometries brings ``_win_index`` / ``_rel_tables``."""
 
     TARGET_MAX = 64.0
-    KIND = "hf"
+    KIND: str
+    NAMES: BlockNames
 
     @staticmethod
     def owns(key: str) -> bool:
@@ -136,60 +176,77 @@ class HfEncoderGraph:
 
     @torch.no_grad()
     def forward(self, images: Tensor) -> Tensor:
-        """(Bn, 3, S, S) fp32 on the device -> [Bn * hw, E] fp32 NHWC rows (CLS dropped), activations kept for ``backward``."""
+        """(Bn, 3, S, S) fp32 on the device -> [Bn * hw, E] fp32 NHWC rows (what the kind's ``_leave`` makes of the last block's state),
+        activations kept for ``backward``."""
         eng = self.engine()
-        spec, w, p = self.spec, eng.w32, eng.p
-        pre = "image_encoder"
+        spec, w, p, nm = self.spec, eng.w32, eng.p, self.NAMES
         images = images.contiguous()
         bn, _, s, _ = images.shape
         e, heads, g = spec.dim, spec.heads, s // spec.patch
-        hw, t = g * g, g * g + 1
-        rows, tpad = bn * t, _ceil(t, 64)
         dev, dt = images.device, eng.dt
-        pos = eng._hf_pos(g)
-        cls_row = eng._hfpos_cache[-g]
-        a, akw = eng.patches("hf.patchA", images, bn * hw, spec.patch)
-        res = torch.empty(rows, e, device=dev)
-        res.view(bn, t, e)[:, 0].copy_(cls_row)
-        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".embeddings.patch_embeddings.projection.bias"], res=pos, res_mod=t, out32=res,
-               map=L.MAP_GROUP, p=(hw, t, 1, 0, 0), **akw)
-        scale = spec.head_dim ** -0.5
-        layers: List[dict] = []
         hdp = self.hdp
         ea, nh = heads * hdp, hdp // 64             # width of the q / k / v / attention-output blocks (== e unless the heads are padded)
-        vt = torch.zeros(bn * heads, hdp, tpad, device=dev, dtype=dt)
+        scale = spec.head_dim ** -0.5
+        c = dict(images=images, bn=bn, g=g, hw=g * g, e=e, ea=ea, heads=heads, scale=scale, dt=dt)      # (self.ctx once the forward is through)
+        res = self._enter(eng, c)
+        rows = c["rows"] = res.shape[0]
+        layers: List[_Saved] = []
+        vts: Dict[BlockGeo, Tensor] = {}            # V^T per geometry: zero beyond t, and la_head_transpose writes the same slots every time
         for i in range(spec.depth):
-            lp = f"{pre}.encoder.layer.{i}"
-            sv = {"x_in": res}                       # (the stream is never updated in place: every residual GEMM writes a new buffer,
-            x16 = torch.empty(rows, e, device=dev, dtype=dt)      # which is also the activation the backward keeps)
-            sv["xn"] = x16                           # the weight gradients take the 16-bit LayerNorm output the GEMMs saw
-            eng.ln(res, lp + ".layernorm_before", 1e-12, out16=x16)
-            sv["qkv"] = torch.empty(rows, 3 * ea, device=dev, dtype=dt)
-            self._qkv_plain(eng, x16, lp + ".qkv.w", sv["qkv"], ea)
-            L.head_transpose(sv["qkv"], 2 * ea, bn, heads * nh, t, tpad, vt)        # (a 128-wide head = two 64-row blocks of V^T)
-            sv["ao"] = torch.empty(rows, ea, device=dev, dtype=dt)
-            sv["lse"] = torch.full((bn * heads, tpad), 1e30, device=dev)
-            L.attn_fwd_lse(sv["qkv"], vt, sv["ao"], sv["lse"], bn, heads, t, tpad, ea, scale)
+            bp = nm.prefix.format(i)
+            geo = self._block_geo(i, c)
+            nb, gg, t, tpad, arows = geo.nb, geo.gg, geo.t, geo.tpad, geo.arows
+            # ---- attention: x_mid = x_in + unpartition(proj(attn(partition(LN1(x_in))))) ------------------------------------------
+            x16 = torch.empty(rows, e, device=dev, dtype=dt)      # the weight gradients take the 16-bit LayerNorm output the GEMMs saw
+            eng.ln(res, f"{bp}.{nm.norm1}", nm.eps, out16=x16)
+            if geo.windowed:                         # pad-after-norm windows: padded rows are zero
+                widx = self._win_index(bn, g, gg, dev)
+                xa = torch.zeros(arows, e, device=dev, dtype=dt)
+                xa.index_copy_(0, widx, x16)
+            else:
+                xa = x16
+            qkv = torch.empty(arows, 3 * ea, device=dev, dtype=dt)
+            self._qkv_plain(eng, xa, bp + ".qkv.w", qkv, ea)
+            relh = relw = None
+            if geo.relpos:
+                # (rel-pos tables whose length is not 2 gg - 1 are resampled like get_rel_pos does, image_encoder.py:321-330: the engine
+                # packs the resampled 16-bit tables the forward kernels read; the backward applies the transposed map, ``_rel_tables``)
+                relh = torch.empty(nb * heads, t, gg, device=dev)
+                relw = torch.empty(nb * heads, t, gg, device=dev)
+                L.relpos_terms(qkv, nb, heads, gg, ea, p[bp + ".tabh"], p[bp + ".tabw"], relh, relw)
+            vt = vts.get(geo)
+            if vt is None:
+                vt = vts[geo] = torch.zeros(nb * heads, hdp, tpad, device=dev, dtype=dt)
+            L.head_transpose(qkv, 2 * ea, nb, heads * nh, t, tpad, vt)        # (a 128-wide head = two 64-row blocks of V^T)
+            ao = torch.empty(arows, ea, device=dev, dtype=dt)
+            lse = torch.empty(nb * heads, tpad, device=dev)        # (slots beyond t: la_attn_bwd sets them itself, attn_bwd.hip:174-176)
+            if geo.relpos:
+                L.attn_fwd_relpos_lse(qkv, vt, ao, relh, relw, lse, nb, heads, t, tpad, gg, ea, scale)
+            else:
+                L.attn_fwd_lse(qkv, vt, ao, lse, nb, heads, t, tpad, ea, scale)
             x_mid = torch.empty(rows, e, device=dev)
-            eng.gemm_w(sv["ao"], lp + ".proj.w", bias=w[lp + ".attention.output.dense.bias"], res=res, out32=x_mid)
-            sv["x_mid"] = x_mid
-            x16b = torch.empty(rows, e, device=dev, dtype=dt)
-            sv["xnb"] = x16b
-            eng.ln(x_mid, lp + ".layernorm_after", 1e-12, out16=x16b)
-            sv["post"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-            sv["pre"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-            self._fc1_fwd(eng, x16b, lp + ".lin1.w", w[lp + ".intermediate.dense.bias"], sv["pre"], sv["post"])
+            if geo.windowed:                         # proj on every window row, real tokens gathered back into image order
+                yw = torch.empty(arows, e, device=dev)
+                eng.gemm_w(ao, bp + ".proj.w", bias=w[f"{bp}.{nm.proj}.bias"], out32=yw)
+                L.add_cast(res, yw.index_select(0, widx), rows, out32=x_mid, dt=L._DT[dt])
+            else:
+                eng.gemm_w(ao, bp + ".proj.w", bias=w[f"{bp}.{nm.proj}.bias"], res=res, out32=x_mid)
+            # ---- MLP: res = x_mid + fc2(gelu(fc1(LN2(x_mid)))) -----------------------------------------------------------------
+            xnb = torch.empty(rows, e, device=dev, dtype=dt)
+            eng.ln(x_mid, f"{bp}.{nm.norm2}", nm.eps, out16=xnb)
+            post = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
+            pre = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
+            self._fc1_fwd(eng, xnb, bp + ".lin1.w", w[f"{bp}.{nm.lin1}.bias"], pre, post)
             # fused / unfused is decided ONCE per graph, here, for the backward half too (la_gemm_fused_act_ok reads the library's
             # mutable kernel selection: an A/B tool that toggles it between forward and backward must not mix the two forms)
-            sv["fuse_fc2_bwd"] = bool(self.fused_gelu and L.gemm_fused_act_ok(rows, spec.mlp, e))
-            res = torch.empty(rows, e, device=dev)
-            eng.gemm_w(sv["post"], lp + ".lin2.w", bias=w[lp + ".output.dense.bias"], res=x_mid, out32=res)
-            layers.append(sv)
-        fin = torch.empty(rows, e, device=dev)
-        eng.ln(res, pre + ".layernorm", 1e-12, out32=fin)
-        out = fin.view(bn, t, e)[:, 1:].reshape(bn * hw, e).contiguous()
-        self.ctx = dict(images=images, layers=layers, x_fin=res, bn=bn, g=g, hw=hw, t=t, rows=rows, tpad=tpad, e=e, ea=ea, heads=heads,
-                        scale=scale, dt=dt)
+            fuse_fc2_bwd = bool(self.fused_gelu and L.gemm_fused_act_ok(rows, spec.mlp, e))
+            x_in, res = res, torch.empty(rows, e, device=dev)
+            eng.gemm_w(post, bp + ".lin2.w", bias=w[f"{bp}.{nm.lin2}.bias"], res=x_mid, out32=res)
+            layers.append(_Saved(geo=geo, x_in=x_in, xa=xa, qkv=qkv, ao=ao, lse=lse, relh=relh, relw=relw, x_mid=x_mid, xnb=xnb, pre=pre,
+                                 post=post, fuse_fc2_bwd=fuse_fc2_bwd))
+        c["layers"] = layers
+        out = self._leave(eng, c, res)
+        self.ctx = c
         return out
 
     def _fc1_fwd(self, eng, x16: Tensor, key: str, bias: Tensor, pre: Tensor, post: Tensor) -> None:
@@ -201,20 +258,18 @@ class HfEncoderGraph:
             eng.gemm_w(x16, key, bias=bias, out16=pre)
             L.gelu_fwd16(pre, post)
 
-    def _fc2_bwd(self, dy32: Tensor, dy16: Tensor, a: dict, wname: str, bname: str, dh: Tensor, dpre32, dpre16: Tensor) -> None:
+    def _fc2_bwd(self, dy32: Tensor, dy16: Tensor, a: _Saved, wname: str, bname: str, dh: Optional[Tensor], dpre32, dpre16: Tensor) -> None:
         """Backward of fc2 and of the GELU in front of it: dW2 += dY^T post, db2 += colsum dY, d pre = (dY W2) * gelu'(pre) - the last as
         ONE product whose epilogue reads the saved pre-activation (LA_ACT_GELU_BWD) where the shape allows, else product + la_gelu_bwd16.
         dpre32 (None = not needed): the fp32 copy the exact-fp32 fallbacks of fc1's weight / bias gradient read."""
-        r, n, k = dy16.shape[0], a["pre"].shape[1], dy16.shape[1]
-        fuse = a["fuse_fc2_bwd"] if "fuse_fc2_bwd" in a else (self.fused_gelu and L.gemm_fused_act_ok(r, n, k))
-        if fuse and dpre32 is None:
+        if a.fuse_fc2_bwd and dpre32 is None:
             wt = self.w[wname]
-            if not self._wgrad(dy16, dy32, a["post"], self.sviews[wname], db=self.sviews[bname]):
+            if not self._wgrad(dy16, dy32, a.post, self.sviews[wname], db=self.sviews[bname]):
                 L.colsum_acc(dy32, self.sviews[bname])
-            L.gemm(dy16, self._wt16(wname, lambda: wt, dy16.dtype), out16=dpre16, act=L.ACT_GELU_BWD, aux16=a["pre"])
+            L.gemm(dy16, self._wt16(wname, lambda: wt, dy16.dtype), out16=dpre16, act=L.ACT_GELU_BWD, aux16=a.pre)
         else:
-            self._linear_bwd(dy32, dy16, a["post"], wname, bname, dx32=dh)
-            L.gelu_bwd16(a["pre"], dh, dpre32, dpre16)
+            self._linear_bwd(dy32, dy16, a.post, wname, bname, dx32=dh)
+            L.gelu_bwd16(a.pre, dh, dpre32, dpre16)
 
     # ---- backward --------------------------------------------------------------------------------------------------------------
     def _wt16(self, key: str, wt_fn, dt) -> Tensor:
@@ -266,15 +321,15 @@ class HfEncoderGraph:
             L.gemm_tn(dy32, x32, dw.view(n, k))
             return False
 
-    def _qkv_wgrad_fused(self, dqkv16: Tensor, x: Tensor, att: str, e: int) -> bool:
+    def _qkv_wgrad_fused(self, dqkv16: Tensor, x: Tensor, bp: str, e: int) -> bool:
         """The three weight gradients of HF's separate query / key / value Linears from ONE split-K product dqkv^T x.  In the flat
         gradient buffer (FlatAdamW packs the tensors back to back in parameter order) the three [E, E] blocks sit a fixed stride
         apart - weight, bias, weight, bias, ... - which is la_gemm's LA_MAP_GROUP row map; the bias gradients come out of the
         transpose's column sums.  Three launches of 9 output tiles each end in three times the atomics of one launch of 27.
         Returns False (nothing done) when the layout or the shape does not allow it."""
         sv = self.sviews
-        gw = [sv[att + nm + ".weight"] for nm in ("query", "key", "value")]
-        gb = [sv[att + nm + ".bias"] for nm in ("query", "key", "value")]
+        gw = [sv[f"{bp}.{q}.weight"] for q in self.NAMES.qkv]
+        gb = [sv[f"{bp}.{q}.bias"] for q in self.NAMES.qkv]
         r = dqkv16.shape[0]
         if not (self.fast_wgrad and e % 256 == 0 and r >= 128 and all(g.is_contiguous() for g in gw + gb)):
             return False
@@ -407,75 +462,164 @@ class HfEncoderGraph:
             self._runs = [(o, m, torch.as_strided(f, (m,), (1,))) for o, m, f in runs]
         return self._runs
 
+    def _work(self, geo: BlockGeo, a: _Saved):
+        """Work buffers of one geometry's attention backward: dao, dqkv16, dvec, drelh, drelw (relpos), and for windows proj's dY and
+        q | k | v's dX in window order.  None needs an initial value but that dY, whose padded rows (dropped outputs) receive no gradient:
+        D and the LSE slots beyond t are written by la_attn_bwd's dQ kernel before its dK / dV kernel reads them (attn_bwd.hip:174-176)."""
+        c = self.ctx
+        dev, dt, e, ea = a.qkv.device, c["dt"], c["e"], c["ea"]
+        return (torch.empty(geo.arows, ea, device=dev, dtype=dt), torch.empty(geo.arows, 3 * ea, device=dev, dtype=dt),
+                torch.empty(geo.nb * c["heads"], geo.tpad, device=dev),
+                torch.empty_like(a.relh) if geo.relpos else None, torch.empty_like(a.relw) if geo.relpos else None,
+                torch.zeros(geo.arows, e, device=dev, dtype=dt) if geo.windowed else None,
+                torch.empty(geo.arows, e, device=dev) if geo.windowed else None)
+
     def _backward_scaled(self, d_out: Tensor, s: float) -> None:
         c = self.ctx
         if c is None:
-            raise RuntimeError("HfEncoderGraph.backward without a forward")
+            raise RuntimeError(f"{type(self).__name__}.backward without a forward")
         self._xt_key = None
-        spec, w, sv = self.spec, self.w, self.sviews
-        pre = "image_encoder"
-        bn, t, hw, rows, tpad, e, heads, dt = c["bn"], c["t"], c["hw"], c["rows"], c["tpad"], c["e"], c["heads"], c["dt"]
-        ea, padded = c["ea"], c["ea"] != c["e"]
+        spec, w, sv, nm = self.spec, self.w, self.sviews, self.NAMES
+        rows, e, ea, dt = c["rows"], c["e"], c["ea"], c["dt"]
         dev = d_out.device
-        dfin = torch.zeros(rows, e, device=dev)
-        tmp = torch.empty_like(d_out)
-        L.cast(d_out.contiguous(), tmp, s)
-        dfin.view(bn, t, e)[:, 1:].copy_(tmp.view(bn, hw, e))
         # dres: the running fp32 gradient of the residual stream, d16 its 16-bit copy (the operand of the next backward GEMM) - both
         # leave every LayerNorm backward together with the skip connection's share (la_layernorm_bwd_res)
-        dres = torch.empty(rows, e, device=dev)
-        d16 = torch.empty(rows, e, device=dev, dtype=dt)
-        L.layernorm_bwd_res(c["x_fin"], dfin, w[pre + ".layernorm.weight"], w[pre + ".layernorm.bias"], 1e-12, None, dres, d16,
-                            sv[pre + ".layernorm.weight"], sv[pre + ".layernorm.bias"])
-        dh = torch.empty(rows, spec.mlp, device=dev)
-        dpre32 = torch.empty(rows, spec.mlp, device=dev)
+        dres, d16 = self._leave_bwd(d_out, s)
+        # (the fp32 copies of d pre-activation and of dq | dk | dv only feed the exact-fp32 fallbacks of the weight / bias gradients; dh: the
+        # unfused gelu')
+        need32 = not (self.fast_wgrad and e % 256 == 0 and rows >= 128)
+        dpre32 = torch.empty(rows, spec.mlp, device=dev) if need32 else None
+        dqkv32 = torch.empty(rows, 3 * ea, device=dev) if need32 and len(nm.qkv) == 3 else None
+        dh = torch.empty(rows, spec.mlp, device=dev) if need32 or not all(a.fuse_fc2_bwd for a in c["layers"]) else None
         dpre16 = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
         dxn = torch.empty(rows, e, device=dev)
-        dao = torch.empty(rows, ea, device=dev, dtype=dt)
-        dqkv16 = torch.empty(rows, 3 * ea, device=dev, dtype=dt)
-        dqkv32 = torch.empty(rows, 3 * ea, device=dev)
-        dvec = torch.zeros(bn * heads, tpad, device=dev)
+        work: Dict[BlockGeo, tuple] = {}            # one set per distinct geometry (HF: one; SAM: windows, global)
+        last = {a.geo: i for i, a in reversed(list(enumerate(c["layers"])))}      # the last block of each geometry the backward visits
         for i in reversed(range(spec.depth)):
-            lp = f"{pre}.encoder.layer.{i}"
+            bp = nm.prefix.format(i)
             a = c["layers"][i]
             # ---- MLP: res = x_mid + fc2(gelu(fc1(LN2(x_mid)))) -----------------------------------------------------------------
-            # (the fp32 copy of d pre-activation only feeds the exact-fp32 fallbacks of the weight / bias gradient)
-            need32 = not (self.fast_wgrad and e % 256 == 0 and rows >= 128)
-            self._fc2_bwd(dres, d16, a, lp + ".output.dense.weight", lp + ".output.dense.bias", dh, dpre32 if need32 else None, dpre16)
-            self._linear_bwd(dpre32 if need32 else None, dpre16, a["xnb"], lp + ".intermediate.dense.weight", lp + ".intermediate.dense.bias",
-                             dx32=dxn)
-            L.layernorm_bwd_res(a["x_mid"], dxn, w[lp + ".layernorm_after.weight"], w[lp + ".layernorm_after.bias"], 1e-12, dres, dres, d16,
-                                sv[lp + ".layernorm_after.weight"], sv[lp + ".layernorm_after.bias"])
-            # ---- attention: x_mid = x_in + proj(attn(LN1(x_in))) -------------------------------------------------------------
-            self._linear_bwd(dres, d16, a["ao"], lp + ".attention.output.dense.weight", lp + ".attention.output.dense.bias", dx16=dao,
-                             pad_in=padded)
-            # (no K^T / Q^T / dO^T copies: the backward kernels read those operands out of the row-major tiles with LDS transpose reads)
-            L.attn_bwd(a["qkv"], a["ao"], dao, None, None, None, a["lse"], dvec, dqkv16, bn, heads, t, tpad, ea, c["scale"])
-            att = lp + ".attention.attention."
-            have32 = False
-            fused = not padded and self._qkv_wgrad_fused(dqkv16, a["xn"], att, e)
-            for j, nm in enumerate(() if fused else ("query", "key", "value")):
-                if padded:
-                    dwp = self._tbuf("dw_pad_qkv", ea, e, torch.float32)
-                    dbp = self._tbuf("db_pad_qkv", 1, ea, torch.float32).view(ea)
-                    dwp.zero_()
-                    dbp.zero_()
-                else:
-                    dwp, dbp = sv[att + nm + ".weight"], sv[att + nm + ".bias"]
-                if not self._wgrad(dqkv16[:, j * ea:(j + 1) * ea], None, a["xn"], dwp, db=dbp):
-                    if not have32:                    # (exact-fp32 fallback of the weight gradient: it needs the fp32 copy)
-                        L.cast(dqkv16, dqkv32)
-                        have32 = True
-                    L.colsum_acc(dqkv32[:, j * ea:(j + 1) * ea], dbp)
-                if padded:
-                    self._fold_padded(dwp, dbp, sv[att + nm + ".weight"], sv[att + nm + ".bias"], False, heads)
-            wqkv_t = self._wt16(att + "qkv", lambda: torch.cat([self._pad_weight(w[att + nm + ".weight"], False, heads if padded else 0)
-                                                                for nm in ("query", "key", "value")]), dt)
-            L.gemm(dqkv16, wqkv_t, out32=dxn)                                                                  # [3E, E]^T
-            L.layernorm_bwd_res(a["x_in"], dxn, w[lp + ".layernorm_before.weight"], w[lp + ".layernorm_before.bias"], 1e-12, dres, dres, d16,
-                                sv[lp + ".layernorm_before.weight"], sv[lp + ".layernorm_before.bias"])
-        # ---- embeddings: res0[b, 0] = cls + pos[0]; res0[b, 1 + i] = patch_i W^T + b + pos[1 + i] --------------------------------
-        emb = pre + ".embeddings."
+            self._fc2_bwd(dres, d16, a, f"{bp}.{nm.lin2}.weight", f"{bp}.{nm.lin2}.bias", dh, dpre32, dpre16)
+            self._linear_bwd(dpre32, dpre16, a.xnb, f"{bp}.{nm.lin1}.weight", f"{bp}.{nm.lin1}.bias", dx32=dxn)
+            L.layernorm_bwd_res(a.x_mid, dxn, w[f"{bp}.{nm.norm2}.weight"], w[f"{bp}.{nm.norm2}.bias"], nm.eps, dres, dres, d16,
+                                sv[f"{bp}.{nm.norm2}.weight"], sv[f"{bp}.{nm.norm2}.bias"])
+            # ---- attention: x_mid = x_in + unpartition(proj(attn(partition(LN1(x_in))))) ------------------------------------------
+            if a.geo not in work:
+                work[a.geo] = self._work(a.geo, a)
+            self._attn_bwd(bp, a, work[a.geo], dres, d16, dxn, dqkv32)
+            if last[a.geo] == i:                     # (with two blocks - the reduced SAM fixtures - this is what keeps the peak from rising:
+                del work[a.geo]                      # the set goes before the other geometry's is allocated)
+        self._enter_bwd(dres)
+
+    def _attn_bwd(self, bp: str, a: _Saved, wk: tuple, dres: Tensor, d16: Tensor, dxn: Tensor, dqkv32: Optional[Tensor]) -> None:
+        """Backward of one block's attention half on the work buffers ``wk`` of its geometry: dres / d16 in, dres / d16 out."""
+        c, w, sv, nm, geo = self.ctx, self.w, self.sviews, self.NAMES, a.geo
+        heads, ea, padded = c["heads"], c["ea"], c["ea"] != c["e"]
+        nb, gg, t, tpad = geo.nb, geo.gg, geo.t, geo.tpad
+        dao, dqkv16, dvec, drelh, drelw, dy16, dxa = wk
+        if geo.windowed:                             # the dropped (padded) output rows receive no gradient
+            widx = self._win_index(c["bn"], c["g"], gg, d16.device)
+            dy16.index_copy_(0, widx, d16)
+            dy32 = None
+        else:                                        # image order: the block's gradient goes where fc1's went
+            dy16, dy32, dxa = d16, dres, dxn
+        self._linear_bwd(dy32, dy16, a.ao, f"{bp}.{nm.proj}.weight", f"{bp}.{nm.proj}.bias", dx16=dao, pad_in=padded)
+        # (no K^T / Q^T / dO^T copies: the backward kernels read those operands out of the row-major tiles with LDS transpose reads)
+        if geo.relpos:
+            L.attn_bwd_relpos(a.qkv, a.ao, dao, None, None, None, a.lse, dvec, dqkv16, a.relh, a.relw, drelh, drelw, nb, heads, t, tpad, gg,
+                              ea, c["scale"])
+            tabs, dtabs, fold = self._rel_tables(bp, gg)
+            L.relpos_bwd(a.qkv, dqkv16, drelh, drelw, tabs[0], tabs[1], dtabs[0], dtabs[1], nb, heads, gg, ea)
+            fold()
+        else:
+            L.attn_bwd(a.qkv, a.ao, dao, None, None, None, a.lse, dvec, dqkv16, nb, heads, t, tpad, ea, c["scale"])
+        self._qkv_bwd(bp, dqkv16, a.xa, dxa, dqkv32)
+        L.layernorm_bwd_res(a.x_in, dxa.index_select(0, widx) if geo.windowed else dxa, w[f"{bp}.{nm.norm1}.weight"],
+                            w[f"{bp}.{nm.norm1}.bias"], nm.eps, dres, dres, d16, sv[f"{bp}.{nm.norm1}.weight"], sv[f"{bp}.{nm.norm1}.bias"])
+
+    def _qkv_bwd(self, bp: str, dqkv16: Tensor, x: Tensor, dx32: Tensor, dqkv32: Optional[Tensor]) -> None:
+        """Backward of the q | k | v projection: parameter gradients, and dx32 = dqkv . W.  dqkv32: room for the fp32 copy of dqkv16 that
+        the exact-fp32 weight gradients of the three-Linear form read (None where they cannot be taken)."""
+        nm, w, sv = self.NAMES, self.w, self.sviews
+        e, ea, heads = self.ctx["e"], self.ctx["ea"], self.spec.heads
+        padded = ea != e
+        if len(nm.qkv) == 1:                         # one fused Linear
+            self._linear_bwd(None, dqkv16, x, f"{bp}.{nm.qkv[0]}.weight", f"{bp}.{nm.qkv[0]}.bias", dx32=dx32, pad_out=3 * heads if padded else 0)
+            return
+        # three Linears: one product for the three weight gradients where the slots and the shape allow, else one per tensor
+        have32 = False
+        fused = not padded and self._qkv_wgrad_fused(dqkv16, x, bp, e)
+        for j, q in enumerate(() if fused else nm.qkv):
+            if padded:
+                dwp = self._tbuf("dw_pad_qkv", ea, e, torch.float32)
+                dbp = self._tbuf("db_pad_qkv", 1, ea, torch.float32).view(ea)
+                dwp.zero_()
+                dbp.zero_()
+            else:
+                dwp, dbp = sv[f"{bp}.{q}.weight"], sv[f"{bp}.{q}.bias"]
+            if not self._wgrad(dqkv16[:, j * ea:(j + 1) * ea], None, x, dwp, db=dbp):
+                if not have32:                    # (exact-fp32 fallback of the weight gradient: it needs the fp32 copy)
+                    L.cast(dqkv16, dqkv32)
+                    have32 = True
+                L.colsum_acc(dqkv32[:, j * ea:(j + 1) * ea], dbp)
+            if padded:
+                self._fold_padded(dwp, dbp, sv[f"{bp}.{q}.weight"], sv[f"{bp}.{q}.bias"], False, heads)
+        wqkv_t = self._wt16(bp + ".qkv", lambda: torch.cat([self._pad_weight(w[f"{bp}.{q}.weight"], False, heads if padded else 0)
+                                                            for q in nm.qkv]), dqkv16.dtype)
+        L.gemm(dqkv16, wqkv_t, out32=dx32)                                                                  # [3E, E]^T
+
+
+class HfEncoderGraph(EncoderGraph):
+    """The HF ViT stack: a CLS row in front of every image's tokens, a position table resampled bicubically to the image's grid, plain
+    global attention in every block, a final LayerNorm; the CLS row is dropped on the way out."""
+
+    KIND = "hf"
+    NAMES = HF_BLOCK
+
+    def _block_geo(self, i: int, c: dict) -> BlockGeo:
+        t = c["hw"] + 1
+        return BlockGeo(nb=c["bn"], gg=c["g"], t=t, tpad=_ceil(t, 64), arows=c["bn"] * t, windowed=False, relpos=False)
+
+    def _enter(self, eng, c: dict) -> Tensor:
+        """res0[b, 0] = cls + pos[0]; res0[b, 1 + i] = patch_i W^T + b + pos[1 + i]"""
+        spec = self.spec
+        bn, g, hw, e = c["bn"], c["g"], c["hw"], c["e"]
+        t = hw + 1
+        pos = eng._hf_pos(g)
+        cls_row = eng._hfpos_cache[-g]
+        a, akw = eng.patches("hf.patchA", c["images"], bn * hw, spec.patch)
+        res = torch.empty(bn * t, e, device=c["images"].device)
+        res.view(bn, t, e)[:, 0].copy_(cls_row)
+        L.gemm(a, eng.p["image_encoder.patch.w"], bias=eng.w32["image_encoder.embeddings.patch_embeddings.projection.bias"], res=pos, res_mod=t,
+               out32=res, map=L.MAP_GROUP, p=(hw, t, 1, 0, 0), **akw)
+        return res
+
+    def _leave(self, eng, c: dict, res: Tensor) -> Tensor:
+        bn, hw, e = c["bn"], c["hw"], c["e"]
+        fin = torch.empty_like(res)
+        eng.ln(res, "image_encoder.layernorm", self.NAMES.eps, out32=fin)
+        c["x_fin"] = res
+        return fin.view(bn, hw + 1, e)[:, 1:].reshape(bn * hw, e).contiguous()
+
+    def _leave_bwd(self, d_out: Tensor, s: float):
+        c, w, sv = self.ctx, self.w, self.sviews
+        bn, hw, rows, e = c["bn"], c["hw"], c["rows"], c["e"]
+        dev = d_out.device
+        dfin = torch.zeros(rows, e, device=dev)                     # (the CLS rows of the output were dropped: no gradient)
+        tmp = torch.empty_like(d_out)
+        L.cast(d_out.contiguous(), tmp, s)
+        dfin.view(bn, hw + 1, e)[:, 1:].copy_(tmp.view(bn, hw, e))
+        dres = torch.empty(rows, e, device=dev)
+        d16 = torch.empty(rows, e, device=dev, dtype=c["dt"])
+        L.layernorm_bwd_res(c["x_fin"], dfin, w["image_encoder.layernorm.weight"], w["image_encoder.layernorm.bias"], self.NAMES.eps, None, dres,
+                            d16, sv["image_encoder.layernorm.weight"], sv["image_encoder.layernorm.bias"])
+        return dres, d16
+
+    def _enter_bwd(self, dres: Tensor) -> None:
+        c, spec, sv = self.ctx, self.spec, self.sviews
+        bn, g, hw, e = c["bn"], c["g"], c["hw"], c["e"]
+        t, dev = hw + 1, dres.device
+        emb = "image_encoder.embeddings."
         d0 = dres.view(bn, t, e)
         dpatch = d0[:, 1:].reshape(bn * hw, e).contiguous()
         k = 3 * spec.patch * spec.patch
@@ -485,22 +629,21 @@ class HfEncoderGraph:
         L.colsum_acc(dpatch, sv[emb + "patch_embeddings.projection.bias"])
         dpos_rows = d0.sum(dim=0)                                   # [t, E]: a few hundred rows of bookkeeping, not a kernel
         sv[emb + "cls_token"].view(-1).add_(dpos_rows[0])
-        pos = w[emb + "position_embeddings"]
-        if c["g"] == spec.pos_grid:
+        if g == spec.pos_grid:
             sv[emb + "position_embeddings"].view(t, e).add_(dpos_rows)
         else:                                                       # through the bicubic resample of the patch positions: dpos = B^T d
             from .engine import bicubic_matrix_t
-            bt = bicubic_matrix_t(spec.pos_grid, c["g"], dev)       # [gin^2, gout^2]
-            b = self._tbuf("bicubic_b", c["g"] * c["g"], spec.pos_grid * spec.pos_grid, torch.float32)
-            if not self._b_ready.get((spec.pos_grid, c["g"])):
+            bt = bicubic_matrix_t(spec.pos_grid, g, dev)            # [gin^2, gout^2]
+            b = self._tbuf("bicubic_b", g * g, spec.pos_grid * spec.pos_grid, torch.float32)
+            if not self._b_ready.get((spec.pos_grid, g)):
                 b.copy_(bt.t())
-                self._b_ready[(spec.pos_grid, c["g"])] = True
+                self._b_ready[(spec.pos_grid, g)] = True
             gp = sv[emb + "position_embeddings"].view(-1, e)        # [1 + gin^2, E]
             gp[0].add_(dpos_rows[0])
             L.gemm_tn(b, dpos_rows[1:].contiguous(), gp[1:])
 
 
-class SamEncoderGraph(HfEncoderGraph):
+class SamEncoderGraph(EncoderGraph):
     """One trainable SAM ViTDet block stack (models/image_encoder.py:110-131 without the neck; blocks :134-197, attention :200-255, window
     partition :258-304, decomposed relative positions :307-376): ``lam_b`` / ``lam_l`` / ``lam_h``-style models with nothing frozen
     (models/lam.py:321-347).  Same machinery as the HF stack (16-bit operands, loss-scaled backward, split-K weight gradients); what is
@@ -515,6 +658,7 @@ class SamEncoderGraph(HfEncoderGraph):
     autograd operators (``DecoderGraph.conv_neck``), so ``image_encoder.neck.*`` is excluded from ``owns``."""
 
     KIND = "sam"
+    NAMES = SAM_BLOCK
 
     @staticmethod
     def owns(key: str) -> bool:
@@ -586,140 +730,53 @@ class SamEncoderGraph(HfEncoderGraph):
                 L.gemm_tn(rm, du, slot)                               # slot [L, hd] += R^T . d(R . table)
         return tabs, dtabs, fold
 
-    @torch.no_grad()
-    def forward(self, images: Tensor) -> Tensor:
-        """(Bn, 3, S, S) fp32 on the device -> the last block's state [Bn * hw, E] fp32 NHWC rows, activations kept for ``backward``."""
-        eng = self.engine()
-        spec, w, p = self.spec, eng.w32, eng.p
-        pre = "image_encoder"
-        images = images.contiguous()
-        bn, _, s, _ = images.shape
-        e, heads, g, ws = spec.dim, spec.heads, s // spec.patch, spec.window
-        if g != spec.pos_grid:
-            raise ValueError(f"the SAM stack has a fixed position embedding: image side {spec.img_size}, got {s}")
-        hw, rows = g * g, bn * g * g
-        dev, dt = images.device, eng.dt
-        a, akw = eng.patches("enc.patchA", images, rows, spec.patch)
-        res = torch.empty(rows, e, device=dev)
-        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".patch_embed.proj.bias"], res=p[pre + ".pos"], res_mod=hw, out32=res, **akw)
-        scale = spec.head_dim ** -0.5
-        hdp = self.hdp
-        ea, nh = heads * hdp, hdp // 64             # (zero-padded heads: see HfEncoderGraph.forward)
+    def _block_geo(self, i: int, c: dict) -> BlockGeo:
+        ws = self.spec.window
+        bn, g = c["bn"], c["g"]
         nw = (g + ws - 1) // ws
-        layers: List[dict] = []
-        for i in range(spec.depth):
-            bp = f"{pre}.blocks.{i}"
-            is_global = i in spec.global_idx
-            nb, gg = (bn, g) if is_global else (bn * nw * nw, ws)
-            t = gg * gg
-            arows, tpad = nb * t, _ceil(t, 64)
-            # (rel-pos tables whose length is not 2 gg - 1 are resampled like get_rel_pos does, image_encoder.py:321-330: the engine packs
-            # the resampled 16-bit tables the forward kernels read; the backward applies the transposed map, ``_rel_tables``)
-            sv = {"x_in": res, "global": is_global, "nb": nb, "g": gg, "t": t, "tpad": tpad, "arows": arows}
-            x16 = torch.empty(rows, e, device=dev, dtype=dt)
-            eng.ln(res, bp + ".norm1", 1e-6, out16=x16)
-            if is_global:
-                xa = x16
-            else:                                    # pad-after-norm windows: padded rows are zero
-                xa = torch.zeros(arows, e, device=dev, dtype=dt)
-                xa.index_copy_(0, self._win_index(bn, g, ws, dev), x16)
-            sv["xa"] = xa
-            sv["qkv"] = torch.empty(arows, 3 * ea, device=dev, dtype=dt)
-            self._qkv_plain(eng, xa, bp + ".qkv.w", sv["qkv"], ea)
-            sv["relh"] = torch.empty(nb * heads, t, gg, device=dev)
-            sv["relw"] = torch.empty(nb * heads, t, gg, device=dev)
-            L.relpos_terms(sv["qkv"], nb, heads, gg, ea, p[bp + ".tabh"], p[bp + ".tabw"], sv["relh"], sv["relw"])
-            vt = torch.zeros(nb * heads, hdp, tpad, device=dev, dtype=dt)
-            L.head_transpose(sv["qkv"], 2 * ea, nb, heads * nh, t, tpad, vt)
-            sv["ao"] = torch.empty(arows, ea, device=dev, dtype=dt)
-            sv["lse"] = torch.empty(nb * heads, tpad, device=dev)
-            L.attn_fwd_relpos_lse(sv["qkv"], vt, sv["ao"], sv["relh"], sv["relw"], sv["lse"], nb, heads, t, tpad, gg, ea, scale)
-            x_mid = torch.empty(rows, e, device=dev)
-            if is_global:
-                eng.gemm_w(sv["ao"], bp + ".proj.w", bias=w[bp + ".attn.proj.bias"], res=res, out32=x_mid)
-            else:                                    # proj on every window row, real tokens gathered back into image order
-                yw = torch.empty(arows, e, device=dev)
-                eng.gemm_w(sv["ao"], bp + ".proj.w", bias=w[bp + ".attn.proj.bias"], out32=yw)
-                L.add_cast(res, yw.index_select(0, self._win_index(bn, g, ws, dev)), rows, out32=x_mid, dt=L._DT[dt])
-            sv["x_mid"] = x_mid
-            x16b = torch.empty(rows, e, device=dev, dtype=dt)
-            sv["xnb"] = x16b
-            eng.ln(x_mid, bp + ".norm2", 1e-6, out16=x16b)
-            sv["post"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-            sv["pre"] = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-            self._fc1_fwd(eng, x16b, bp + ".lin1.w", w[bp + ".mlp.lin1.bias"], sv["pre"], sv["post"])
-            sv["fuse_fc2_bwd"] = bool(self.fused_gelu and L.gemm_fused_act_ok(rows, spec.mlp, e))      # (decided with the forward: see HfEncoderGraph)
-            res = torch.empty(rows, e, device=dev)
-            eng.gemm_w(sv["post"], bp + ".lin2.w", bias=w[bp + ".mlp.lin2.bias"], res=x_mid, out32=res)
-            layers.append(sv)
-        self.ctx = dict(images=images, layers=layers, bn=bn, g=g, hw=hw, rows=rows, e=e, ea=ea, heads=heads, scale=scale, dt=dt, ws=ws)
+        windowed = i not in self.spec.global_idx
+        nb, gg = (bn * nw * nw, ws) if windowed else (bn, g)
+        return BlockGeo(nb=nb, gg=gg, t=gg * gg, tpad=_ceil(gg * gg, 64), arows=nb * gg * gg, windowed=windowed, relpos=True)
+
+    def _enter(self, eng, c: dict) -> Tensor:
+        """res0[b, i] = patch_i W^T + b + pos[i]"""
+        spec = self.spec
+        if c["g"] != spec.pos_grid:
+            raise ValueError(f"the SAM stack has a fixed position embedding: image side {spec.img_size}, got {c['images'].shape[-1]}")
+        rows = c["bn"] * c["hw"]
+        a, akw = eng.patches("enc.patchA", c["images"], rows, spec.patch)
+        res = torch.empty(rows, c["e"], device=c["images"].device)
+        L.gemm(a, eng.p["image_encoder.patch.w"], bias=eng.w32["image_encoder.patch_embed.proj.bias"], res=eng.p["image_encoder.pos"],
+               res_mod=c["hw"], out32=res, **akw)
         return res
 
-    def _backward_scaled(self, d_out: Tensor, s: float) -> None:
+    def _leave(self, eng, c: dict, res: Tensor) -> Tensor:
+        return res                                   # the last block's state (the neck is the trainer's business)
+
+    def _leave_bwd(self, d_out: Tensor, s: float):
         c = self.ctx
-        if c is None:
-            raise RuntimeError("SamEncoderGraph.backward without a forward")
-        self._xt_key = None
-        spec, w, sv = self.spec, self.w, self.sviews
-        pre = "image_encoder"
-        bn, g, hw, rows, e, heads, dt, ws = c["bn"], c["g"], c["hw"], c["rows"], c["e"], c["heads"], c["dt"], c["ws"]
-        ea, padded = c["ea"], c["ea"] != c["e"]
-        dev = d_out.device
-        dres = torch.empty(rows, e, device=dev)
+        dres = torch.empty(c["rows"], c["e"], device=d_out.device)
         L.cast(d_out.contiguous(), dres, s)
-        d16 = torch.empty(rows, e, device=dev, dtype=dt)
+        d16 = torch.empty(c["rows"], c["e"], device=d_out.device, dtype=c["dt"])
         L.cast(dres, d16)
-        dh = torch.empty(rows, spec.mlp, device=dev)
-        dpre32 = torch.empty(rows, spec.mlp, device=dev)
-        dpre16 = torch.empty(rows, spec.mlp, device=dev, dtype=dt)
-        dxn = torch.empty(rows, e, device=dev)
-        for i in reversed(range(spec.depth)):
-            bp = f"{pre}.blocks.{i}"
-            a = c["layers"][i]
-            nb, gg, t, tpad, arows = a["nb"], a["g"], a["t"], a["tpad"], a["arows"]
-            # ---- MLP: res = x_mid + lin2(gelu(lin1(LN2(x_mid)))) -----------------------------------------------------------------
-            need32 = not (self.fast_wgrad and e % 256 == 0 and rows >= 128)
-            self._fc2_bwd(dres, d16, a, bp + ".mlp.lin2.weight", bp + ".mlp.lin2.bias", dh, dpre32 if need32 else None, dpre16)
-            self._linear_bwd(dpre32 if need32 else None, dpre16, a["xnb"], bp + ".mlp.lin1.weight", bp + ".mlp.lin1.bias", dx32=dxn)
-            L.layernorm_bwd_res(a["x_mid"], dxn, w[bp + ".norm2.weight"], w[bp + ".norm2.bias"], 1e-6, dres, dres, d16, sv[bp + ".norm2.weight"],
-                                sv[bp + ".norm2.bias"])
-            # ---- attention: x_mid = x_in + unpartition(proj(attn(partition(LN1(x_in))))) ------------------------------------------
-            if a["global"]:
-                dy16, dy32 = d16, dres
-            else:                                    # the dropped (padded) output rows receive no gradient
-                widx = self._win_index(bn, g, ws, dev)
-                dy16 = torch.zeros(arows, e, device=dev, dtype=dt)
-                dy16.index_copy_(0, widx, d16)
-                dy32 = None
-            dao = torch.empty(arows, ea, device=dev, dtype=dt)
-            self._linear_bwd(dy32, dy16, a["ao"], bp + ".attn.proj.weight", bp + ".attn.proj.bias", dx16=dao, pad_in=padded)
-            dvec = torch.empty(nb * heads, tpad, device=dev)
-            dqkv16 = torch.empty(arows, 3 * ea, device=dev, dtype=dt)
-            drelh, drelw = torch.empty_like(a["relh"]), torch.empty_like(a["relw"])
-            L.attn_bwd_relpos(a["qkv"], a["ao"], dao, None, None, None, a["lse"], dvec, dqkv16, a["relh"], a["relw"], drelh, drelw, nb, heads, t,
-                              tpad, gg, ea, c["scale"])
-            tabs, dtabs, fold = self._rel_tables(bp, gg)
-            L.relpos_bwd(a["qkv"], dqkv16, drelh, drelw, tabs[0], tabs[1], dtabs[0], dtabs[1], nb, heads, gg, ea)
-            fold()
-            dxa = torch.empty(arows, e, device=dev)
-            self._linear_bwd(None, dqkv16, a["xa"], bp + ".attn.qkv.weight", bp + ".attn.qkv.bias", dx32=dxa, pad_out=3 * heads if padded else 0)
-            dxn_i = dxa if a["global"] else dxa.index_select(0, self._win_index(bn, g, ws, dev))
-            L.layernorm_bwd_res(a["x_in"], dxn_i.contiguous(), w[bp + ".norm1.weight"], w[bp + ".norm1.bias"], 1e-6, dres, dres, d16,
-                                sv[bp + ".norm1.weight"], sv[bp + ".norm1.bias"])
-        # ---- patch embedding + absolute position embedding: res0[b, i] = patch_i W^T + b + pos[i] -------------------------------------
+        return dres, d16
+
+    def _enter_bwd(self, dres: Tensor) -> None:
+        c, spec, sv = self.ctx, self.spec, self.sviews
+        bn, hw, e = c["bn"], c["hw"], c["e"]
         k = 3 * spec.patch * spec.patch
-        a32 = torch.empty(rows, k, device=dev)
+        a32 = torch.empty(bn * hw, k, device=dres.device)
         L.im2col_patch(c["images"], spec.patch, a32)
-        self._wgrad(None, dres, a32, sv[pre + ".patch_embed.proj.weight"].view(e, k))
-        L.colsum_acc(dres, sv[pre + ".patch_embed.proj.bias"])
-        sv[pre + ".pos_embed"].view(hw, e).add_(dres.view(bn, hw, e).sum(dim=0))        # (a few thousand rows of bookkeeping)
+        self._wgrad(None, dres, a32, sv["image_encoder.patch_embed.proj.weight"].view(e, k))
+        L.colsum_acc(dres, sv["image_encoder.patch_embed.proj.bias"])
+        sv["image_encoder.pos_embed"].view(hw, e).add_(dres.view(bn, hw, e).sum(dim=0))        # (a few thousand rows of bookkeeping)
 
 
 class _EncoderFn(torch.autograd.Function):
-    """Autograd shell: forward / backward of ``HfEncoderGraph`` around the decoder graph's autograd."""
+    """Autograd shell: forward / backward of an ``EncoderGraph`` (either kind) around the decoder graph's autograd."""
 
     @staticmethod
-    def forward(ctx, graph: HfEncoderGraph, images: Tensor, anchor: Tensor):
+    def forward(ctx, graph: EncoderGraph, images: Tensor, anchor: Tensor):
         ctx.graph = graph
         return graph.forward(images)
 
@@ -729,5 +786,5 @@ class _EncoderFn(torch.autograd.Function):
         return None, None, None
 
 
-def encode_trainable(graph: HfEncoderGraph, images: Tensor, anchor: Tensor) -> Tensor:
+def encode_trainable(graph: EncoderGraph, images: Tensor, anchor: Tensor) -> Tensor:
     return _EncoderFn.apply(graph, images, anchor)

@@ -10,7 +10,24 @@ planes instead of token means (planes), no split precision, bf16, no SAM neck, w
 la_relpos_terms, padded windows); at 256 px 16 x 16 (in-kernel rel-pos, windows wider than the image); 20 x 20 windows at 640 px (the
 only windows beyond 16 slots); the reduced fixtures' sam_tiny; 80-wide heads padded to 128.  HF, 768 wide, depth 2: folded and
 LayerNorm-kernel stacks at 224 px, V^T attention, fp8 QK^T, 96 px (37 tokens: below the fold's group size), hf_tiny with a resampled
-position table, 32-wide heads padded to 64."""
+position table, 32-wide heads padded to 64.
+
+The TRAINING graphs (train_encoder.py) have a table of their own, EXPECTED_TRAIN: forward, then backward of an all-ones gradient, on two
+zero images, with the gradient slots laid out in one flat buffer as FlatAdamW does.  Each row is pinned twice: the full trace, and the
+shape trace with the storage numbers masked.  The table was recorded with the four hand-written block copies that the one block stack of
+train_encoder.py replaced (forward and _backward_scaled of HfEncoderGraph and of SamEncoderGraph); the shape digests and the full digests
+of the HF rows are from that recording, unchanged.  The full digests of the SAM rows were re-recorded with the one stack, which aliases
+what the SAM copy allocated afresh: V^T and the attention backward's dO, dq | dk | dv, D, d relh, d relw, window-order dY and dX are one
+set per block geometry (windows, global) instead of one per block, and a global block's dX of q | k | v goes where fc1's dX went, as in
+the HF copy.
+
+What the rows reach.  hf_tiny at 240 px: resampled position table, widths that are no multiple of 256 (exact-fp32 weight gradients),
+unfused GELU; at 224 px the table as stored.  HF 768 wide at 224 px: la_gemm_tn16, the fused q | k | v weight gradient, and the GELU
+epilogues with la_gemm_fused_act_ok answering yes and no; then exact-fp32 weight gradients (fast_wgrad off), transposed copies + split-K
+(tn16 off), GELU passes (fused_gelu off), the gradient slots laid out and handed over back to front (negative stride between query,
+key and value: three la_gemm_tn16 products per block on purpose, none with gsize), 32-wide heads padded to 64, bf16.  SAM: sam_tiny (one padded-window block, one global block), the same with rel-pos tables of another
+length (longer for block 0, shorter for block 1), 768 wide at 448 px (two window blocks of one geometry + one global) with the GELU
+epilogues on and off, 80-wide heads padded to 128."""
 import os
 import sys
 
@@ -46,9 +63,44 @@ EXPECTED = {
     'hf hd32 160': (19, '0fc307c677c6ebd002ffed0a3518237d7dbfd690bae86ced86831027c31d717c'),
 }
 
+# name: (number of lines, sha256 of the full trace, sha256 of the shape trace) - python tools/encoder_trace.py --train-table
+EXPECTED_TRAIN = {
+    'train hf_tiny 240': (104, 'f00bf8744e831e965485a6433101432edc5aa199ebf52806d7d9995f99445787',
+                              '56925bb9c4d90f9db792e5cbf00dda00d6ca14ab1da68c9fd66ff27067172f70'),
+    'train hf_tiny 224': (102, '55a559359d346be20330a65e7fa3624c612b0dc9421c08d32eca1451543851f3',
+                              '5f70876bfd853b7ccf47fadb1dfa17c3cae7cac1f3dd8e8961f6062fcc0bb112'),
+    'train hf 224 fused act': (62, 'db52b4b3da498636eb047f15e900cc5192b7dd5770ec131d2fd10239b99883e2',
+                                   '36e89dd2e3ba63d05a94798b4976e451dbaec1d6ec1ef40ccaddd80548224e75'),
+    'train hf 224 unfused act': (66, '07812948169e2f139577c942d10c1411ca93f053f114f7fdadeb2c28fdb2e08d',
+                                     'b1fdd319ac0087506356b8570495358e6963edf3dbc77b319926d5a43a7dfc97'),
+    'train hf 224 exact wgrad': (98, 'bf9eb3a127f86222056bffd117fd1b2f7cd79e5e08091c8e15bff0b05b58e4b2',
+                                     'd06ab4be073ce180c92a7148854e49f682c4f3340271694c3d65243d636c4f16'),
+    'train hf 224 no tn16': (78, 'df58d7ae6d38848928aa45bc47dd09b5c58df79edfdf30f413d3acb995a468d3',
+                                 'd33d77d5b22373f49b1c2e4063760a4e4c1655d4e0c10446fb975912bca15dcb'),
+    'train hf 224 no fused gelu': (62, '0b5e0c3d35071acae614dae9fb55bb357d4c5d39c0d1eb21624b30e6d215fc7f',
+                                       'e7c0ad9e52cc7e340c5338c155d6423d2385a520cbb8a4ef5db2caf3a95c2190'),
+    'train hf 224 reversed slots': (66, 'c2a9e2993663088318084935f68afbdeaf76e5d57c83d20b3f24a8e3dfb6fad6',
+                                        '5ccead187f6499b34492ea8fd981b79518e395b866abb360edf0932258ac3ed3'),
+    'train hf hd32 160': (104, '6f3845d2c07e70d12ed18d154181acdea65a790e265334cfffbddc1efe5a45ac',
+                              '6fa9fa943861fb64ac315c422baa0699f490e9b8c177aaf8eca05fc2be8c4cbc'),
+    'train hf 224 bf16': (62, 'e4764caf4b279f1f421a3d8ae4ccbfb75a3cdf28443006739cbcbd73ebebf0b9',
+                              'd74be701ced495b27c9c587fdd4667cfb5b6cbd25694440f3c612d988b3ae60d'),
+    'train sam_tiny': (92, '6d7efaf2bff2d973e6195562d0c80517de06632ff5ff78cb0d7bd9608358ebd9',
+                           'db723e8463cca01412773bfb37a8be3fbe6dbef99993b6f7e12a30f56791d3d4'),
+    'train sam_tiny resampled rel-pos': (100, '8c44b4c25fb5c2c8e9bb448cee5da959181f9042bc22549b0516685285b35821',
+                                             '5ad3437b1af68f77c35bb6014b7cb3ff3b007440e843b5893c440b05385bfdea'),
+    'train sam 448 fused act': (94, '7796d8ed3c7ee70a5f95612d773de60862503085329ee189026eaa793ac834ee',
+                                    'b45df100cb321352bc71ae0b2dd0c43c9dfef603e51961dbd5b81fb3eb1aa0e6'),
+    'train sam 448 unfused act': (100, '2ede3a32bc399b789746cbe9dd415dce90e94585ab4b379cc6e1711cb66b181c',
+                                      '94d48e7b85117ec692370506434fa0d2303028fc5aea9bf97e1cb85f4031d09c'),
+    'train sam hd80 448': (90, '09315ed0d8cf3925d65957fb811f846fecd1b8ef7469cedb2fde106000c272e2',
+                               '18b3eb1b5aa65ea525d915cf0406ba7afd5e641732c9076079b0355d1297e91a'),
+}
+
 
 def test_the_table_covers_the_matrix():
     assert list(T.matrix()) == list(EXPECTED)
+    assert list(T.train_matrix()) == list(EXPECTED_TRAIN)
 
 
 @pytest.mark.parametrize("name", list(EXPECTED))
@@ -58,3 +110,13 @@ def test_encoder_launch_trace_is_unchanged(name, monkeypatch):
         print(f"launch trace of {name!r} changed: {got} != {EXPECTED[name]}; inspect it with\n"
               f"  python tools/encoder_trace.py --print {name!r}")
     assert got == EXPECTED[name]
+
+
+@pytest.mark.parametrize("name", list(EXPECTED_TRAIN))
+def test_training_graph_launch_trace_is_unchanged(name, monkeypatch):
+    rec = T.train_trace(T.train_matrix()[name], monkeypatch.setattr)
+    got = rec.digest() + rec.digest(shape=True)[1:]
+    if got != EXPECTED_TRAIN[name]:
+        print(f"training launch trace of {name!r} changed: {got} != {EXPECTED_TRAIN[name]}; inspect it with\n"
+              f"  python tools/encoder_trace.py --print {name!r}")
+    assert got == EXPECTED_TRAIN[name]

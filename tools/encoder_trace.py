@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Launch trace of the image-encoder driver, on the CPU.
+"""Launch trace of the image-encoder drivers, on the CPU.
 
 Every public function of ``labelanything_amd._lib`` is replaced by a recorder, so ``LamEngine.encode_images`` runs without a GPU and
 leaves one line per launch: the function and every argument that is not at its default, under the name the launcher's signature gives
@@ -8,7 +8,12 @@ by first appearance in the trace) and storage offset.  A last line holds what th
 launch the same kernels with the same arguments, in the same order, on the same buffers and aliases - what
 tests/test_encoder_trace_cpu.py pins for the matrix below.
 
+A second matrix (``train_matrix``) does the same for the TRAINING graphs of ``train_encoder.py``: forward, then backward of an all-ones
+gradient, with the gradient slots laid out in one flat buffer as FlatAdamW does.  Each of its rows is pinned twice: the full trace, and
+a shape trace whose storage numbers are masked (which launches, on which shapes - whatever the buffers alias).
+
   python tools/encoder_trace.py --table             name, number of calls, sha256 of the trace for the whole matrix
+  python tools/encoder_trace.py --train-table       the same for the training matrix: full and shape digest per row
   python tools/encoder_trace.py --print NAME        one trace
   python tools/encoder_trace.py --packed NAME       key, shape, dtype, sha256 of the bytes of every packed weight of NAME's engine
 """
@@ -44,19 +49,26 @@ def _is_default(v, default) -> bool:
 class Recorder:
     """Stands in for the library: ``patch(setattr)`` replaces every public function of ``_lib`` with one that appends a line here."""
 
-    def __init__(self):
+    def __init__(self, returns=None):
         self.lines = []
+        self.shape_lines = []    # the same trace with the storage numbers masked
+        self.returns = returns or {}          # launcher name -> what its stand-in returns (default None)
         self._storages = {}
         self._keep = []          # a freed storage's address would be reused and renumber the trace: hold every tensor seen
 
-    def _fmt(self, v) -> str:
+    def _fmt(self, v, mask: bool = False) -> str:
         if isinstance(v, torch.Tensor):
             self._keep.append(v)
             n = self._storages.setdefault(v.untyped_storage().data_ptr(), len(self._storages))
-            return f"T({tuple(v.shape)},{str(v.dtype)[6:]},{tuple(v.stride())},s{n}+{v.storage_offset()})"
+            return f"T({tuple(v.shape)},{str(v.dtype)[6:]},{tuple(v.stride())},s{'*' if mask else n}+{v.storage_offset()})"
         if isinstance(v, (tuple, list)):
-            return "(" + ",".join(self._fmt(x) for x in v) + ")"
+            return "(" + ",".join(self._fmt(x, mask) for x in v) + ")"
         return repr(v)
+
+    def note(self, head: str, items) -> None:
+        """One trace line: ``head`` and (name, value) pairs, in the full and in the shape trace."""
+        for lines, mask in ((self.lines, False), (self.shape_lines, True)):
+            lines.append(" ".join([head] + [f"{k}={self._fmt(v, mask)}" if k else self._fmt(v, mask) for k, v in items]))
 
     def _stub(self, name: str):
         def call(*args, **kw):
@@ -64,10 +76,10 @@ class Recorder:
             # one left out, record the same launch: signature order, then the other keywords sorted; defaults are not printed
             named = LAUNCHERS[name].bind(*args, **kw).arguments
             extra = named.pop("epilogue", {})
-            parts = [f"{k}={self._fmt(v)}" for k, v in named.items() if not _is_default(v, LAUNCHERS[name].parameters[k].default)]
-            parts += [f"{k}={self._fmt(extra[k])}" for k in sorted(extra) if not _is_default(extra[k], EPILOGUE[k])]
-            self.lines.append(f"{name} " + " ".join(parts))
-            return args[0] if name == "twoway_pe_layout" else None
+            items = [(k, v) for k, v in named.items() if not _is_default(v, LAUNCHERS[name].parameters[k].default)]
+            items += [(k, extra[k]) for k in sorted(extra) if not _is_default(extra[k], EPILOGUE[k])]
+            self.note(name, items)
+            return args[0] if name == "twoway_pe_layout" else self.returns.get(name)
         return call
 
     def patch(self, setattr_) -> None:
@@ -75,8 +87,9 @@ class Recorder:
         for name in LAUNCHERS:
             setattr_(L, name, (lambda: None) if name == "lib" else self._stub(name))
 
-    def digest(self):
-        return len(self.lines), hashlib.sha256("\n".join(self.lines).encode()).hexdigest()
+    def digest(self, shape: bool = False):
+        lines = self.shape_lines if shape else self.lines
+        return len(lines), hashlib.sha256("\n".join(lines).encode()).hexdigest()
 
 
 def _wide(kind: str, depth: int, **kw) -> EncoderSpec:
@@ -157,7 +170,80 @@ def trace(row: dict, setattr_=setattr) -> Recorder:
     s = row["cfg"]["image_size"]
     images = torch.zeros(2, 3, s, s)
     out = eng.sam_encoder(images, want_last_block=True) if row["last"] else eng.encode_images(images)
-    rec.lines.append("return " + rec._fmt(out))          # which buffers the caller gets
+    rec.note("return", [("", out)])          # which buffers the caller gets
+    return rec
+
+
+def train_matrix() -> dict:
+    """name -> configuration of one training-graph row.  Two images each, the smallest shape that reaches the row's path; see the
+    module docstring of tests/test_encoder_trace_cpu.py."""
+    fused, unfused = {"gemm_fused_act_ok": True}, {"gemm_fused_act_ok": False}
+
+    def row(base: dict, returns=None, dtype=torch.float16, reverse=False, relpos=False, **attrs) -> dict:
+        return dict(cfg=base["cfg"], returns=returns, dtype=dtype, reverse=reverse, relpos=relpos, attrs=attrs)
+
+    hf_tiny, sam_tiny = dict(enc="hf_tiny", dim=128), dict(enc="sam_tiny", image_embed_dim=96)
+    return {
+        "train hf_tiny 240": row(_hf(240, **hf_tiny)),
+        "train hf_tiny 224": row(_hf(224, **hf_tiny)),
+        "train hf 224 fused act": row(_hf(224), fused),
+        "train hf 224 unfused act": row(_hf(224), unfused),
+        "train hf 224 exact wgrad": row(_hf(224), fused, fast_wgrad=False),
+        "train hf 224 no tn16": row(_hf(224), fused, tn16=False),
+        "train hf 224 no fused gelu": row(_hf(224), fused, fused_gelu=False),
+        "train hf 224 reversed slots": row(_hf(224), fused, reverse=True),
+        "train hf hd32 160": row(_hf(160, enc="trace_hf_hd32", dim=128)),
+        "train hf 224 bf16": row(_hf(224), fused, dtype=torch.bfloat16),
+        "train sam_tiny": row(_sam(224, **sam_tiny)),
+        "train sam_tiny resampled rel-pos": row(_sam(224, **sam_tiny), relpos=True),
+        "train sam 448 fused act": row(_sam(448), fused),
+        "train sam 448 unfused act": row(_sam(448), unfused),
+        "train sam hd80 448": row(_sam(448, enc="trace_sam_hd80", image_embed_dim=64)),
+    }
+
+
+def train_graph(row: dict):
+    """The training graph of one row on the CPU (call under a patched ``_lib``), its gradient slots views of ONE flat fp32 buffer in
+    ``named_parameters`` order as FlatAdamW packs them.  reverse: laid out AND handed to the graph back to front - the graph's scratch
+    follows the order it is given the slots in, and ``_qkv_wgrad_fused`` decides from the distances between the scratch views: query, key
+    and value then sit a negative stride apart, and one product per tensor runs."""
+    from labelanything_amd.models import Lam
+    from labelanything_amd import train_encoder as TE
+    _specs()
+    cfg = LamConfig(spatial_convs=3, custom_preprocess=False, **row["cfg"])
+    lam = Lam(cfg, seed=0, compute_dtype=row["dtype"])
+    if row["relpos"]:           # tables of another grid: longer ones for the window block, shorter ones for the global block
+        for k, v in [(k, v) for k, v in lam.named_parameters() if "rel_pos" in k]:
+            mod, leaf = k.rsplit(".", 1)
+            setattr(lam.get_submodule(mod), leaf, torch.nn.Parameter(torch.zeros(v.shape[0] + (8 if ".blocks.0." in k else -6), v.shape[1])))
+    named = [(k, p) for k, p in lam.named_parameters() if k.startswith("image_encoder.")]
+    flat = torch.zeros(sum(p.numel() for _, p in named))
+    views, off = {}, 0
+    for k, p in (reversed(named) if row["reverse"] else named):
+        views[k] = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    cls = TE.SamEncoderGraph if cfg.encoder_spec.kind == "sam" else TE.HfEncoderGraph
+    # (numerics as LamTrainer chooses them: no token-mean corrections in the saved-activation forward)
+    graph = cls(lam, views, precise=tuple(g for g in lam.precise if g not in ("vmean", "projmean")))
+    for k, v in row["attrs"].items():
+        assert hasattr(graph, k), k
+        setattr(graph, k, v)
+    return graph
+
+
+def train_trace(row: dict, setattr_=setattr) -> Recorder:
+    """Forward, then backward of an all-ones gradient, of one training row under a fresh recorder.  ``torch.empty`` is ``torch.zeros``
+    meanwhile: the host reads a few buffers back (the finite check of the loss-scale loop), which must not see what a recycled
+    allocation holds."""
+    rec = Recorder(row["returns"])
+    rec.patch(setattr_)
+    setattr_(torch, "empty", torch.zeros)
+    setattr_(torch, "empty_like", torch.zeros_like)
+    graph = train_graph(row)
+    s = row["cfg"]["image_size"]
+    out = graph.forward(torch.zeros(2, 3, s, s))
+    rec.note("return", [("", out)])
+    graph.backward(torch.ones_like(out))
     return rec
 
 
@@ -175,6 +261,7 @@ def main() -> None:
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--print", dest="show", metavar="NAME")
     g.add_argument("--table", action="store_true")
+    g.add_argument("--train-table", action="store_true")
     g.add_argument("--packed", metavar="NAME")
     a = ap.parse_args()
     rows = matrix()
@@ -182,6 +269,13 @@ def main() -> None:
         for name, row in rows.items():
             n, h = trace(row).digest()
             print(f"{name!r}: ({n}, {h!r}),")
+    elif a.train_table:
+        for name, row in train_matrix().items():
+            rec = train_trace(row)
+            n, h = rec.digest()
+            print(f"{name!r}: ({n}, {h!r},\n{'':{len(name) + 9}}{rec.digest(shape=True)[1]!r}),")
+    elif a.show in train_matrix():
+        print("\n".join(train_trace(train_matrix()[a.show]).lines))
     elif a.show:
         print("\n".join(trace(rows[a.show]).lines))
     else:
