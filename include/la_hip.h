@@ -607,6 +607,35 @@ int la_attn_fwd_cs(const void* qkv, const void* vt, void* out16, const float* re
 int la_attn_fwd_rows(const void* qkv, void* out16, const void* tabh, const void* tabw, int B, int heads, int T, int Tpad, int G, int E,
                      float scale, int mode, float* cspart, int imgH, int imgW, const void* padrow, int dt, void* stream);
 
+/* ---- what an encoder-attention call launches (csrc/attn_plan.h: attn_fwd_plan / attn_bwd_plan, one pure host function per direction) ----
+ * LaAttnCall: the union of the entry points' arguments (scales and the stream decide nothing); an entry point leaves what it does not take
+ * at zero.  The pointers are only tested for NULL, never read - any address will do.
+ * LaAttnLaunch: kernel = family; mode = its bias form (the ATTN_* / ATTN_BWD_* / ATTN_DKV_* constants of csrc/attn_plan.h: template
+ * argument MODE / BIAS; 0 for the la_relpos_bwd kernels); nh = head width / 64, vrow = V tiles row-major from qkv (forward tile kernel) -
+ * template arguments too; grid, block, lds_bytes = workgroups, threads per workgroup, dynamic LDS.
+ * LaAttnPlan: launch[0 .. n) in order, the last repeated `repeat` times (la_relpos_bwd: once per 64-column block of the head); ry =
+ * query rows per workgroup of LA_ATTN_K_RELPOS_BWD. */
+enum { LA_ATTN_EP_FWD = 0 /* and la_attn_fwd_cs */, LA_ATTN_EP_FWD_ROWS, LA_ATTN_EP_FWD_LSE, LA_ATTN_EP_FWD_RELPOS_LSE,
+       LA_ATTN_EP_BWD, LA_ATTN_EP_BWD_RELPOS, LA_ATTN_EP_RELPOS_BWD };
+enum { LA_ATTN_K_FWD = 0, LA_ATTN_K_WINDOW, LA_ATTN_K_BWD_DQ, LA_ATTN_K_BWD_DKV, LA_ATTN_K_RELPOS_BWD_ROWS, LA_ATTN_K_RELPOS_BWD };
+typedef struct LaAttnCall {
+  const void *qkv, *vt, *out16, *relh, *relw, *tabh, *tabw, *lse, *cspart, *padrow;      /* forward (tabh / tabw: la_relpos_bwd too) */
+  const void *dout16, *dvec, *dqkv, *drelh, *drelw, *dtabh, *dtabw;                       /* backward */
+  int B, heads, T, Tpad, G, E, mode, csH, csW, imgH, imgW, dt;
+} LaAttnCall;
+typedef struct LaAttnLaunch {
+  int kernel, mode, nh, vrow, grid, block, lds_bytes;
+} LaAttnLaunch;
+typedef struct LaAttnPlan {
+  LaAttnLaunch launch[2];
+  int n, repeat, ry;
+} LaAttnPlan;
+
+/* The entry point's decision without the launch: its checks and error texts, then *out.  entry = LA_ATTN_EP_FWD .. _FWD_RELPOS_LSE for
+ * la_attn_fwd_plan, LA_ATTN_EP_BWD .. _RELPOS_BWD for la_attn_bwd_plan.  Needs no GPU. */
+int la_attn_fwd_plan(int entry, const LaAttnCall* call, LaAttnPlan* out);
+int la_attn_bwd_plan(int entry, const LaAttnCall* call, LaAttnPlan* out);
+
 /* out[g * ldo + c] = inv * sum over the chunks j of part[(g * chunks + j) * D + c], added in index order (fp32). */
 int la_colsum_fold(const float* part, int groups, int chunks, int D, float inv, float* out, int ldo, void* stream);
 

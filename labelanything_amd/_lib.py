@@ -76,6 +76,7 @@ EXPORTS = [
     "la_mfma_shape_probe",
     "la_mask_embed_pooled",
     "la_stream_mlp", "la_stream_mlp_ok",
+    "la_attn_fwd_plan", "la_attn_bwd_plan",
 ]
 
 
@@ -195,6 +196,53 @@ def gemm_plan(a, lda: int, w, ldw: int, m: int, n: int, k: int, dt: int, ncu: in
                             C.c_int(dt), C.c_int(ncu), C.byref(plan))
     _check(rc, "la_gemm_plan")
     return plan
+
+
+_ATTN_CALL_PTRS = ("qkv", "vt", "out16", "relh", "relw", "tabh", "tabw", "lse", "cspart", "padrow", "dout16", "dvec", "dqkv", "drelh", "drelw", "dtabh",
+                   "dtabw")
+_ATTN_CALL_INTS = ("B", "heads", "T", "Tpad", "G", "E", "mode", "csH", "csW", "imgH", "imgW", "dt")
+
+
+class LaAttnCall(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in _ATTN_CALL_PTRS] + [(f, C.c_int) for f in _ATTN_CALL_INTS]
+
+
+class LaAttnLaunch(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("kernel", "mode", "nh", "vrow", "grid", "block", "lds_bytes")]
+
+
+class LaAttnPlan(C.Structure):
+    _fields_ = [("launch", LaAttnLaunch * 2), ("n", C.c_int), ("repeat", C.c_int), ("ry", C.c_int)]
+
+
+# LaAttnPlan entry points (LA_ATTN_EP_*), kernel families (LA_ATTN_K_*) and the bias forms of csrc/attn_plan.h (LaAttnLaunch.mode)
+ATTN_ENTRIES = ("attn_fwd", "attn_fwd_rows", "attn_fwd_lse", "attn_fwd_relpos_lse", "attn_bwd", "attn_bwd_relpos", "relpos_bwd")
+ATTN_KERNELS = ("FWD", "WINDOW", "BWD_DQ", "BWD_DKV", "RELPOS_BWD_ROWS", "RELPOS_BWD")
+ATTN_FWD_MODES = ("NOBIAS", "TERMS", "TERMS_ROW64", "TABLES_WIN", "TABLES_ROW64", "TABLES_WIN16")
+ATTN_BWD_MODES = ("NOBIAS", "TERMS", "ROW64", "WIN16")
+ATTN_DKV_MODES = ("NOBIAS", "TERMS", "STAGED")
+
+
+def _attn_plan(fn, entry: str, **call) -> LaAttnPlan:
+    c, plan = LaAttnCall(), LaAttnPlan()
+    for k, v in call.items():
+        setattr(c, k, _addr(v))
+    _check(fn(C.c_int(ATTN_ENTRIES.index(entry)), C.byref(c), C.byref(plan)), fn.__name__)
+    return plan
+
+
+def attn_fwd_plan(entry: str, **call) -> LaAttnPlan:
+    """la_attn_fwd_plan: what the forward entry point ``entry`` (``attn_fwd`` - also ``attn_fwd_cs`` -, ``attn_fwd_rows``, ``attn_fwd_lse``,
+    ``attn_fwd_relpos_lse``) would launch for the LaAttnCall fields given as keywords (B, heads, T, Tpad, G, E, mode, dt, buffers, ...;
+    the rest zero), with its argument errors and no launch.  Buffers are tensors or plain integer addresses - only tested for None -, so
+    this runs without a GPU."""
+    return _attn_plan(lib().la_attn_fwd_plan, entry, **call)
+
+
+def attn_bwd_plan(entry: str, **call) -> LaAttnPlan:
+    """la_attn_bwd_plan: the same for ``attn_bwd``, ``attn_bwd_relpos`` (two launches: dq, then dk / dv) and ``relpos_bwd`` (one launch,
+    ``plan.repeat`` times)."""
+    return _attn_plan(lib().la_attn_bwd_plan, entry, **call)
 
 
 def mfma_shape_probe(a: torch.Tensor, w: torch.Tensor, shape: int) -> torch.Tensor:

@@ -14,11 +14,11 @@
 #include <cstdlib>
 #include "la_common.h"
 #include "../../include/la_hip.h"
+#include "attn_plan.h"
 
 namespace la {
 
 constexpr float BWD_NEG_BIG = -1.0e30f;
-constexpr int TILE_B = 64 * 64 * 2;      // one 64 x 64 16-bit tile: 8 KiB, 128-byte rows, XOR swizzled (swz_off)
 
 struct AttnBwdEncArgs {
   const void* qkv;      // [B*T, 3E] 16-bit: q | k | v rows
@@ -130,11 +130,11 @@ template <typename T> __device__ __forceinline__ float dot8(uint4 a, uint4 b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// BIAS 0: plain.  BIAS 1: rel-pos bias, any G <= 32 (per-wave LDS tables of the wave's 32 query rows, as the forward's MODE 1; the bias
-// gradients are scatter-added into a second pair of tables with ds_add_f32 - the two half-lanes of a query row hit the same entries).
-// BIAS 3: G <= 16 (the 14 x 14 windows) - no per-score work at all: the bias enters S^T as the product E R on the matrix pipe (R in hi + lo
-// 16-bit parts: exact to 2^-22), and d relh | d relw = E^T dS^T accumulates beside dQ^T from the same dS^T fragments.
-// BIAS 2: G == 64 - a 64-key tile is exactly one key row: relh[q][tile] is one scalar per tile, relw[q][0..63] lives in the 32 score
+// BIAS: the ATTN_BWD_* constants of attn_plan.h.  TERMS: rel-pos bias, any G <= 32 (per-wave LDS tables of the wave's 32 query rows, as the
+// forward's ATTN_TERMS; the bias gradients are scatter-added into a second pair of tables with ds_add_f32 - the two half-lanes of a query
+// row hit the same entries).  WIN16: G <= 16 (the 14 x 14 windows) - no per-score work at all: the bias enters S^T as the product E R on the
+// matrix pipe (R in hi + lo 16-bit parts: exact to 2^-22), and d relh | d relw = E^T dS^T accumulates beside dQ^T from the same dS^T fragments.
+// ROW64: G == 64 - a 64-key tile is exactly one key row: relh[q][tile] is one scalar per tile, relw[q][0..63] lives in the 32 score
 // registers' positions for the whole kernel, d relw accumulates in 32 more registers and d relh[q][tile] is one store per tile.
 // NH = head width / 64 (1 or 2): a 128-wide head (SAM ViT-H's 80 zero-padded by the packed weights, engine.py head_pad) is two 64-wide
 // halves everywhere - NH K tiles + NH V tiles per stage, 4 NH k-slices of S^T / dP^T, 2 NH accumulator tiles of dQ^T - on one wave per SIMD.
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
   const int* keyinfo = nullptr;
   f32x16 rw[2], drw[2];         // BIAS 2: relw / d relw of the lane's 32 key columns
   const float* rhq = nullptr;
-  if (BIAS == 1) {
+  if (BIAS == ATTN_BWD_TERMS) {
     float* tab = reinterpret_cast<float*>(smem + 2 * STAGE);
     my_bh = tab + wave * 4 * 32 * GS;
     for (int idx = lane; idx < 32 * G; idx += 64) {
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
   f32x16 drel;                  // d R[c][q] = sum_key E^T[c][key] dS^T[key][q]
   const char* et = nullptr;     // E^T [32][Tpad] 16-bit in LDS, rows padded by 16 bytes
   int ETS = 0;
-  if (BIAS == 3) {
+  if (BIAS == ATTN_BWD_WIN16) {
     ETS = a.Tpad * 2 + 16;
     char* etw = smem + 2 * STAGE;
     int* ki = reinterpret_cast<int*>(etw + 32 * ETS);
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
 #pragma unroll
     for (int r = 0; r < 16; ++r) drel[r] = 0.f;
   }
-  if (BIAS == 2) {
+  if (BIAS == ATTN_BWD_ROW64) {
     rhq = a.relh + ((size_t)bh * T_ + qc) * 64;
     const float* p = a.relw + ((size_t)bh * T_ + qc) * 64;
 #pragma unroll
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[t][r] = dp[t][r] = 0.f;
-      if (BIAS == 3) {
+      if (BIAS == ATTN_BWD_WIN16) {
         // the lane's key row of E: a one at c = key row (first k-step) and at c = 16 + key column (second); this lane holds c = fh*8 .. +8
         const int info = keyinfo[j * 64 + t * 32 + fr];
         const uint32_t one = pack2<T>(1.0f, 0.0f);
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
     }
     const bool tail = j * 64 + 64 > T_;
     float rh = 0.f, drh = 0.f;
-    if (BIAS == 2) rh = rhq[j];
+    if (BIAS == ATTN_BWD_ROW64) rh = rhq[j];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -335,25 +335,25 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
         const int key = j * 64 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
         float sraw = s[t][r];
         int info = 0;
-        if (BIAS == 1) {
+        if (BIAS == ATTN_BWD_TERMS) {
           info = keyinfo[key];
           sraw += (my_bh[fr * GS + (info >> 16)] + my_bh[(32 + fr) * GS + (info & 0xffff)]) * inv_c;
         }
-        if (BIAS == 2) sraw += (rh + rw[t][r]) * inv_c;
+        if (BIAS == ATTN_BWD_ROW64) sraw += (rh + rw[t][r]) * inv_c;
         const float sv_ = (tail && key >= T_) ? BWD_NEG_BIG : sraw;
         const float p = __builtin_amdgcn_exp2f(fmaf(sv_, c2, -lse2));
         const float dsv = p * (dp[t][r] - dsum);   // dS^T (before the 1/sqrt(d) factor, applied at the end)
         s[t][r] = dsv;
-        if (BIAS == 1 && q < T_ && !(tail && key >= T_)) {
+        if (BIAS == ATTN_BWD_TERMS && q < T_ && !(tail && key >= T_)) {
           atomicAdd(&my_bh[(64 + fr) * GS + (info >> 16)], dsv);
           atomicAdd(&my_bh[(96 + fr) * GS + (info & 0xffff)], dsv);
         }
-        if (BIAS == 2) {
+        if (BIAS == ATTN_BWD_ROW64) {
           drh += dsv;
           drw[t][r] += dsv;
         }
       }
-    if (BIAS == 2) {
+    if (BIAS == ATTN_BWD_ROW64) {
       drh += __shfl_xor(drh, 32, 64);
       if (q < T_ && fh == 0) a.drelh[((size_t)bh * T_ + q) * 64 + j] = drh;
     }
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
         const uint4 ktf = tr_frag(sk_lds + (d >> 1) * TILE_B, tro, d & 1, ks);      // K^T[32 d .. + 32][keys 16 ks .. + 16] out of the row-major K tiles
         acc[d] = Half16<T>::mfma32(ktf, dsf[ks], acc[d]);
       }
-    if (BIAS == 3) {
+    if (BIAS == ATTN_BWD_WIN16) {
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const uint4 etf = *reinterpret_cast<const uint4*>(et + fr * ETS + (j * 64 + ks * 16 + fh * 8) * 2);
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
         *reinterpret_cast<uint2*>(op + d * 32 + 8 * g4 + 4 * fh) = v;
       }
   }
-  if (BIAS == 2 && q < T_) {
+  if (BIAS == ATTN_BWD_ROW64 && q < T_) {
     float* p = a.drelw + ((size_t)bh * T_ + q) * 64;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
         *reinterpret_cast<float4*>(p + t * 32 + 8 * g4 + 4 * fh) =
             make_float4(drw[t][g4 * 4 + 0], drw[t][g4 * 4 + 1], drw[t][g4 * 4 + 2], drw[t][g4 * 4 + 3]);
   }
-  if (BIAS == 3 && q < T_) {
+  if (BIAS == ATTN_BWD_WIN16 && q < T_) {
     // register r of the accumulator is c = (r & 3) + 8 (r >> 2) + 4 fh: r < 8 the key rows, r >= 8 the key columns
     float* ph = a.drelh + ((size_t)bh * T_ + q) * G;
     float* pw = a.drelw + ((size_t)bh * T_ + q) * G;
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
       }
     }
   }
-  if (BIAS == 1) {
+  if (BIAS == ATTN_BWD_TERMS) {
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     for (int idx = lane; idx < 32 * G; idx += 64) {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dq_kernel(Att
 // ---------------------------------------------------------------------------------------------------------------------------
 // BIAS: the rel-pos terms of (query register, key lane) are read straight from the fp32 term arrays (a fixed register = one query row:
 // the 64 keys of the wave read inside one <= 256-byte row of relh / relw)
-// BIAS 0: none.  1: the two terms of a score read from global memory (odd G: rows of 64 queries are not 16-byte aligned).  2: staged in LDS.
+// BIAS: the ATTN_DKV_* constants of attn_plan.h (none / the two terms of a score read from global memory / staged in LDS).
 template <typename T, int BIAS, int NH>
 __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dkv_kernel(AttnBwdEncArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dkv_kernel(At
   // queries - relw rows [64][G] fp32 (16 KiB at G = 64) and relh: [64][G] for G <= 32, the 4-column group that holds this workgroup's
   // two key rows [64][4] for G = 64 (a workgroup = 128 keys = two key rows) - staged by LDS-DMA like the tiles (round 4 read two terms per
   // score from global memory: 64 vector-memory instructions per tile and wave)
-  constexpr int BIAS_B = BIAS == 2 ? 16384 + 1024 : 0;      // G = 64: relw 16 KiB + relh 1 KiB; G <= 32: relw <= 8 KiB, relh <= 8 KiB behind it
+  constexpr int BIAS_B = BIAS == ATTN_DKV_STAGED ? 16384 + 1024 : 0;     // G = 64: relw 16 KiB + relh 1 KiB; G <= 32: relw <= 8 KiB, relh <= 8 KiB behind it
   constexpr int STAGE = 2 * NH * TILE_B + 512 + BIAS_B;      // (NH tiles of 64 dims each for Q and for dO)
   constexpr int HDT = 64 * NH, KS = 4 * NH;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : 1)) void attn_bwd_dkv_kernel(At
   const int kh_l = kc / G, kw_l = kc % G;
   const float inv_c = 1.0f / a.scale;
   // staged bias terms need 16-byte aligned rows of 64 queries: (bh T + 64 i) G % 4 == 0 - every even G (the 14 x 14 windows, 64 x 64)
-  constexpr bool stage_bias = BIAS == 2;
+  constexpr bool stage_bias = BIAS == ATTN_DKV_STAGED;
   const int relh_cols = G == 64 ? 4 : G;                                       // staged relh row length
   const int relh_c0 = G == 64 ? ((2 * kblk) & ~3) : 0;                          // first staged relh column
   const long rel_total = (long)a.B * a.heads * T_ * G;                          // floats in relh / relw
@@ -635,45 +635,6 @@ __global__ __launch_bounds__(256) void head_transpose_kernel(const T* __restrict
     T* p = dst + ((size_t)bh * 64 + d) * Tpad + t0 + t8;
     *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(&o[0]);
     *reinterpret_cast<uint4*>(p + 8) = *reinterpret_cast<const uint4*>(&o[8]);
-  }
-}
-
-// launch both backward kernels (dq first: it writes D); bias 0 plain, 1 rel-pos G <= 32, 2 rel-pos G == 64
-template <typename T, int BIAS, int NH>
-static void launch_attn_bwd_nh(const AttnBwdEncArgs& a, hipStream_t st) {
-  const int nblk = (a.T + 127) / 128 * a.B * a.heads;
-  const int lds_dq = 2 * 2 * NH * TILE_B + (BIAS == 1   ? 4 * 4 * 32 * (a.G + 1) * (int)sizeof(float) + a.Tpad * (int)sizeof(int)
-                                           : BIAS == 3 ? 32 * (a.Tpad * 2 + 16) + a.Tpad * (int)sizeof(int)
-                                                       : 0);
-  static unsigned long long m1 = 0, m2 = 0, m3 = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(attn_bwd_dq_kernel<T, BIAS, NH>), 160 * 1024, m1);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, BIAS, NH>), dim3(nblk), dim3(256), lds_dq, st, a);
-  if (BIAS != 0 && (a.G & 1) == 0) {           // staged bias terms: even G (16-byte aligned rows of 64 queries)
-    constexpr int LDS_DKV = 2 * (2 * NH * TILE_B + 512 + 16384 + 1024);      // 67 KiB: two workgroups per CU (wide heads: 99 KiB, one)
-    ensure_dyn_lds(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<T, 2, NH>), LDS_DKV, m3);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 2, NH>), dim3(nblk), dim3(256), LDS_DKV, st, a);
-  } else {
-    constexpr int LDS_DKV = 2 * (2 * NH * TILE_B + 512);
-    ensure_dyn_lds(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<T, (BIAS != 0 ? 1 : 0), NH>), LDS_DKV, m2);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, (BIAS != 0 ? 1 : 0), NH>), dim3(nblk), dim3(256), LDS_DKV, st, a);
-  }
-}
-template <typename T, int BIAS>
-static void launch_attn_bwd_t(const AttnBwdEncArgs& a, hipStream_t st) {
-  if (a.E == a.heads * 128) launch_attn_bwd_nh<T, BIAS, 2>(a, st);
-  else launch_attn_bwd_nh<T, BIAS, 1>(a, st);
-}
-static void launch_attn_bwd(const AttnBwdEncArgs& a, int bias, int dt, hipStream_t st) {
-  if (dt == LA_F16) {
-    if (bias == 0) launch_attn_bwd_t<f16_t, 0>(a, st);
-    else if (bias == 1) launch_attn_bwd_t<f16_t, 1>(a, st);
-    else if (bias == 3) launch_attn_bwd_t<f16_t, 3>(a, st);
-    else launch_attn_bwd_t<f16_t, 2>(a, st);
-  } else {
-    if (bias == 0) launch_attn_bwd_t<bf16_t, 0>(a, st);
-    else if (bias == 1) launch_attn_bwd_t<bf16_t, 1>(a, st);
-    else if (bias == 3) launch_attn_bwd_t<bf16_t, 3>(a, st);
-    else launch_attn_bwd_t<bf16_t, 2>(a, st);
   }
 }
 
@@ -933,7 +894,69 @@ __global__ __launch_bounds__(256, 2) void relpos_bwd_rows_kernel(const T* __rest
   }
 }
 
+// launch what the plan says (attn_plan.h): with launch_relpos_bwd below the only place a backward instantiation is named.  dq first: it
+// writes D.  Dynamic-LDS limits: dq the most any request of an instance can need (160 KiB), dk / dv what the instance asks for (a constant)
+template <typename T>
+static void launch_attn_bwd(const LaAttnPlan& p, const AttnBwdEncArgs& a, hipStream_t st) {
+  for (int i = 0; i < p.n; ++i) {
+    const LaAttnLaunch& l = p.launch[i];
+    with_int<1, 2>(l.nh, [&](auto nh) {
+      if (l.kernel == LA_ATTN_K_BWD_DQ)
+        with_int<ATTN_BWD_NOBIAS, ATTN_BWD_TERMS, ATTN_BWD_ROW64, ATTN_BWD_WIN16>(
+            l.mode, [&](auto b) { launch_dyn<attn_bwd_dq_kernel<T, LA_V(b), LA_V(nh)>>(l.grid, l.block, l.lds_bytes, 160 * 1024, st, a); });
+      else
+        with_int<ATTN_DKV_NOBIAS, ATTN_DKV_TERMS, ATTN_DKV_STAGED>(
+            l.mode, [&](auto b) { launch_dyn<attn_bwd_dkv_kernel<T, LA_V(b), LA_V(nh)>>(l.grid, l.block, l.lds_bytes, l.lds_bytes, st, a); });
+    });
+  }
+}
+
+// la_relpos_bwd: the plan's one launch once per 64-column block of the head (c0 = its first column)
+template <typename T>
+static void launch_relpos_bwd(const LaAttnPlan& p, const LaAttnCall& c, float gscale, hipStream_t st) {
+  const LaAttnLaunch& l = p.launch[0];
+  const T* qkv = (const T*)c.qkv;
+  T* dqkv = (T*)c.dqkv;
+  const float *drelh = (const float*)c.drelh, *drelw = (const float*)c.drelw, *tabh = (const float*)c.tabh, *tabw = (const float*)c.tabw;
+  float *dtabh = (float*)c.dtabh, *dtabw = (float*)c.dtabw;
+  for (int c0 = 0; c0 < 64 * p.repeat; c0 += 64) {
+    if (l.kernel == LA_ATTN_K_RELPOS_BWD_ROWS)
+      launch_dyn<relpos_bwd_rows_kernel<T>>(l.grid, l.block, l.lds_bytes, 0, st, qkv, dqkv, drelh, drelw, tabh, tabw, dtabh, dtabw, c.B, c.heads, c.G, c.E,
+                                            gscale, c0);
+    else
+      launch_dyn<relpos_bwd_kernel<T>>(l.grid, l.block, l.lds_bytes, 80 * 1024, st, qkv, dqkv, drelh, drelw, tabh, tabw, dtabh, dtabw, c.B, c.heads, c.G,
+                                       c.E, gscale, p.ry, c0);
+  }
+}
+
+static int attn_bwd_plan_checked(int entry, const LaAttnCall& c, LaAttnPlan* p) {
+  char err[384];
+  if (attn_bwd_plan(entry, c, p, err, sizeof(err)) != 0) {
+    la_set_error("%s", err);
+    return -1;
+  }
+  return 0;
+}
+
+// la_attn_bwd, la_attn_bwd_relpos: plan -> kernel arguments -> launch
+static int attn_bwd_run(int entry, const LaAttnCall& c, const void* kt, const void* qt, const void* dot, float scale, void* stream) {
+  LaAttnPlan p;
+  if (attn_bwd_plan_checked(entry, c, &p) != 0) return -1;
+  const AttnBwdEncArgs a{c.qkv, c.dout16, c.out16, kt, qt, dot, (float*)c.lse, (float*)c.dvec, (void*)c.dqkv, c.B, c.heads, c.T, c.Tpad, c.E, scale,
+                         (const float*)c.relh, (const float*)c.relw, (float*)c.drelh, (float*)c.drelw, c.G};
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (c.dt == LA_F16) launch_attn_bwd<f16_t>(p, a, st);
+  else launch_attn_bwd<bf16_t>(p, a, st);
+  LA_CHECK_LAUNCH(attn_entry_name(entry));
+  return 0;
+}
+
 }  // namespace la
+
+extern "C" int la_attn_bwd_plan(int entry, const LaAttnCall* call, LaAttnPlan* out) {
+  LA_CHECK_ARG(call && out, "la_attn_bwd_plan: null pointer");
+  return la::attn_bwd_plan_checked(entry, *call, out);
+}
 
 extern "C" int la_head_transpose(const void* src, int ld, int col0, int B, int heads, int T, int Tpad, void* dst, int dt, void* stream) {
   LA_CHECK_ARG(src && dst && B > 0 && heads > 0 && T > 0, "la_head_transpose: bad arguments");
@@ -950,77 +973,37 @@ extern "C" int la_head_transpose(const void* src, int ld, int col0, int B, int h
   return 0;
 }
 
+static LaAttnCall attn_bwd_call(const void* qkv, void* dqkv, int B, int heads, int T, int Tpad, int G, int E, int dt) {
+  LaAttnCall c{};
+  c.qkv = qkv, c.dqkv = dqkv;
+  c.B = B, c.heads = heads, c.T = T, c.Tpad = Tpad, c.G = G, c.E = E, c.dt = dt;
+  return c;
+}
+
 extern "C" int la_attn_bwd(const void* qkv, const void* out16, const void* dout16, const void* kt, const void* qt, const void* dot, float* lse,
                            float* dvec, void* dqkv, int B, int heads, int T, int Tpad, int E, float scale, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && out16 && dout16 && lse && dvec && dqkv, "la_attn_bwd: null pointer");      // (kt / qt / dot: unused since round 5)
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_bwd: needs head_dim 64 or 128 - other widths zero-padded (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_bwd: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_bwd: bad dtype %d", dt);
-  la::AttnBwdEncArgs a{qkv, dout16, out16, kt, qt, dot, lse, dvec, dqkv, B, heads, T, Tpad, E, scale, nullptr, nullptr, nullptr, nullptr, 0};
-  la::launch_attn_bwd(a, 0, dt, reinterpret_cast<hipStream_t>(stream));
-  LA_CHECK_LAUNCH("la_attn_bwd");
-  return 0;
+  LaAttnCall c = attn_bwd_call(qkv, dqkv, B, heads, T, Tpad, 0, E, dt);      // (kt / qt / dot: unused since round 5)
+  c.out16 = out16, c.dout16 = dout16, c.lse = lse, c.dvec = dvec;
+  return la::attn_bwd_run(LA_ATTN_EP_BWD, c, kt, qt, dot, scale, stream);
 }
 
 extern "C" int la_attn_bwd_relpos(const void* qkv, const void* out16, const void* dout16, const void* kt, const void* qt, const void* dot,
                                   float* lse, float* dvec, void* dqkv, const float* relh, const float* relw, float* drelh, float* drelw, int B,
                                   int heads, int T, int Tpad, int G, int E, float scale, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && out16 && dout16 && lse && dvec && dqkv && relh && relw && drelh && drelw, "la_attn_bwd_relpos: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_bwd_relpos: needs head_dim 64 or 128 - other widths zero-padded (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_bwd_relpos: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(G * G == T && (G <= 32 || G == 64), "la_attn_bwd_relpos: T == G*G with G <= 32 or G == 64 (T=%d G=%d)", T, G);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_bwd_relpos: bad dtype %d", dt);
-  la::AttnBwdEncArgs a{qkv, dout16, out16, kt, qt, dot, lse, dvec, dqkv, B, heads, T, Tpad, E, scale, relh, relw, drelh, drelw, G};
-  la::launch_attn_bwd(a, G == 64 ? 2 : G <= 16 ? 3 : 1, dt, reinterpret_cast<hipStream_t>(stream));
-  LA_CHECK_LAUNCH("la_attn_bwd_relpos");
-  return 0;
+  LaAttnCall c = attn_bwd_call(qkv, dqkv, B, heads, T, Tpad, G, E, dt);
+  c.out16 = out16, c.dout16 = dout16, c.lse = lse, c.dvec = dvec, c.relh = relh, c.relw = relw, c.drelh = drelh, c.drelw = drelw;
+  return la::attn_bwd_run(LA_ATTN_EP_BWD_RELPOS, c, kt, qt, dot, scale, stream);
 }
 
 extern "C" int la_relpos_bwd(const void* qkv, void* dqkv, const float* drelh, const float* drelw, const float* tabh, const float* tabw,
                              float* dtabh, float* dtabw, int B, int heads, int G, int E, float gscale, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && dqkv && drelh && drelw && tabh && tabw && dtabh && dtabw, "la_relpos_bwd: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && G > 0 && G <= 64 && (E == heads * 64 || E == heads * 128),
-               "la_relpos_bwd: needs head_dim 64 or 128 (tables [(2 G - 1), head_dim] fp32), G <= 64 (E=%d heads=%d G=%d)", E, heads, G);
-  const int hdw = E / heads;
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_relpos_bwd: bad dtype %d", dt);
+  LaAttnCall c = attn_bwd_call(qkv, dqkv, B, heads, 0, 0, G, E, dt);       // (T = G * G: the plan needs only G)
+  c.drelh = drelh, c.drelw = drelw, c.tabh = tabh, c.tabw = tabw, c.dtabh = dtabh, c.dtabw = dtabw;
+  LaAttnPlan p;
+  if (la::attn_bwd_plan_checked(LA_ATTN_EP_RELPOS_BWD, c, &p) != 0) return -1;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (G <= 16) {                                     // the windows: dense products over units of 32 queries
-    const int lds_rows = 64 * 64 * (int)sizeof(float) + 4 * (2 * 32 * G * (int)sizeof(float) + 32 * 64 * 2);
-    const int nunits = B * heads * ((G * G + 31) / 32);
-    const int grid_rows = nunits / 4 < 512 ? (nunits + 3) / 4 : 512;          // (256 / 512 / 768 workgroups on 100 x 12 windows: 135 / 117 / 132 us)
-    for (int c0 = 0; c0 < hdw; c0 += 64) {
-      if (dt == LA_F16)
-        hipLaunchKernelGGL(la::relpos_bwd_rows_kernel<la::f16_t>, dim3(grid_rows), dim3(256), lds_rows, st, (const la::f16_t*)qkv, (la::f16_t*)dqkv,
-                           drelh, drelw, tabh, tabw, dtabh, dtabw, B, heads, G, E, gscale, c0);
-      else
-        hipLaunchKernelGGL(la::relpos_bwd_rows_kernel<la::bf16_t>, dim3(grid_rows), dim3(256), lds_rows, st, (const la::bf16_t*)qkv,
-                           (la::bf16_t*)dqkv, drelh, drelw, tabh, tabw, dtabh, dtabw, B, heads, G, E, gscale, c0);
-    }
-    LA_CHECK_LAUNCH("la_relpos_bwd");
-    return 0;
-  }
-  const int lds = (2 * G * (G + 1) + (2 * G - 1) * 64) * (int)sizeof(float) + G * 64 * 2;        // 73 KiB at G = 64: two workgroups per CU
-  // rows per workgroup.  Large grids (G == 64: 4 image-heads x 64 rows per CU): as many as keep >= ~3 workgroups per CU in the launch - the
-  // table atomics shrink by that factor.  Windows (G <= 32, tables of a few KiB, workgroups of 10 KiB): one row each - a row's three
-  // dependent global round trips (operands in, dq read-modify-write) are what it waits for, and only more resident workgroups hide them
-  // (measured on 100 x 12 windows of 14 x 14: 471 us with 14 rows per workgroup)
-  int ry = 1;
-  while (G > 32 && ry < G && (long)B * heads * ((G + 2 * ry - 1) / (2 * ry)) >= 768) ry *= 2;
-  const int grid = B * heads * ((G + ry - 1) / ry);
-  static unsigned long long m1 = 0, m2 = 0;
-  for (int c0 = 0; c0 < hdw; c0 += 64) {
-    if (dt == LA_F16) {
-      la::ensure_dyn_lds(reinterpret_cast<const void*>(la::relpos_bwd_kernel<la::f16_t>), 80 * 1024, m1);
-      hipLaunchKernelGGL(la::relpos_bwd_kernel<la::f16_t>, dim3(grid), dim3(256), lds, st, (const la::f16_t*)qkv, (la::f16_t*)dqkv, drelh,
-                         drelw, tabh, tabw, dtabh, dtabw, B, heads, G, E, gscale, ry, c0);
-    } else {
-      la::ensure_dyn_lds(reinterpret_cast<const void*>(la::relpos_bwd_kernel<la::bf16_t>), 80 * 1024, m2);
-      hipLaunchKernelGGL(la::relpos_bwd_kernel<la::bf16_t>, dim3(grid), dim3(256), lds, st, (const la::bf16_t*)qkv, (la::bf16_t*)dqkv, drelh,
-                         drelw, tabh, tabw, dtabh, dtabw, B, heads, G, E, gscale, ry, c0);
-    }
-  }
+  if (dt == LA_F16) la::launch_relpos_bwd<la::f16_t>(p, c, gscale, st);
+  else la::launch_relpos_bwd<la::bf16_t>(p, c, gscale, st);
   LA_CHECK_LAUNCH("la_relpos_bwd");
   return 0;
 }

@@ -33,11 +33,11 @@
 #define LA_ATTN_X 0         // timing experiments (results wrong beyond tile 0): 2 no maximum pass after the first tile, 4 exp2 of the bare score, 8 no row sums
 #endif
 #include "../../include/la_hip.h"
+#include "attn_plan.h"
 
 namespace la {
 
 constexpr int HD = 64;
-constexpr int KV_STAGE = 2 * 64 * HD * 2;  // K tile + V^T tile, 16 KiB
 constexpr float NEG_BIG = -1.0e30f;
 constexpr float RESCALE_THR = 8.0f;   // log2 units
 
@@ -130,12 +130,12 @@ __device__ __forceinline__ float xhalf_sum(float v) {
 }
 
 #ifdef LA_DEBUG
-// phase timeline of the window instance of attn_fwd_kernel (MODE 5): s_memtime of the workgroup in the MIDDLE of the launch (steady state),
+// phase timeline of the window instance of attn_fwd_kernel (ATTN_TABLES_WIN16): s_memtime of the workgroup in the MIDDLE of the launch (steady state),
 // [wave][i]; tools/win_phases.py
 __device__ unsigned long long g_win_stamps[4 * 16];
 #define WIN_STAMP(i)                                                                                  \
   do {                                                                                                \
-    if (MODE == 5 && blockIdx.x == gridDim.x / 2) {                                                   \
+    if (MODE == ATTN_TABLES_WIN16 && blockIdx.x == gridDim.x / 2) {                                   \
       unsigned long long t_;                                                                          \
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                     \
       if ((threadIdx.x & 63) == 0) g_win_stamps[(threadIdx.x >> 6) * 16 + (i)] = t_;                   \
@@ -152,7 +152,7 @@ struct AttnArgs {
   void* out;
   const float* relh;
   const float* relw;
-  const void* tabh;   // MODE 3: 16-bit rel-pos tables [(2G-1), 64]
+  const void* tabh;   // ATTN_TABLES_*: 16-bit rel-pos tables [(2G-1), head_dim]
   const void* tabw;
   int B, heads, T, Tpad, G, E;
   float scale;
@@ -184,10 +184,8 @@ static inline void set_win_magic(AttnArgs& a) {
   a.mg_G = magic_of(a.G);
 }
 
-// MODE 0: no bias.  MODE 1: rel-pos, generic G (LDS tables filled from la_relpos_terms output).
-// MODE 2: rel-pos, G == 64 (tile == key row), terms from la_relpos_terms.  MODE 4: same with the terms computed in-kernel.
-// MODE 3: rel-pos, G <= 16 (SAM windows): the decomposed terms are computed
-// IN the kernel (U[r][q] = R[r] . q on MFMA, 8 extra MFMAs per 32-query tile) - no la_relpos_terms pass, no global bias.
+// MODE: where the rel-pos bias comes from - the ATTN_* constants of attn_plan.h (ATTN_TABLES_*: the decomposed terms are computed IN the
+// kernel, U[r][q] = R[r] . q on MFMA, 8 extra MFMAs per 32-query tile - no la_relpos_terms pass, no global bias).
 // NH = head_dim / 64 (1 or 2).  A 128-wide head is two 64-wide halves everywhere: the K tile is two [64 keys][64 dims]
 // sub-tiles, the V^T tile two [64 dims][64 keys] sub-tiles (same 128-byte rows, same swizzle, same DMA pieces), Q has
 // 4 NH MFMA k-slices and O^T 2 NH accumulator tiles.  (Heads that are not a multiple of 64 wide - SAM ViT-H has 80 - are
@@ -197,7 +195,9 @@ static inline void set_win_magic(AttnArgs& a) {
 // reads: in a 16-lane group lane 4 j + c fetches the 8 bytes (row k0 + j, dims D + 4 c ..), lane p receives dimension D + p of the four
 // rows (probed on the part: tools/micro/tr_probe.hip).  A 32-lane pass covers 4 rows x 64 bytes = every bank once.
 template <typename T, int MODE, int NH, bool VROW = false>
-__global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_TABLES_WIN16) && NH == 1) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
+  constexpr bool WIN16 = MODE == ATTN_TABLES_WIN16;                                   // windows, keys in 16-wide slot order
+  constexpr bool ROW64 = MODE == ATTN_TERMS_ROW64 || MODE == ATTN_TABLES_ROW64;       // G == 64: a key tile is one key row
   constexpr int HDT = 64 * NH, KS = 4 * NH, SUB = 64 * 64 * 2, KVS = KV_STAGE * NH;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   WIN_STAMP(0);
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
   int bh, qblk;
   {
     const int nq = (a.T + 127) / 128;
-    if (MODE == 5) {             // (windows: T <= 256 = one or two query blocks - shifts and multiply-highs, no run-time division)
+    if (WIN16) {             // (windows: T <= 256 = one or two query blocks - shifts and multiply-highs, no run-time division)
       const bool two = nq == 2;
       if ((BH & 7) == 0) {
         const int idx = blockIdx.x >> 3;
@@ -229,20 +229,20 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
       qblk = blockIdx.x / BH;
     }
   }
-  const int b = MODE == 5 ? udiv_magic(bh, a.heads, a.mg_heads) : bh / a.heads;
+  const int b = WIN16 ? udiv_magic(bh, a.heads, a.mg_heads) : bh / a.heads;
   const int h = bh - b * a.heads;
   const int T_ = a.T, E3 = 3 * a.E;
   const T* qkv = reinterpret_cast<const T*>(a.qkv);
   const T* vt = reinterpret_cast<const T*>(a.vt);
   // (windows: wave w works on query tile (w + bh) % 4 of the block - T = 196 leaves the second block's fourth tile empty, and a fixed
   // assignment puts that hole on the same SIMD every time)
-  const int q0 = qblk * 128 + ((MODE == 5 && LA_WIN_ROT) ? ((wave + bh) & 3) : wave) * 32;
+  const int q0 = qblk * 128 + ((WIN16 && LA_WIN_ROT) ? ((wave + bh) & 3) : wave) * 32;
   const int q = q0 + fr;
   const int qc = min(q, T_ - 1);
   const float inv_scale = 1.0f / a.scale;
   const float c2 = a.scale * 1.44269504088896340736f;  // logits -> log2 domain
-  // image-order windows (MODE 5, imgH > 0): window b = (image, wy, wx); token (ty, tx) of the window is image token (wy G + ty, wx G + tx)
-  const bool img_order = MODE == 5 && VROW && a.imgH > 0;
+  // image-order windows (WIN16, imgH > 0): window b = (image, wy, wx); token (ty, tx) of the window is image token (wy G + ty, wx G + tx)
+  const bool img_order = WIN16 && VROW && a.imgH > 0;
   int wimg = 0, wy0 = 0, wx0 = 0;
   if (img_order) {
     wimg = udiv_magic(b, a.nwin, a.mg_nwin);
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     wx0 = (w_ - wy * a.nwx) * a.G;
   }
   // windows: the lane's query as window coordinates
-  const int qy5 = MODE == 5 ? udiv_magic(qc, a.G, a.mg_G) : 0, qx5 = qc - qy5 * a.G;
+  const int qy5 = WIN16 ? udiv_magic(qc, a.G, a.mg_G) : 0, qx5 = qc - qy5 * a.G;
   // row of window token (ty, tx) in the image-order buffers, or -1 beyond the image
   auto img_row = [&](int ty, int tx) -> long {
     const int y = wy0 + ty, x = wx0 + tx;
@@ -315,11 +315,11 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
       int key = 0;
       const T* kp = nullptr;
       const T* vp = nullptr;
-      if (MODE != 5 && !LA_ATTN_DMA_RUN) {      // (A/B build: clamp + 64-bit multiply-add per piece, the form before round 6)
+      if (!WIN16 && !LA_ATTN_DMA_RUN) {      // (A/B build: clamp + 64-bit multiply-add per piece, the form before round 6)
         key = min(j * 64 + krow[i], T_ - 1);
         kp = ksrc[i] + (size_t)key * E3;
         if (VROW) vp = vsrc[i] + (size_t)key * E3;
-      } else if (MODE != 5) {
+      } else if (!WIN16) {
         unsigned ko = krun[i], vo = vrun[i];
         if (j * 64 + 64 > T_) {          // (wave-uniform: the last, ragged tile) rows beyond T - 1 re-read row T - 1, masked later
           const unsigned back = (unsigned)max(j * 64 + krow[i] - (T_ - 1), 0) * (unsigned)(E3 * sizeof(T));
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
           else dma16(vsrc[i] + (size_t)hh * 64 * a.Tpad + j * 64, sv + hh * SUB + (i * 4 + wave) * 1024);
         }
         continue;
-      } else if (MODE == 5) {   // slot -> token of the ws x ws window (padded slots read a clamped, later masked, row)
+      } else if (WIN16) {   // slot -> token of the ws x ws window (padded slots read a clamped, later masked, row)
         const int slot = j * 64 + krow[i];
         const int ty = min(slot >> 4, a.G - 1), tx = min(slot & 15, a.G - 1);
         key = ty * a.G + tx;
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
           vp = rp + voff[i];
         }
       }
-      if (MODE == 5 && !img_order) {
+      if (WIN16 && !img_order) {
         kp = ksrc[i] + (size_t)key * E3;
         if (VROW) vp = vsrc[i] + (size_t)key * E3;
       }
@@ -362,10 +362,10 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
   // the first K / V^T tile goes on its way BEFORE the bias tables are built: a window's key loop is four tiles long, and two thirds of
   // that kernel's time were the per-workgroup prologue chain (loads -> table MFMAs -> LDS -> first tile) - the stages and the bias
   // tables do not overlap in LDS
-  const int ntiles = (MODE == 5) ? ((16 * a.G + 63) >> 6) : ((T_ + 63) >> 6);
+  const int ntiles = WIN16 ?((16 * a.G + 63) >> 6) : ((T_ + 63) >> 6);
   // windows: the last tile's upper 32 key slots are all padding (G = 14: key rows 14 / 15) - their scores carry NEG_BIG, exp2 gives exactly 0,
   // so the tile runs its lower half only and no bit changes
-  const bool half_last = MODE == 5 && LA_WIN_HALF && ((16 * a.G) & 63) != 0 && ((16 * a.G) & 63) <= 32;
+  const bool half_last = WIN16 && LA_WIN_HALF && ((16 * a.G) & 63) != 0 && ((16 * a.G) & 63) <= 32;
   dma(0, 0);
   WIN_STAMP(1);
 
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
   float* my_bh = nullptr;
   float* my_bw = nullptr;
   const int* keyinfo = nullptr;
-  if (MODE == 2) {
+  if (MODE == ATTN_TERMS_ROW64) {
     my_bh = bias_lds + wave * 32 * 65;
     for (int i = 0; i < 32; ++i) {
       const int qi = min(q0 + i, T_ - 1);
@@ -393,8 +393,8 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
         rw[t][g4 * 4 + 2] = v.z * inv_scale;
         rw[t][g4 * 4 + 3] = v.w * inv_scale;   // (vector element writes with constant indices stay in registers)
       }
-  } else if (MODE == 5) {
-    // windows in 16-wide slot order: U tables as in MODE 3, then the bias of score register (t, r) in tile j is
+  } else if (WIN16) {
+    // windows in 16-wide slot order: U tables as in ATTN_TABLES_WIN, then the bias of score register (t, r) in tile j is
     //   bh4[2t + (r >> 3)]  (key row 4j + 2t + (r>>3))  +  bw8[((r >> 2) & 1) * 4 + (r & 3)]  (key column 8((r>>2)&1) + 4fh + (r&3)),
     // with padded rows / columns carrying NEG_BIG (no separate masking pass).
     // One 32 x 33 table per wave, used twice: first for U_w (only needed to pick the lane's 8 column terms bw8), then
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
 #pragma unroll
     for (int r = 0; r < 16; ++r) my_bh[fr * 33 + (r & 3) + 8 * (r >> 2) + 4 * fh] = uh[r] * inv_scale;
     __builtin_amdgcn_wave_barrier();
-  } else if (MODE == 4) {
+  } else if (MODE == ATTN_TABLES_ROW64) {
     // G == 64, terms computed in-kernel.  The wave's 32 queries share the image row y and cover columns x0 .. x0+31.
     //   relw[q][kw] = q . Rw[x - kw + 63] = Uw[(x - x0) + 63 - kw][q],  Uw[i][q] = Rw[x0 + i] . q,  i < 96   (12 MFMAs)
     //   relh[q][j]  = q . Rh[y - j + 63]  = Uh[63 - j][q],              Uh[i][q] = Rh[y + i] . q,   i < 64   ( 8 MFMAs)
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
         }
     }
     __builtin_amdgcn_wave_barrier();
-  } else if (MODE == 1) {
+  } else if (MODE == ATTN_TERMS) {
     const int G = a.G, GS = G + 1;
     my_bh = bias_lds + wave * 2 * 32 * GS;
     my_bw = my_bh + 32 * GS;
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     int* ki = reinterpret_cast<int*>(bias_lds + 4 * 2 * 32 * GS);
     for (int k = tid; k < a.Tpad; k += 256) ki[k] = ((k / G) << 16) | (k % G);
     keyinfo = ki;
-  } else if (MODE == 3) {
+  } else if (MODE == ATTN_TABLES_WIN) {
     // U_h[q][r] = q . Rh[r], U_w[q][r] = q . Rw[r] for r < 2G-1 <= 32; bias(q, k) = U_h[q][qy - kh + G-1] + U_w[q][qx - kw + G-1]
     const int G = a.G, nrel = 2 * G - 1;
     my_bh = bias_lds + wave * 2 * 32 * 33;
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
 
   WIN_STAMP(2);
   dma_wait<0>();
-  // MODE 4: relh[q][j] = Uh[63 - j][q], Uh[i][q] = Rh[y + i] . q; half hf covers tiles j in [32 hf, 32 hf + 32) = rows
+  // ATTN_TABLES_ROW64: relh[q][j] = Uh[63 - j][q], Uh[i][q] = Rh[y + i] . q; half hf covers tiles j in [32 hf, 32 hf + 32) = rows
   // i in [32 (1 - hf), +32): my_bh[q][j & 31]
   auto fill_relh_half = [&](int hf) {
     const int y = q0 >> 6;
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     for (int r = 0; r < 16; ++r) my_bh[fr * 33 + 31 - ((r & 3) + 8 * (r >> 2) + 4 * fh)] = u[r] * inv_scale;
     __builtin_amdgcn_wave_barrier();
   };
-  if (MODE == 4) fill_relh_half(0);
+  if (MODE == ATTN_TABLES_ROW64) fill_relh_half(0);
   __syncthreads();
   WIN_STAMP(3);
   // a wave whose 32 query rows all lie beyond T (T = 901: three of the 32 waves of an image-head) only helps staging the tiles
@@ -549,22 +549,22 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     }
     const char* sk = smem + (j & 1) * KVS;
     const char* sv = sk + NH * SUB;
-    if (MODE == 4 && j == 32) fill_relh_half(1);
+    if (MODE == ATTN_TABLES_ROW64 && j == 32) fill_relh_half(1);
 
     // ---- S^T tile: 64 keys x 32 queries.  G == 64: the C operand of the first MFMA IS the relw register block
     // (no per-tile initialisation pass); the per-row scalar relh[q][tile] is folded into the softmax constants below.
     f32x16 s[2];
     float rh = 0.f;
-    const bool half = MODE == 5 && half_last && j == ntiles - 1;      // (wave-uniform)
-    if (MODE == 2) rh = my_bh[fr * 65 + j];
-    if (MODE == 4) rh = my_bh[fr * 33 + (j & 31)];
+    const bool half = WIN16 && half_last && j == ntiles - 1;      // (wave-uniform)
+    if (MODE == ATTN_TERMS_ROW64) rh = my_bh[fr * 65 + j];
+    if (MODE == ATTN_TABLES_ROW64) rh = my_bh[fr * 33 + (j & 31)];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      if (MODE == 5 && t == 1 && half) continue;
+      if (WIN16 && t == 1 && half) continue;
       const uint4 kf0 = *reinterpret_cast<const uint4*>(sk + swz_off(t * 32 + fr, fh));
-      if (MODE == 2 || MODE == 4) {
+      if (ROW64) {
         s[t] = Half16<T>::mfma32(kf0, qf[0], rw[t]);
-      } else if (MODE == 5) {
+      } else if (WIN16) {
         f32x16 z;
         const int qy = qy5;
 #pragma unroll
@@ -587,13 +587,13 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     for (int ks = 1; ks < KS; ++ks) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        if (MODE == 5 && t == 1 && half) continue;
+        if (WIN16 && t == 1 && half) continue;
         const uint4 kf = *reinterpret_cast<const uint4*>(sk + (ks >> 2) * SUB + swz_off(t * 32 + fr, (ks & 3) * 2 + fh));
         s[t] = Half16<T>::mfma32(kf, qf[ks], s[t]);
       }
     }
 #endif
-    if (MODE == 1) {
+    if (MODE == ATTN_TERMS) {
       const int GS = a.G + 1;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
           s[t][r] += my_bh[fr * GS + (info >> 16)] + my_bw[fr * GS + (info & 0xffff)];
         }
     }
-    if (MODE == 3) {
+    if (MODE == ATTN_TABLES_WIN) {
       const int qy = qc / a.G, qx = qc % a.G;
       const float* bh_q = my_bh + fr * 33 + qy;
       const float* bw_q = my_bw + fr * 33 + qx;
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
           s[t][r] += bh_q[info >> 16] + bw_q[info & 0xffff];
         }
     }
-    if (MODE != 5 && j * 64 + 64 > T_) {  // tail tile: mask keys >= T (wave-uniform branch)
+    if (!WIN16 && j * 64 + 64 > T_) {  // tail tile: mask keys >= T (wave-uniform branch)
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -637,7 +637,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     float mx = s[0][0];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      if (MODE == 5 && t == 1 && half) continue;
+      if (WIN16 && t == 1 && half) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[t][r]);
     }
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     float psum = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      if (MODE == 5 && t == 1 && half) continue;
+      if (WIN16 && t == 1 && half) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         // (scalar FMAs on purpose: v_pk_fma_f32 does not overlap with another wave's MFMA stream at all, v_fma_f32 partly, v_exp_f32
@@ -685,7 +685,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     uint4 pf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (MODE == 5 && ks >= 2 && half) continue;
+      if (WIN16 && ks >= 2 && half) continue;
       const int t = ks >> 1, g0 = (ks & 1) * 8;  // register group base (4 regs per group)
       const uint32_t x0 = pack2<T>(s[t][g0 + 0], s[t][g0 + 1]);
       const uint32_t x1 = pack2<T>(s[t][g0 + 2], s[t][g0 + 3]);
@@ -703,7 +703,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
 #else
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (MODE == 5 && ks >= 2 && half) continue;
+      if (WIN16 && ks >= 2 && half) continue;
 #pragma unroll
       for (int d = 0; d < 2 * NH; ++d) {
         uint4 vf;
@@ -755,7 +755,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
     // 4 NH MFMAs per wave instead of 32 NH four-step DPP sums (128 vector instructions of a window workgroup's ~1200: with the DPP form the
     // window blocks' sums cost as much as the la_colmean16 pass they replace).  The four waves' sums meet in LDS, fixed order.
     bool valid = q < T_ && qrow >= 0;
-    if (MODE == 5 && a.csH > 0 && !img_order) {
+    if (WIN16 && a.csH > 0 && !img_order) {
       const int nwx = (a.csW + a.G - 1) / a.G, nwy = (a.csH + a.G - 1) / a.G;
       const int w = b % (nwx * nwy);
       valid = valid && (w / nwx) * a.G + qy5 < a.csH && (w % nwx) * a.G + qx5 < a.csW;
@@ -820,7 +820,7 @@ __global__ __launch_bounds__(256, (((MODE == 4 || MODE == 5) && NH == 1) ? 3 : 2
 // ONE WAVE per (window, head, 32-query tile), no LDS staging of K / V and no workgroup barriers in the key loop - the
 // MFMA A operands (K rows, V^T rows) are fetched straight from global memory (the 7 query tiles of a window-head hit
 // the same lines in L1/L2).  16 independent waves per CU hide the load latency.  Rel-pos terms are computed in the
-// prologue (U[r][q] = R[r] . q, 8 MFMAs) and bounced through a small per-wave LDS table, as in MODE 3 above.
+// prologue (U[r][q] = R[r] . q, 8 MFMAs) and bounced through a small per-wave LDS table, as in ATTN_TABLES_WIN above.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256, 3) void attn_window_kernel(AttnArgs a, int qtiles) {
@@ -977,28 +977,21 @@ __global__ __launch_bounds__(256, 3) void attn_window_kernel(AttnArgs a, int qti
   }
 }
 
+// launch what the plan says (attn_plan.h): the only place a forward instantiation is named.  The tile kernel's dynamic-LDS limit is raised
+// to the most any request of an instance can need (160 KiB); the V-row form exists for the three modes la_attn_fwd_rows has
 template <typename T>
-static void launch_window(const AttnArgs& a, hipStream_t st) {
-  const int qtiles = (a.T + 31) / 32;
-  const int njobs = a.B * a.heads * qtiles;
-  const size_t lds = (size_t)a.Tpad * sizeof(int) + 4 * 2 * 32 * 33 * sizeof(float);
-  hipLaunchKernelGGL((attn_window_kernel<T>), dim3((njobs + 3) / 4), dim3(256), lds, st, a, qtiles);
-}
-
-template <typename T, int MODE, int NH, bool VROW = false>
-static void launch_attn_nh(const AttnArgs& a, size_t lds, hipStream_t st) {
-  // raise the dynamic-LDS limit to the most any request of this variant can need (160 KiB), once per device
-  static unsigned long long attr_mask = 0;
-  ensure_dyn_lds(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, NH, VROW>), 160 * 1024, attr_mask);
-  const int nq = (a.T + 127) / 128;
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, NH, VROW>), dim3(nq * a.B * a.heads), dim3(256), lds, st, a);
-}
-
-// extra = LDS beyond the two K / V^T stages (bias tables); head_dim = E / heads is 64 or 128
-template <typename T, int MODE, bool VROW = false>
-static void launch_attn(const AttnArgs& a, size_t extra, hipStream_t st) {
-  if (a.E == a.heads * 128) launch_attn_nh<T, MODE, 2, VROW>(a, 2 * (size_t)KV_STAGE * 2 + extra, st);
-  else launch_attn_nh<T, MODE, 1, VROW>(a, 2 * (size_t)KV_STAGE + extra, st);
+static void launch_attn_fwd(const LaAttnPlan& p, const AttnArgs& a, hipStream_t st) {
+  const LaAttnLaunch& l = p.launch[0];
+  if (l.kernel == LA_ATTN_K_WINDOW) return launch_dyn<attn_window_kernel<T>>(l.grid, l.block, l.lds_bytes, 0, st, a, (a.T + 31) / 32);
+  constexpr int LIMIT = 160 * 1024;
+  with_int<1, 2>(l.nh, [&](auto nh) {
+    if (l.vrow)
+      with_int<ATTN_NOBIAS, ATTN_TABLES_ROW64, ATTN_TABLES_WIN16>(
+          l.mode, [&](auto m) { launch_dyn<attn_fwd_kernel<T, LA_V(m), LA_V(nh), true>>(l.grid, l.block, l.lds_bytes, LIMIT, st, a); });
+    else
+      with_int<ATTN_NOBIAS, ATTN_TERMS, ATTN_TERMS_ROW64, ATTN_TABLES_WIN, ATTN_TABLES_ROW64, ATTN_TABLES_WIN16>(
+          l.mode, [&](auto m) { launch_dyn<attn_fwd_kernel<T, LA_V(m), LA_V(nh), false>>(l.grid, l.block, l.lds_bytes, LIMIT, st, a); });
+  });
 }
 
 
@@ -1166,7 +1159,51 @@ __global__ __launch_bounds__(256) void qk_fp8_kernel(const T* __restrict__ qkv, 
   }
 }
 
+// the plan of a forward call, with the entry point's errors
+static int attn_fwd_plan_checked(int entry, const LaAttnCall& c, LaAttnPlan* p) {
+  char err[384];
+  if (attn_fwd_plan(entry, c, p, err, sizeof(err)) != 0) {
+    la_set_error("%s", err);
+    return -1;
+  }
+#ifdef LA_DEBUG
+  // The measurement library only: the environment edits the FINISHED plan - the pure plan never sees it.  LA_WINDOW_PATH=lds: the LDS-staged
+  // ATTN_TABLES_WIN instance of attn_fwd_kernel wherever the plan takes the no-LDS window kernel
+  static const char* wforce = getenv("LA_WINDOW_PATH");
+  if (wforce && wforce[0] == 'l' && p->launch[0].kernel == LA_ATTN_K_WINDOW) p->launch[0] = attn_fwd_tile_launch(ATTN_TABLES_WIN, false, c);
+#endif
+  return 0;
+}
+
+static LaAttnCall attn_call(int B, int heads, int T, int Tpad, int G, int E, int mode, int dt) {
+  LaAttnCall c{};
+  c.B = B, c.heads = heads, c.T = T, c.Tpad = Tpad, c.G = G, c.E = E, c.mode = mode, c.dt = dt;
+  return c;
+}
+
+// every forward entry point: plan -> kernel arguments -> launch
+static int attn_fwd_run(int entry, const LaAttnCall& c, float scale, void* stream) {
+  LaAttnPlan p;
+  if (attn_fwd_plan_checked(entry, c, &p) != 0) return -1;
+  AttnArgs a{c.qkv, c.vt, const_cast<void*>(c.out16), (const float*)c.relh, (const float*)c.relw, c.tabh, c.tabw, c.B, c.heads, c.T, c.Tpad, c.G,
+             c.E, scale, (float*)c.lse, (float*)c.cspart, c.csH, c.csW};
+  if (p.launch[0].mode == ATTN_TABLES_WIN16) {
+    if (c.imgH > 0) a.imgH = c.imgH, a.imgW = c.imgW, a.padrow = c.padrow;
+    set_win_magic(a);
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (c.dt == LA_F16) launch_attn_fwd<f16_t>(p, a, st);
+  else launch_attn_fwd<bf16_t>(p, a, st);
+  LA_CHECK_LAUNCH(attn_entry_name(entry));
+  return 0;
+}
+
 }  // namespace la
+
+extern "C" int la_attn_fwd_plan(int entry, const LaAttnCall* call, LaAttnPlan* out) {
+  LA_CHECK_ARG(call && out, "la_attn_fwd_plan: null pointer");
+  return la::attn_fwd_plan_checked(entry, *call, out);
+}
 
 extern "C" int la_relpos_terms(const void* qkv, int B, int heads, int G, int E, const void* tabh, const void* tabw, float* relh,
                                float* relw, int dt, void* stream) {
@@ -1189,10 +1226,6 @@ extern "C" int la_relpos_terms(const void* qkv, int B, int heads, int G, int E, 
   return 0;
 }
 
-extern "C" int la_attn_fwd_cs(const void* qkv, const void* vt, void* out16, const float* relh, const float* relw, const void* tabh,
-                              const void* tabw, int B, int heads, int T, int Tpad, int G, int E, float scale, int mode, float* cspart, int csH,
-                              int csW, int dt, void* stream);
-
 #ifdef LA_DEBUG
 extern "C" int la_dbg_win_stamps(unsigned long long* host_out) {
   (void)hipDeviceSynchronize();
@@ -1200,70 +1233,18 @@ extern "C" int la_dbg_win_stamps(unsigned long long* host_out) {
 }
 #endif
 
-extern "C" int la_attn_fwd(const void* qkv, const void* vt, void* out16, const float* relh, const float* relw, const void* tabh,
-                           const void* tabw, int B, int heads, int T, int Tpad, int G, int E, float scale, int mode, int dt, void* stream) {
-  return la_attn_fwd_cs(qkv, vt, out16, relh, relw, tabh, tabw, B, heads, T, Tpad, G, E, scale, mode, nullptr, 0, 0, dt, stream);
-}
-
 extern "C" int la_attn_fwd_cs(const void* qkv, const void* vt, void* out16, const float* relh, const float* relw, const void* tabh,
                               const void* tabw, int B, int heads, int T, int Tpad, int G, int E, float scale, int mode, float* cspart, int csH,
                               int csW, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && vt && out16, "la_attn_fwd: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_fwd: needs head_dim 64 or 128 - pad other widths with zero columns (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_fwd: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_fwd: bad dtype %d", dt);
-  la::AttnArgs a{qkv, vt, out16, relh, relw, tabh, tabw, B, heads, T, Tpad, G, E, scale, nullptr, cspart, csH, csW};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const size_t kv = 0;       // launch_attn adds the K / V^T stages for the head width; the sizes below are the bias tables
-  if (mode == LA_ATTN_PLAIN) {
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 0>(a, kv, st);
-    else la::launch_attn<la::bf16_t, 0>(a, kv, st);
-  } else if (mode == LA_ATTN_RELPOS_WIN16) {
-    LA_CHECK_ARG(tabh && tabw && G > 0 && G <= 16 && G * G == T && Tpad >= 16 * G,
-                 "la_attn_fwd: WIN16 needs the tables, T == G*G, G <= 16 and Tpad >= 16*G (T=%d G=%d Tpad=%d)", T, G, Tpad);
-    const size_t lds = kv + 4 * 32 * 33 * sizeof(float);
-    la::set_win_magic(a);
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 5>(a, lds, st);
-    else la::launch_attn<la::bf16_t, 5>(a, lds, st);
-  } else if (mode == LA_ATTN_RELPOS) {
-    LA_CHECK_ARG(G > 0 && G <= 64 && G * G == T, "la_attn_fwd: rel-pos needs T == G*G, G <= 64 (T=%d G=%d)", T, G);
-    if (tabh && tabw && G <= 16) {        // windows: bias terms computed in-kernel from the tables
-      static const char* wforce = la_dbg_env("LA_WINDOW_PATH");     // debugging: "lds" selects the LDS-staged MODE 3 kernel
-      if (!(wforce && wforce[0] == 'l') && E == heads * 64) {   // (the no-LDS window kernel is 64-wide only)
-        if (dt == LA_F16) la::launch_window<la::f16_t>(a, st);
-        else la::launch_window<la::bf16_t>(a, st);
-        LA_CHECK_LAUNCH("la_attn_fwd");
-        return 0;
-      }
-      const size_t lds = kv + 4 * 2 * 32 * 33 * sizeof(float) + (size_t)Tpad * sizeof(int);
-      if (dt == LA_F16) la::launch_attn<la::f16_t, 3>(a, lds, st);
-      else la::launch_attn<la::bf16_t, 3>(a, lds, st);
-      LA_CHECK_LAUNCH("la_attn_fwd");
-      return 0;
-    }
-    if (tabh && tabw && G == 64) {        // global blocks: terms computed in the prologue of each query tile
-      const size_t lds = kv + 4 * 32 * 33 * sizeof(float);
-      if (dt == LA_F16) la::launch_attn<la::f16_t, 4>(a, lds, st);
-      else la::launch_attn<la::bf16_t, 4>(a, lds, st);
-      LA_CHECK_LAUNCH("la_attn_fwd");
-      return 0;
-    }
-    LA_CHECK_ARG(relh && relw, "la_attn_fwd: rel-pos terms missing (run la_relpos_terms, or pass the tables for G <= 16 / G == 64)");
-    if (G == 64) {
-      const size_t lds = kv + 4 * 32 * 65 * sizeof(float);
-      if (dt == LA_F16) la::launch_attn<la::f16_t, 2>(a, lds, st);
-      else la::launch_attn<la::bf16_t, 2>(a, lds, st);
-    } else {
-      const size_t lds = kv + 4 * 2 * 32 * (G + 1) * sizeof(float) + (size_t)Tpad * sizeof(int);
-      if (dt == LA_F16) la::launch_attn<la::f16_t, 1>(a, lds, st);
-      else la::launch_attn<la::bf16_t, 1>(a, lds, st);
-    }
-  } else {
-    LA_CHECK_ARG(false, "la_attn_fwd: bad mode %d", mode);
-  }
-  LA_CHECK_LAUNCH("la_attn_fwd");
-  return 0;
+  LaAttnCall c = la::attn_call(B, heads, T, Tpad, G, E, mode, dt);
+  c.qkv = qkv, c.vt = vt, c.out16 = out16, c.relh = relh, c.relw = relw, c.tabh = tabh, c.tabw = tabw;
+  c.cspart = cspart, c.csH = csH, c.csW = csW;
+  return la::attn_fwd_run(LA_ATTN_EP_FWD, c, scale, stream);
+}
+
+extern "C" int la_attn_fwd(const void* qkv, const void* vt, void* out16, const float* relh, const float* relw, const void* tabh,
+                           const void* tabw, int B, int heads, int T, int Tpad, int G, int E, float scale, int mode, int dt, void* stream) {
+  return la_attn_fwd_cs(qkv, vt, out16, relh, relw, tabh, tabw, B, heads, T, Tpad, G, E, scale, mode, nullptr, 0, 0, dt, stream);
 }
 
 // The same attention without a V^T copy: V tiles come row-major from the v columns of qkv (ds_read_b64_tr_b16 feeds the MFMA).  Modes:
@@ -1272,78 +1253,24 @@ extern "C" int la_attn_fwd_cs(const void* qkv, const void* vt, void* out16, cons
 // windows, padrow = [3E] 16-bit q | k | v of a padded token (the qkv bias: pad-after-norm, image_encoder.py:160-172), no window buffers.
 extern "C" int la_attn_fwd_rows(const void* qkv, void* out16, const void* tabh, const void* tabw, int B, int heads, int T, int Tpad, int G, int E,
                                 float scale, int mode, float* cspart, int imgH, int imgW, const void* padrow, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && out16, "la_attn_fwd_rows: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_fwd_rows: needs head_dim 64 or 128 - pad other widths with zero columns (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_fwd_rows: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_fwd_rows: bad dtype %d", dt);
-  la::AttnArgs a{qkv, nullptr, out16, nullptr, nullptr, tabh, tabw, B, heads, T, Tpad, G, E, scale, nullptr, cspart, 0, 0, 0, 0, nullptr};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (mode == LA_ATTN_PLAIN) {
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 0, true>(a, 0, st);
-    else la::launch_attn<la::bf16_t, 0, true>(a, 0, st);
-  } else if (mode == LA_ATTN_RELPOS_WIN16) {
-    LA_CHECK_ARG(tabh && tabw && G > 0 && G <= 16 && G * G == T && Tpad >= 16 * G,
-                 "la_attn_fwd_rows: WIN16 needs the tables, T == G*G, G <= 16 and Tpad >= 16*G (T=%d G=%d Tpad=%d)", T, G, Tpad);
-    if (imgH > 0) {
-      const int nw = ((imgH + G - 1) / G) * ((imgW + G - 1) / G);
-      LA_CHECK_ARG(imgW > 0 && padrow && B % nw == 0, "la_attn_fwd_rows: image-order windows need imgW, padrow and B = images * %d windows", nw);
-      a.imgH = imgH;
-      a.imgW = imgW;
-      a.padrow = padrow;
-    }
-    la::set_win_magic(a);
-    const size_t lds = 4 * 32 * 33 * sizeof(float);
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 5, true>(a, lds, st);
-    else la::launch_attn<la::bf16_t, 5, true>(a, lds, st);
-  } else if (mode == LA_ATTN_RELPOS) {
-    LA_CHECK_ARG(tabh && tabw && G == 64 && T == 4096, "la_attn_fwd_rows: rel-pos form needs the tables and the 64 x 64 grid (G=%d T=%d)", G, T);
-    const size_t lds = 4 * 32 * 33 * sizeof(float);
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 4, true>(a, lds, st);
-    else la::launch_attn<la::bf16_t, 4, true>(a, lds, st);
-  } else {
-    LA_CHECK_ARG(false, "la_attn_fwd_rows: bad mode %d", mode);
-  }
-  LA_CHECK_LAUNCH("la_attn_fwd_rows");
-  return 0;
+  LaAttnCall c = la::attn_call(B, heads, T, Tpad, G, E, mode, dt);
+  c.qkv = qkv, c.out16 = out16, c.tabh = tabh, c.tabw = tabw, c.cspart = cspart;
+  c.imgH = imgH, c.imgW = imgW, c.padrow = padrow;
+  return la::attn_fwd_run(LA_ATTN_EP_FWD_ROWS, c, scale, stream);
 }
 
 extern "C" int la_attn_fwd_lse(const void* qkv, const void* vt, void* out16, float* lse, int B, int heads, int T, int Tpad, int E, float scale,
                                int dt, void* stream) {
-  LA_CHECK_ARG(qkv && vt && out16 && lse, "la_attn_fwd_lse: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_fwd_lse: needs head_dim 64 or 128 - other widths zero-padded (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_fwd_lse: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_fwd_lse: bad dtype %d", dt);
-  la::AttnArgs a{qkv, vt, out16, nullptr, nullptr, nullptr, nullptr, B, heads, T, Tpad, 0, E, scale, lse};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dt == LA_F16) la::launch_attn<la::f16_t, 0>(a, 0, st);
-  else la::launch_attn<la::bf16_t, 0>(a, 0, st);
-  LA_CHECK_LAUNCH("la_attn_fwd_lse");
-  return 0;
+  LaAttnCall c = la::attn_call(B, heads, T, Tpad, 0, E, LA_ATTN_PLAIN, dt);
+  c.qkv = qkv, c.vt = vt, c.out16 = out16, c.lse = lse;
+  return la::attn_fwd_run(LA_ATTN_EP_FWD_LSE, c, scale, stream);
 }
 
 extern "C" int la_attn_fwd_relpos_lse(const void* qkv, const void* vt, void* out16, const float* relh, const float* relw, float* lse, int B, int heads,
                                       int T, int Tpad, int G, int E, float scale, int dt, void* stream) {
-  LA_CHECK_ARG(qkv && vt && out16 && relh && relw && lse, "la_attn_fwd_relpos_lse: null pointer");
-  LA_CHECK_ARG(B > 0 && heads > 0 && T > 0 && (E == heads * 64 || E == heads * 128),
-               "la_attn_fwd_relpos_lse: needs head_dim 64 or 128 - other widths zero-padded (E=%d heads=%d)", E, heads);
-  LA_CHECK_ARG(Tpad >= T && (Tpad % 64) == 0, "la_attn_fwd_relpos_lse: Tpad=%d must be a multiple of 64 covering T=%d", Tpad, T);
-  LA_CHECK_ARG(G > 0 && G <= 64 && G * G == T, "la_attn_fwd_relpos_lse: rel-pos needs T == G*G, G <= 64 (T=%d G=%d)", T, G);
-  LA_CHECK_ARG(dt == LA_F16 || dt == LA_BF16, "la_attn_fwd_relpos_lse: bad dtype %d", dt);
-  la::AttnArgs a{qkv, vt, out16, relh, relw, nullptr, nullptr, B, heads, T, Tpad, G, E, scale, lse};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (G == 64) {
-    const size_t lds = 4 * 32 * 65 * sizeof(float);
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 2>(a, lds, st);
-    else la::launch_attn<la::bf16_t, 2>(a, lds, st);
-  } else {
-    const size_t lds = 4 * 2 * 32 * (G + 1) * sizeof(float) + (size_t)Tpad * sizeof(int);
-    if (dt == LA_F16) la::launch_attn<la::f16_t, 1>(a, lds, st);
-    else la::launch_attn<la::bf16_t, 1>(a, lds, st);
-  }
-  LA_CHECK_LAUNCH("la_attn_fwd_relpos_lse");
-  return 0;
+  LaAttnCall c = la::attn_call(B, heads, T, Tpad, G, E, LA_ATTN_RELPOS, dt);
+  c.qkv = qkv, c.vt = vt, c.out16 = out16, c.relh = relh, c.relw = relw, c.lse = lse;
+  return la::attn_fwd_run(LA_ATTN_EP_FWD_RELPOS_LSE, c, scale, stream);
 }
 
 extern "C" int la_qk_fp8(const void* qkv, long rows, int E, void* qk8, int dt, void* stream) {

@@ -410,13 +410,6 @@ static void launch(dim3 grid, const LaGemmPlan& p, const GemmArgs& g, Extra... e
                      g.N, g.K / p.planes, g.e, extra...);
 }
 
-// f(std::integral_constant<int, E>) for the E among Es that v equals: a plan field becomes a template argument; false: none did
-template <int... Es, typename F>
-static bool with_int(int v, F&& f) {
-  return (((v == Es) && (f(std::integral_constant<int, Es>{}), true)) || ...);
-}
-#define LA_V(x) decltype(x)::value
-
 // gemm_w4.hip: the four-wave persistent 256 x 256 x 64 kernel (EPI 1 / 2 / 3 as epilogue_wave); stg: start stagger (measurement library only, else 0)
 template <typename T, int EPI>
 void launch_t256w(const LaGemmPlan& p, const GemmArgs& g, int stg);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // Measurement / debugging switches (environment overrides of kernel selection, ablation bits of la_gemm_variant) exist only in a
 // -DLA_DEBUG build (`make DEBUG=1` -> libla_hip_dbg.so, loaded by tools/ through LA_HIP_LIB): the product library never reads the
@@ -215,6 +216,21 @@ static inline void ensure_dyn_lds(const void* kernel, int bytes, unsigned long l
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (dev >= 0 && dev < 64) mask |= 1ull << dev;
 }
+
+// launch kernel instantiation Kern; limit > 0: with its dynamic-LDS limit raised to `limit` bytes first (once per instantiation and device)
+template <auto Kern, typename... Args>
+static void launch_dyn(int grid, int block, int lds_bytes, int limit, hipStream_t st, Args... args) {
+  static unsigned long long attr_mask = 0;
+  if (limit > 0) ensure_dyn_lds(reinterpret_cast<const void*>(Kern), limit, attr_mask);
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds_bytes, st, args...);
+}
+
+// f(std::integral_constant<int, E>) for the E among Es that v equals: a plan field becomes a template argument; false: none did
+template <int... Es, typename F>
+static bool with_int(int v, F&& f) {
+  return (((v == Es) && (f(std::integral_constant<int, Es>{}), true)) || ...);
+}
+#define LA_V(x) decltype(x)::value
 
 // compute units of the CURRENT device, cached per device (a process may drive several GPUs)
 inline int cu_count() {
