@@ -29,6 +29,9 @@
 #ifndef LA_WIN_HALF
 #define LA_WIN_HALF 1       // SAM windows: the last key tile runs its lower 32 slots only when the upper 32 are padding (0: full tile, A/B)
 #endif
+#ifndef LA_ATTN_STAGE_AT
+#define LA_ATTN_STAGE_AT 1  // attn_fwd_kernel: the next tile's LDS-DMA pieces go out 1: one by one between the groups of the softmax's exponentials, K first - the windows (WIN16) keep them at the top of the tile (0: at the top everywhere, 2: inside the softmax everywhere; tools/attn_ab.sh A/B)
+#endif
 #ifndef LA_ATTN_X
 #define LA_ATTN_X 0         // timing experiments (results wrong beyond tile 0): 2 no maximum pass after the first tile, 4 exp2 of the bare score, 8 no row sums
 #endif
@@ -131,18 +134,35 @@ __device__ __forceinline__ float xhalf_sum(float v) {
 
 #ifdef LA_DEBUG
 // phase timeline of the window instance of attn_fwd_kernel (ATTN_TABLES_WIN16): s_memtime of the workgroup in the MIDDLE of the launch (steady state),
-// [wave][i]; tools/win_phases.py
+// [wave][i]; tools/win_phases.py.  (The stamps collect in the lanes of a register pair and are stored at the end of the kernel: a store inside
+// the key loop is counted by vmcnt, and the tile's wait for the next tile then waits for the stamp as well.)
 __device__ unsigned long long g_win_stamps[4 * 16];
 #define WIN_STAMP(i)                                                                                  \
   do {                                                                                                \
     if (MODE == ATTN_TABLES_WIN16 && blockIdx.x == gridDim.x / 2) {                                   \
       unsigned long long t_;                                                                          \
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                     \
-      if ((threadIdx.x & 63) == 0) g_win_stamps[(threadIdx.x >> 6) * 16 + (i)] = t_;                   \
+      win_log = (int)(threadIdx.x & 63) == (i) ? t_ : win_log;                                        \
     }                                                                                                 \
+  } while (0)
+// per-tile timeline of the key loop, ATTN_TABLES_ROW64 (instance 0: tiles 28 .. 35, the middle of 64, with the table refill at 32) and
+// ATTN_TABLES_WIN16 (instance 1: tiles 0 .. 3): [instance][wave][tile][point], low 32 bits of s_memtime; points 0 top of the tile, 1 last piece
+// of the next tile issued, 2 S MFMAs issued, 3 softmax done, 4 P . V MFMAs issued, 5 after the wait, 6 after the barrier.  The stamps of a wave
+// collect in the lanes of ONE register (lane 8 tile + point) and are stored after the loop: no store - nothing counted by vmcnt - inside the loop.
+// tools/attn_tile_phases.py
+__device__ unsigned g_tile_stamps[2 * 4 * 64];
+#define TILE_STAMP(p)                                                                                                         \
+  do {                                                                                                                        \
+    if ((MODE == ATTN_TABLES_WIN16 || MODE == ATTN_TABLES_ROW64) && blockIdx.x == gridDim.x / 2 &&                            \
+        (unsigned)(j - tile_j0) < 8u) {                                                                                       \
+      unsigned long long t_;                                                                                                  \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                                             \
+      tile_log = lane == (j - tile_j0) * 8 + (p) ? (unsigned)t_ : tile_log;                                                  \
+    }                                                                                                                         \
   } while (0)
 #else
 #define WIN_STAMP(i) do {} while (0)
+#define TILE_STAMP(p) do {} while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -200,8 +220,12 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
   constexpr bool ROW64 = MODE == ATTN_TERMS_ROW64 || MODE == ATTN_TABLES_ROW64;       // G == 64: a key tile is one key row
   constexpr int HDT = 64 * NH, KS = 4 * NH, SUB = 64 * 64 * 2, KVS = KV_STAGE * NH;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+#ifdef LA_DEBUG
+  unsigned long long win_log = 0ull;
+#endif
   WIN_STAMP(0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (a scalar: the idle-wave test, the pieces' LDS destinations and the per-wave tables hold no vector register)
   const int fr = lane & 31, fh = lane >> 5;
   const int BH = a.B * a.heads;
   // Workgroup -> (image*head, query block).  Workgroup b runs on XCD b % 8; the ~64 workgroups an XCD has in flight must
@@ -307,55 +331,68 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
     vrun[i] = (unsigned)(((size_t)krow[i] * E3 + voff[i]) * sizeof(T));
   }
   const unsigned tile_step = (unsigned)((size_t)64 * E3 * sizeof(T));
-  auto dma = [&](int j, int stage) {
-    const unsigned sk = lds0 + stage * KVS;
-    const unsigned sv = sk + NH * SUB;
+  // Staging a tile is two steps, so that a piece can go out from straight-line code in the middle of the softmax: dma_src(j) - at the top of
+  // the tile before, with every branch the addresses need - settles where the wave's pieces of tile j come from; dma(j, stage, pieces) only
+  // issues.  (A branch beside a piece makes a basic block of it, and hipcc then sinks the exponentials behind all four.)
+  //   running form: the offsets krun / vrun ARE the sources.  The ragged tile is the last one staged, so its clamp - rows beyond T - 1
+  //   re-read row T - 1, masked later - is applied to them in place (wave-uniform branch); they are not used again.
+  //   windows, and the A/B form without running offsets: row pointers src_k / src_v, held from the top of the tile to the pieces.
+  const T* src_k[2] = {nullptr, nullptr};
+  const T* src_v[2] = {nullptr, nullptr};
+  auto dma_src = [&](int j) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int key = 0;
-      const T* kp = nullptr;
-      const T* vp = nullptr;
       if (!WIN16 && !LA_ATTN_DMA_RUN) {      // (A/B build: clamp + 64-bit multiply-add per piece, the form before round 6)
         key = min(j * 64 + krow[i], T_ - 1);
-        kp = ksrc[i] + (size_t)key * E3;
-        if (VROW) vp = vsrc[i] + (size_t)key * E3;
+        src_k[i] = ksrc[i] + (size_t)key * E3;
+        if (VROW) src_v[i] = vsrc[i] + (size_t)key * E3;
       } else if (!WIN16) {
-        unsigned ko = krun[i], vo = vrun[i];
-        if (j * 64 + 64 > T_) {          // (wave-uniform: the last, ragged tile) rows beyond T - 1 re-read row T - 1, masked later
+        if (j * 64 + 64 > T_) {
           const unsigned back = (unsigned)max(j * 64 + krow[i] - (T_ - 1), 0) * (unsigned)(E3 * sizeof(T));
-          ko -= back;
-          vo -= back;
+          krun[i] -= back;
+          vrun[i] -= back;
         }
-        krun[i] += tile_step;
-        vrun[i] += tile_step;
-#pragma unroll
-        for (int hh = 0; hh < NH; ++hh) {
-          dma16s(img_base, ko + hh * 128, sk + hh * SUB + (i * 4 + wave) * 1024);
-          if (VROW) dma16s(img_base, vo + hh * 128, sv + hh * SUB + (i * 4 + wave) * 1024);
-          else dma16(vsrc[i] + (size_t)hh * 64 * a.Tpad + j * 64, sv + hh * SUB + (i * 4 + wave) * 1024);
-        }
-        continue;
-      } else if (WIN16) {   // slot -> token of the ws x ws window (padded slots read a clamped, later masked, row)
+      } else {              // slot -> token of the ws x ws window (padded slots read a clamped, later masked, row)
         const int slot = j * 64 + krow[i];
         const int ty = min(slot >> 4, a.G - 1), tx = min(slot & 15, a.G - 1);
         key = ty * a.G + tx;
         if (img_order) {
           const long r = img_row(ty, tx);
           const T* rp = r >= 0 ? qkv + (size_t)r * E3 : padrow;
-          kp = rp + koff[i];
-          vp = rp + voff[i];
+          src_k[i] = rp + koff[i];
+          src_v[i] = rp + voff[i];
+        } else {
+          src_k[i] = ksrc[i] + (size_t)key * E3;
+          if (VROW) src_v[i] = vsrc[i] + (size_t)key * E3;
         }
       }
-      if (WIN16 && !img_order) {
-        kp = ksrc[i] + (size_t)key * E3;
-        if (VROW) vp = vsrc[i] + (size_t)key * E3;
-      }
+    }
+  };
+  // pieces: which of the wave's four pieces of the tile go out in this call - bit i: K rows of half i, bit 2 + i: V rows of half i (a piece = NH
+  // instructions; every piece of a tile exactly once, a running offset advances with its piece)
+  auto dma = [&](int j, int stage, int pieces = 15) {
+    const unsigned sk = lds0 + stage * KVS;
+    const unsigned sv = sk + NH * SUB;
+    constexpr bool RUN = !WIN16 && LA_ATTN_DMA_RUN;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const bool do_k = (pieces >> i) & 1, do_v = (pieces >> (2 + i)) & 1;
+      const unsigned dst = (i * 4 + wave) * 1024;
 #pragma unroll
       for (int hh = 0; hh < NH; ++hh) {            // dims 64 hh .. of K (and of the V rows), rows 64 hh .. of V^T
-        dma16(kp + hh * 64, sk + hh * SUB + (i * 4 + wave) * 1024);
-        if (VROW) dma16(vp + hh * 64, sv + hh * SUB + (i * 4 + wave) * 1024);
-        else dma16(vsrc[i] + (size_t)hh * 64 * a.Tpad + j * 64, sv + hh * SUB + (i * 4 + wave) * 1024);
+        if (do_k) {
+          if (RUN) dma16s(img_base, krun[i] + hh * 128, sk + hh * SUB + dst);
+          else dma16(src_k[i] + hh * 64, sk + hh * SUB + dst);
+        }
+        if (do_v) {
+          if (!VROW) dma16(vsrc[i] + (size_t)hh * 64 * a.Tpad + j * 64, sv + hh * SUB + dst);
+          else if (RUN) dma16s(img_base, vrun[i] + hh * 128, sv + hh * SUB + dst);
+          else dma16(src_v[i] + hh * 64, sv + hh * SUB + dst);
+        }
       }
+      if (RUN && do_k) krun[i] += tile_step;
+      if (RUN && do_v) vrun[i] += tile_step;
     }
   };
 
@@ -366,6 +403,7 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
   // windows: the last tile's upper 32 key slots are all padding (G = 14: key rows 14 / 15) - their scores carry NEG_BIG, exp2 gives exactly 0,
   // so the tile runs its lower half only and no bit changes
   const bool half_last = WIN16 && LA_WIN_HALF && ((16 * a.G) & 63) != 0 && ((16 * a.G) & 63) <= 32;
+  dma_src(0);
   dma(0, 0);
   WIN_STAMP(1);
 
@@ -538,14 +576,37 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
   WIN_STAMP(3);
   // a wave whose 32 query rows all lie beyond T (T = 901: three of the 32 waves of an image-head) only helps staging the tiles
   const bool idle_wave = q0 >= T_;
-  for (int j = 0; j < ntiles; ++j) {
-#if !(LA_ATTN_ABL & 8)
-    if (j + 1 < ntiles) dma(j + 1, (j + 1) & 1);
+#ifdef LA_DEBUG
+  unsigned tile_log = 0u;
+  const int tile_j0 = WIN16 ? 0 : 28;
 #endif
+  // One key tile.  LAST - the last tile, which stages nothing - is a compile-time constant and the loop below runs two copies of the body:
+  // behind a run-time test of j every piece is a basic block of its own, and hipcc gathers all four in front of the first exponential.
+  auto tile = [&](const int j, auto last_tile) {
+    constexpr bool LAST = decltype(last_tile)::value;
+    TILE_STAMP(0);
+    // Staging of tile j + 1.  Issued at the top of the tile, the wave's four pieces stand in front of the K fragment reads and the score
+    // MFMAs and hold them up; their bytes are not needed before the bottom of the tile.  So a working wave sends them from the vector-only
+    // stretch instead, one piece in front of each group of eight exponentials, K first (stage_piece).  An idle wave has no such stretch: it
+    // sends all four here, as before, and goes to the barrier.
+    constexpr bool stage_next = !LAST && !(LA_ATTN_ABL & 8);
+    // (the windows' four-tile loop waits for its rows at the bottom of every tile: there the early request is worth more than the slot)
+    constexpr bool stage_in_softmax = LA_ATTN_STAGE_AT == 2 || (LA_ATTN_STAGE_AT == 1 && !WIN16);
+    if (stage_next) dma_src(j + 1);
+    if (stage_next && (!stage_in_softmax || idle_wave)) dma(j + 1, (j + 1) & 1);
+    // piece p of tile j + 1, pinned where it stands: nothing is scheduled across it in either direction
+    auto stage_piece = [&](int p) {
+      if (stage_in_softmax && stage_next) {
+        __builtin_amdgcn_sched_barrier(0);
+        dma(j + 1, (j + 1) & 1, 1 << p);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if (!stage_in_softmax) TILE_STAMP(1);
     if (idle_wave) {
       dma_wait<0>();
       __syncthreads();
-      continue;
+      return;
     }
     const char* sk = smem + (j & 1) * KVS;
     const char* sv = sk + NH * SUB;
@@ -555,7 +616,7 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
     // (no per-tile initialisation pass); the per-row scalar relh[q][tile] is folded into the softmax constants below.
     f32x16 s[2];
     float rh = 0.f;
-    const bool half = WIN16 && half_last && j == ntiles - 1;      // (wave-uniform)
+    const bool half = WIN16 && LAST && half_last;      // (wave-uniform)
     if (MODE == ATTN_TERMS_ROW64) rh = my_bh[fr * 65 + j];
     if (MODE == ATTN_TABLES_ROW64) rh = my_bh[fr * 33 + (j & 31)];
 #pragma unroll
@@ -593,6 +654,7 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
       }
     }
 #endif
+    TILE_STAMP(2);
     if (MODE == ATTN_TERMS) {
       const int GS = a.G + 1;
 #pragma unroll
@@ -658,10 +720,15 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
     const float mc = (rh - m_run) * c2;
     float psum = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int tg = 0; tg < 4; ++tg) {
+      // one staging piece in front of every eight exponentials - in front of the half-tile skip too (a half tile is a last tile and stages
+      // nothing, but the placement does not rest on that)
+      stage_piece(tg);
+      if (stage_in_softmax && tg == 3) TILE_STAMP(1);
+      const int t = tg >> 1;
       if (WIN16 && t == 1 && half) continue;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
+      for (int r = (tg & 1) * 8; r < (tg & 1) * 8 + 8; ++r) {
         // (scalar FMAs on purpose: v_pk_fma_f32 does not overlap with another wave's MFMA stream at all, v_fma_f32 partly, v_exp_f32
         // fully - tools/probes/coissue.hip; the packed form of this loop measured 0.7 % slower)
 #if LA_ATTN_ABL & 1
@@ -695,6 +762,7 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
       const auto r1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
       pf[ks] = make_uint4(r0[0], r1[0], r0[1], r1[1]);
     }
+    TILE_STAMP(3);
 
     // ---- O^T += V^T P^T -----------------------------------------------------------------------------------
 #if LA_ATTN_ABL & 4
@@ -722,14 +790,23 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
       }
     }
 #endif
+    TILE_STAMP(4);
 
 #if !(LA_ATTN_ABL & 8)
     if (j < 4) WIN_STAMP(8 + j);      // (the tile's own work is done; what follows is the wait for the next tile + the barrier)
-    dma_wait<0>();     // next tile (issued before this tile's MFMAs) has landed for this wave ...
+    dma_wait<0>();     // next tile (requested earlier in this tile) has landed for this wave ...
+    TILE_STAMP(5);
     __syncthreads();   // ... and for all waves; orders the stage swap
 #endif
+    TILE_STAMP(6);
     if (j < 4) WIN_STAMP(4 + j);
-  }
+  };
+  for (int j = 0; j + 1 < ntiles; ++j) tile(j, std::false_type{});
+  tile(ntiles - 1, std::true_type{});
+#ifdef LA_DEBUG
+  if ((MODE == ATTN_TABLES_WIN16 || MODE == ATTN_TABLES_ROW64) && blockIdx.x == gridDim.x / 2)
+    g_tile_stamps[((MODE == ATTN_TABLES_WIN16 ? 1 : 0) * 4 + wave) * 64 + lane] = tile_log;
+#endif
 
   // ---- normalise and store: lane holds O[q][d*32 + 8*g + 4*fh + 0..3] ---------------------------------------
   const float l_tot = xhalf_sum(l_run);
@@ -748,6 +825,9 @@ __global__ __launch_bounds__(256, (((MODE == ATTN_TABLES_ROW64 || MODE == ATTN_T
       }
   }
   WIN_STAMP(12);
+#ifdef LA_DEBUG
+  if (MODE == ATTN_TABLES_WIN16 && blockIdx.x == gridDim.x / 2 && lane < 16) g_win_stamps[wave * 16 + lane] = win_log;
+#endif
   if (a.cspart != nullptr) {
     // Column sums of the block's stored rows ON THE MATRIX PIPE: a wave writes its 32 normalised 16-bit rows into LDS in the V tile's
     // layout (the K / V stages are idle: the key loop ended with a barrier) and runs the P . V step on them with P = 1 -
@@ -1230,6 +1310,10 @@ extern "C" int la_relpos_terms(const void* qkv, int B, int heads, int G, int E, 
 extern "C" int la_dbg_win_stamps(unsigned long long* host_out) {
   (void)hipDeviceSynchronize();
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(la::g_win_stamps), sizeof(unsigned long long) * 64);
+}
+extern "C" int la_dbg_tile_stamps(unsigned* host_out) {
+  (void)hipDeviceSynchronize();
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(la::g_tile_stamps), sizeof(unsigned) * 512);
 }
 #endif
 
