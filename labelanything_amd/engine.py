@@ -1048,17 +1048,13 @@ class LamEngine:
     def _attn_core(self, q32, k32, v32, groups, nq, nk, internal, tag, image_side: bool = False) -> Tensor:
         """image_side: the output feeds an image-side GEMM (rows = groups * hw): plane-pair operand in split mode."""
         heads = self.cfg.dec_heads
-        if image_side:
-            o16 = self.ibuf(tag + ".o16", groups * nq, internal)
-            L.attn_small(q32, k32, v32, groups, nq, nk, heads, internal // heads, out16=o16, dt=self.idti)
-            return o16
-        o16 = self.dbuf(tag + ".o16", (groups * nq, internal))
-        L.attn_small(q32, k32, v32, groups, nq, nk, heads, internal // heads, out16=o16, dt=self.ddti)
+        o16 = self.ibuf(tag + ".o16", groups * nq, internal) if image_side else self.dbuf(tag + ".o16", (groups * nq, internal))
+        L.attn_small(q32, k32, v32, groups, nq, nk, heads, internal // heads, out16=o16, dt=self.idti if image_side else self.ddti)
         return o16
 
     def attention_mlp_block(self, pre: str, x32: Tensor, groups: int, n: int, tag: str) -> Tensor:
         """AttentionMLPBlock (common.py:151-184): y = LN(attn(x)+x); out = LN(mlp(y)+y), one shared LayerNorm, GELU."""
-        w, p = self.w32, self.p
+        p = self.p
         rows, d = x32.shape
         internal = p[pre + ".attn.q_proj.w"].shape[0]
         x16 = self.dbuf(tag + ".x16", (rows, d))
@@ -1067,15 +1063,25 @@ class LamEngine:
         L.gemm(x16, p[pre + ".attn.qkv.w"], bias=p[pre + ".attn.qkv.b"], out32=qkv)
         o16 = self._attn_core(qkv[:, :internal], qkv[:, internal:2 * internal], qkv[:, 2 * internal:], groups, n, n, internal, tag)
         y = self.f32(tag + ".y", (rows, d))
-        L.gemm(o16, p[pre + ".attn.out_proj.w"], bias=w[pre + ".attn.out_proj.bias"], res=x32, out32=y)
         y16 = self.dbuf(tag + ".y16", (rows, d))
-        self.dln(y, pre + ".norm", 1e-5, out32=y, out16=y16)
-        hbuf = self.dbuf(tag + ".h", (rows, self.cfg.dec_mlp))
-        L.gemm(y16, p[pre + ".mlp.lin1.w"], bias=w[pre + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_GELU)
+        self._token_sublayer(o16, pre + ".attn.out_proj", pre + ".norm", x32, y, y, y16)
         z = self.f32(tag + ".z", (rows, d))
-        L.gemm(hbuf, p[pre + ".mlp.lin2.w"], bias=w[pre + ".mlp.lin2.bias"], res=y, out32=z)
-        self.dln(z, pre + ".norm", 1e-5, out32=z)
+        self._token_mlp(y16, pre + ".mlp", L.ACT_GELU, tag + ".h", pre + ".norm", y, z, z, None)
         return z
+
+    def _token_sublayer(self, a: Tensor, mod: str, norm: str, res, tnew: Tensor, t32: Tensor, t16, tq16=None, tpe=None) -> None:
+        """End of a token-side sub-layer (transformer.py:303-320, 248-250, 146-152; common.py:176-183): tnew = a W^T + b of ``mod`` (+ res),
+        (t32, t16) = LayerNorm ``norm`` of it as fp32 / GEMM operand; tq16: the operand copy of t32 + tpe (tokens + their PE) as well."""
+        w = self.w32
+        L.gemm(a, self.p[mod + ".w"], bias=w[mod + ".bias"], res=res, out32=tnew)
+        L.layernorm(tnew, w[norm + ".weight"], w[norm + ".bias"], 1e-5, out32=t32, out16=t16, out16_pe=tq16, pe=tpe, dt=self.ddti)
+
+    def _token_mlp(self, x16: Tensor, mlp: str, act: int, hname: str, norm: str, res, tnew: Tensor, t32: Tensor, t16, tq16=None, tpe=None):
+        """Token-side MLP sub-layer (transformer.py:317-320, 149-152; common.py:181-183): lin1 + ``act`` into the 16-bit hidden buffer
+        ``hname``, then lin2 + res and the norm as in ``_token_sublayer``."""
+        hbuf = self.dbuf(hname, (x16.shape[0], self.cfg.dec_mlp))
+        L.gemm(x16, self.p[mlp + ".lin1.w"], bias=self.w32[mlp + ".lin1.bias"], out16=hbuf, act=act)
+        self._token_sublayer(hbuf, mlp + ".lin2", norm, res, tnew, t32, t16, tq16, tpe)
 
     def fused_ok(self, nt: int) -> bool:
         return self.fuse_twoway and nt <= 32
@@ -1092,19 +1098,19 @@ class LamEngine:
             self._pe_tables[key] = t
         return t
 
-    def _t2i(self, ca: str, q: Tensor, img32: Tensor, pe32: Tensor, img16, imgpe16, groups: int, nt: int, hw: int, tag: str) -> Tensor:
-        """Attention output (before out_proj) of the tokens over the image side; fused: K / V are never materialised."""
-        w, p = self.w32, self.p
-        di = self.cfg.embed_dim // 2
+    def _t2i(self, ca: str, tq16: Tensor, img32: Tensor, pe32: Tensor, img16, imgpe16, groups: int, nt: int, hw: int, tag: str) -> Tensor:
+        """Attention output (before out_proj) of the tokens, queries from tq16 = tokens + PE, over the image side (transformer.py:310-313,
+        245-248); fused: K / V are never materialised."""
+        w, p, di, ri = self.w32, self.p, self.cfg.embed_dim // 2, groups * hw
+        q = self.f32(tag + ".tq", (groups * nt, di))
+        L.gemm(tq16, p[ca + ".q_proj.w"], bias=w[ca + ".q_proj.bias"], out32=q)
         if self.fused_ok(nt):
             o = self.f32(tag + ".t2i.o", (groups * nt, di))
             part = self.f32(tag + ".t2i.part", (L.twoway_part_size(groups, hw, nt, self.cfg.embed_dim),))
             L.twoway_t2i(img32, p[ca + ".k_proj.planes"], p[ca + ".v_proj.planes"], self.pe_table(ca + ".k_proj", pe32), w[ca + ".v_proj.bias"], q,
                          groups, hw, nt, self.cfg.dec_heads, part, o)
             return o
-        ri = groups * hw
-        k = self.f32(tag + ".ik", (ri, di))
-        v = self.f32(tag + ".iv", (ri, di))
+        k, v = self.f32(tag + ".ik", (ri, di)), self.f32(tag + ".iv", (ri, di))
         self.igemm(imgpe16, ca + ".k_proj.w", bias=w[ca + ".k_proj.bias"], out32=k)
         self.igemm(img16, ca + ".v_proj.w", bias=w[ca + ".v_proj.bias"], out32=v)
         return self._attn_core(q, k, v, groups, nt, hw, di, tag + ".t2i")
@@ -1114,11 +1120,9 @@ class LamEngine:
         """TwoWayTransformer (transformer.py:206-329).  tok32 [groups*nt, D] fp32 (also the token PE); image side
         [groups*hw, D] as fp32 stream, updated in place (+ its GEMM-operand copies x and x+pe when the unfused chain runs:
         ``fused_ok(nt)`` false).  Returns (tokens32, tokens16)."""
-        w, p, cfg = self.w32, self.p, self.cfg
-        d = cfg.embed_dim
-        di = d // 2
+        w, p = self.w32, self.p
+        d = self.cfg.embed_dim
         r = groups * nt
-        ri = groups * hw
         fused = self.fused_ok(nt)
         tpe = tok32
         t32 = self.f32(tag + ".t32", (r, d))
@@ -1133,52 +1137,51 @@ class LamEngine:
                 qkv = self.f32(tag + ".sa_qkv", (r, 3 * d))
                 L.gemm(t16, p[sa + ".qkv.w"], bias=p[sa + ".qkv.b"], out32=qkv)
                 o16 = self._attn_core(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], groups, nt, nt, d, tag + ".sa")
-                L.gemm(o16, p[sa + ".out_proj.w"], bias=w[sa + ".out_proj.bias"], out32=tnew)      # replaces the tokens
             else:
                 qk = self.f32(tag + ".sa_qk", (r, 2 * d))
                 L.gemm(tq16, p[sa + ".qk.w"], bias=p[sa + ".qk.b"], out32=qk)
                 v = self.f32(tag + ".sa_v", (r, d))
                 L.gemm(t16, p[sa + ".v_proj.w"], bias=w[sa + ".v_proj.bias"], out32=v)
                 o16 = self._attn_core(qk[:, :d], qk[:, d:], v, groups, nt, nt, d, tag + ".sa")
-                L.gemm(o16, p[sa + ".out_proj.w"], bias=w[sa + ".out_proj.bias"], res=t32, out32=tnew)
-            self.dln(tnew, lp + ".norm1", 1e-5, out32=t32, out16=t16, out16_pe=tq16, pe=tpe, pe_mod=0)
+            # (layer 0's self-attention has no residual: its output replaces the tokens)
+            self._token_sublayer(o16, sa + ".out_proj", lp + ".norm1", t32 if l else None, tnew, t32, t16, tq16, tpe)
             # tokens -> image
             ca = lp + ".cross_attn_token_to_image"
-            q = self.f32(tag + ".tq", (r, di))
-            L.gemm(tq16, p[ca + ".q_proj.w"], bias=w[ca + ".q_proj.bias"], out32=q)
-            o16 = self._t2i(ca, q, img32, pe32, img16, imgpe16, groups, nt, hw, tag)
-            L.gemm(o16, p[ca + ".out_proj.w"], bias=w[ca + ".out_proj.bias"], res=t32, out32=tnew)
-            self.dln(tnew, lp + ".norm2", 1e-5, out32=t32, out16=t16)
+            o16 = self._t2i(ca, tq16, img32, pe32, img16, imgpe16, groups, nt, hw, tag)
+            self._token_sublayer(o16, ca + ".out_proj", lp + ".norm2", t32, tnew, t32, t16)
             # MLP (ReLU)
-            hbuf = self.dbuf(tag + ".mlp", (r, cfg.dec_mlp))
-            L.gemm(t16, p[lp + ".mlp.lin1.w"], bias=w[lp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_RELU)
-            L.gemm(hbuf, p[lp + ".mlp.lin2.w"], bias=w[lp + ".mlp.lin2.bias"], res=t32, out32=tnew)
-            self.dln(tnew, lp + ".norm3", 1e-5, out32=t32, out16=t16, out16_pe=tq16, pe=tpe, pe_mod=0)
-            # image -> tokens
-            ca = lp + ".cross_attn_image_to_token"
-            kt = self.f32(tag + ".tk", (r, di))
-            vtok = self.f32(tag + ".tv", (r, di))
-            L.gemm(tq16, p[ca + ".k_proj.w"], bias=w[ca + ".k_proj.bias"], out32=kt)
-            L.gemm(t16, p[ca + ".v_proj.w"], bias=w[ca + ".v_proj.bias"], out32=vtok)
-            if fused:       # q_proj + attention + out_proj + residual + norm4: one read and one write of the stream
-                L.twoway_i2t(img32, p[ca + ".q_proj.planes"], self.pe_table(ca + ".q_proj", pe32), kt, vtok, p[ca + ".out_proj.planes"],
-                             w[ca + ".out_proj.bias"], w[lp + ".norm4.weight"], w[lp + ".norm4.bias"], 1e-5, groups, hw, nt, cfg.dec_heads)
-            else:
-                qi = self.f32(tag + ".iq", (ri, di))
-                self.igemm(imgpe16, ca + ".q_proj.w", bias=w[ca + ".q_proj.bias"], out32=qi)
-                oi16 = self._attn_core(qi, kt, vtok, groups, hw, nt, di, tag + ".i2t", image_side=True)
-                self.igemm(oi16, ca + ".out_proj.w", bias=w[ca + ".out_proj.bias"], res=img32, out32=img32)
-                L.layernorm(img32, w[lp + ".norm4.weight"], w[lp + ".norm4.bias"], 1e-5, out32=img32, out16=img16, out16_pe=imgpe16, pe=pe32,
-                            pe_mod=hw, dt=self.idti)
+            self._token_mlp(t16, lp + ".mlp", L.ACT_RELU, tag + ".mlp", lp + ".norm3", t32, tnew, t32, t16, tq16, tpe)
+            # image -> tokens; the norm leaves x and x + pe up to date for the next layer
+            self._image_from_tokens(lp + ".cross_attn_image_to_token", lp + ".norm4", True, fused, tq16, t16, "", img32, img16, imgpe16, pe32,
+                                    groups, nt, hw, tag)
         if not want_tokens:
             return None, None
         ca = pre + ".final_attn_token_to_image"
-        q = self.f32(tag + ".tq", (r, di))
-        L.gemm(tq16, p[ca + ".q_proj.w"], bias=w[ca + ".q_proj.bias"], out32=q)
-        o16 = self._t2i(ca, q, img32, pe32, img16, imgpe16, groups, nt, hw, tag)
-        L.gemm(o16, p[ca + ".out_proj.w"], bias=w[ca + ".out_proj.bias"], res=t32, out32=tnew)
-        self.dln(tnew, pre + ".norm_final_attn", 1e-5, out32=t32, out16=t16)
+        o16 = self._t2i(ca, tq16, img32, pe32, img16, imgpe16, groups, nt, hw, tag)
+        self._token_sublayer(o16, ca + ".out_proj", pre + ".norm_final_attn", t32, tnew, t32, t16)
         return t32, t16
+
+    def _image_from_tokens(self, ca: str, norm: str, refresh_pe: bool, fused: bool, tk16: Tensor, tv16: Tensor, kv: str, img32: Tensor,
+                           img16, imgpe16, pe32: Tensor, groups: int, nt: int, hw: int, tag: str) -> None:
+        """Image <- tokens attention of a TwoWayAttentionBlock (transformer.py:322-327) / OneWayAttentionBlock (transformer.py:143-147):
+        k / v from the token operands tk16 / tv16 into the buffers tag.tk<kv> / tag.tv<kv>, then in place on the fp32 stream
+        img = LayerNorm ``norm`` (img + out_proj(attn(q = img + pe, k, v))).  fused: one la_twoway_i2t.  Otherwise the chain on the operand
+        copies: q from imgpe16 (x + pe); the norm writes img16 (x) and, with refresh_pe, imgpe16 for the next attention that reads it."""
+        w, p = self.w32, self.p
+        di = self.cfg.embed_dim // 2
+        kt, vtok = self.f32(f"{tag}.tk{kv}", (groups * nt, di)), self.f32(f"{tag}.tv{kv}", (groups * nt, di))
+        L.gemm(tk16, p[ca + ".k_proj.w"], bias=w[ca + ".k_proj.bias"], out32=kt)
+        L.gemm(tv16, p[ca + ".v_proj.w"], bias=w[ca + ".v_proj.bias"], out32=vtok)
+        if fused:       # q_proj + attention + out_proj + residual + norm
+            L.twoway_i2t(img32, p[ca + ".q_proj.planes"], self.pe_table(ca + ".q_proj", pe32), kt, vtok, p[ca + ".out_proj.planes"],
+                         w[ca + ".out_proj.bias"], w[norm + ".weight"], w[norm + ".bias"], 1e-5, groups, hw, nt, self.cfg.dec_heads)
+            return
+        qi = self.f32(tag + ".iq", (groups * hw, di))
+        self.igemm(imgpe16, ca + ".q_proj.w", bias=w[ca + ".q_proj.bias"], out32=qi)
+        oi16 = self._attn_core(qi, kt, vtok, groups, hw, nt, di, tag + ".i2t", image_side=True)
+        self.igemm(oi16, ca + ".out_proj.w", bias=w[ca + ".out_proj.bias"], res=img32, out32=img32)
+        pe = dict(out16_pe=imgpe16, pe=pe32, pe_mod=hw) if refresh_pe else {}
+        L.layernorm(img32, w[norm + ".weight"], w[norm + ".bias"], 1e-5, out32=img32, out16=img16, dt=self.idti, **pe)
 
     # la_stream_mlp against the lin1 -> lin2 (+ residual) -> LayerNorm chain on the same buffers (tools/bench_oneway.py, part (a);
     # profiles/r12_oneway.md has the table).  A 128-row tile takes 223 us whatever the row count up to 32 768 rows (one workgroup per CU);
@@ -1202,7 +1205,6 @@ class LamEngine:
         leaves up to date.  norm3 is never applied.  Returns (tokens32, tokens16) for class_mlp: the class embeddings themselves."""
         w, p, cfg = self.w32, self.p, self.cfg
         d = cfg.embed_dim
-        di = d // 2
         r, ri = groups * nt, groups * hw
         fused = self.oneway_fused(nt)
         mlp_fused = self.oneway_mlp_fused(nt, ri)
@@ -1212,20 +1214,10 @@ class LamEngine:
             img16 = self.ibuf(tag + ".x16", ri, d)
         for l in range(2):
             lp = f"{pre}.layers.{l}"
-            ca = lp + ".cross_attn_image_to_token"
-            kt = self.f32(f"{tag}.tk{l}", (r, di))           # the tokens never change: k / v of both layers depend on the class embeddings alone
-            vtok = self.f32(f"{tag}.tv{l}", (r, di))
-            L.gemm(t16, p[ca + ".k_proj.w"], bias=w[ca + ".k_proj.bias"], out32=kt)
-            L.gemm(t16, p[ca + ".v_proj.w"], bias=w[ca + ".v_proj.bias"], out32=vtok)
-            if fused:       # q_proj + attention + out_proj + residual + norm1: one read and one write of the stream
-                L.twoway_i2t(img32, p[ca + ".q_proj.planes"], self.pe_table(ca + ".q_proj", pe32), kt, vtok, p[ca + ".out_proj.planes"],
-                             w[ca + ".out_proj.bias"], w[lp + ".norm1.weight"], w[lp + ".norm1.bias"], 1e-5, groups, hw, nt, cfg.dec_heads)
-            else:
-                qi = self.f32(tag + ".iq", (ri, di))
-                self.igemm(imgpe16, ca + ".q_proj.w", bias=w[ca + ".q_proj.bias"], out32=qi)
-                oi16 = self._attn_core(qi, kt, vtok, groups, hw, nt, di, tag + ".i2t", image_side=True)
-                self.igemm(oi16, ca + ".out_proj.w", bias=w[ca + ".out_proj.bias"], res=img32, out32=img32)
-                L.layernorm(img32, w[lp + ".norm1.weight"], w[lp + ".norm1.bias"], 1e-5, out32=img32, out16=img16, dt=self.idti)
+            # the tokens never change: k / v of both layers, in buffers of their own, depend on the class embeddings alone.  norm1 leaves only
+            # x up to date: the MLP reads it, and norm2 below refreshes x + pe
+            self._image_from_tokens(lp + ".cross_attn_image_to_token", lp + ".norm1", False, fused, t16, t16, str(l), img32, img16, imgpe16,
+                                    pe32, groups, nt, hw, tag)
             if mlp_fused:   # lin1 + ReLU + lin2 + residual + norm2: the 2048-wide hidden layer never leaves the chip
                 L.stream_mlp(img32, p[lp + ".mlp.lin1.planes"], w[lp + ".mlp.lin1.bias"], p[lp + ".mlp.lin2.planes"], w[lp + ".mlp.lin2.bias"],
                              w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5)
@@ -1241,11 +1233,8 @@ class LamEngine:
                 hbuf = self.dbuf(tag + ".mlp", (ri, cfg.dec_mlp))
                 self.igemm(img16, lp + ".mlp.lin1.w", bias=w[lp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_RELU)
             self.igemm(hbuf, lp + ".mlp.lin2.w", bias=w[lp + ".mlp.lin2.bias"], res=img32, out32=img32)
-            if fused:
-                L.layernorm(img32, w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5, out32=img32, dt=self.idti)
-            else:
-                L.layernorm(img32, w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5, out32=img32, out16=img16, out16_pe=imgpe16, pe=pe32,
-                            pe_mod=hw, dt=self.idti)
+            chain = {} if fused else dict(out16=img16, out16_pe=imgpe16, pe=pe32, pe_mod=hw)      # x and x + pe for the next layer's chain
+            L.layernorm(img32, w[lp + ".norm2.weight"], w[lp + ".norm2.bias"], 1e-5, out32=img32, dt=self.idti, **chain)
         return tok32, t16
 
     # ------------------------------------------------------------------------------------------------
@@ -1321,23 +1310,9 @@ class LamEngine:
             sp = sp2
         if cfg.prompt_encoder == "TokenPool":
             return self._token_pool(support32, sp, class_enc, b, m, c, ns, g, masks, flag_examples)
-        # dense stream
-        pe32 = self.dense_pe(g)
-        src32 = self.f32("pe.src32", (pcount * hw, d))
-        fused = self.fused_ok(ns)           # fused two-way kernels read the fp32 stream itself: no GEMM-operand copies
-        src16 = None if fused else self.ibuf("pe.src16", pcount * hw, d)
-        srcpe16 = None if fused else self.ibuf("pe.srcpe16", pcount * hw, d)
-        if masks is not None:
-            mk, mf = masks
-            mk = self.h2d(mk, torch.float32).reshape(pcount, mk.shape[-2], mk.shape[-1]).contiguous()
-            if mk.shape[-1] != mk.shape[-2]:
-                raise ValueError("prompt masks must be square")
-            mf = self.h2d(mf.reshape(pcount), torch.int32).contiguous()
-            L.mask_embed(mk, mf, pcount, c, mk.shape[-1], g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16,
-                         srcpe16, self.idti)
-        else:
-            L.mask_embed(None, None, pcount, c, 0, g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16, srcpe16,
-                         self.idti)
+        # dense stream: one slab per (support, class) pair, ns tokens each
+        pe32, src32, src16, srcpe16, mk, mf, hm = self._prompt_stream(pcount, ns, pcount, g, masks)
+        L.mask_embed(mk, mf, pcount, c, hm, g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16, srcpe16, self.idti)
         self.two_way(pe_ + ".transformer", sp, pcount, ns, src32, src16, srcpe16, hw, pe32, "pe.tw", want_tokens=False)
         k = cfg.pool_side
         fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
@@ -1346,7 +1321,7 @@ class LamEngine:
             n = emb.shape[1]
             # prompt_encoder.py:299-300: a query of class c is valid when any support of the episode shows the class
             flags = (fe != 0).any(dim=1, keepdim=True).to(torch.uint8).expand(b, n, c).contiguous()
-            return {"flag_examples": flags, "class_examples_embeddings": emb, "class_examples_src": src32.view(pcount, hw, d)}
+            return self._prompt_result(flags, None, emb, src32.view(pcount, hw, d))
         if k > 1:
             # embeddings_per_example > 1 (prompt_encoder.py:726-731): k x k region means per (support, class) instead of the slab mean; every
             # bin is an example of its own from here on - M k k of them, flagged like the support they come from
@@ -1359,8 +1334,34 @@ class LamEngine:
             emb = self.f32("pe.emb", (pcount, d))
             L.colmean(src32, pcount, hw, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
         emb, cls = self._merge_and_class_mean(emb, fe, b, m, c)
-        return {"flag_examples": flag_examples, "class_embeddings": cls,
-                "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(pcount, hw, d)}
+        return self._prompt_result(flag_examples, cls, emb.view(b, m, c, d).clone(), src32.view(pcount, hw, d))
+
+    def _prompt_stream(self, slabs: int, nt: int, pcount: int, g: int, masks):
+        """The prompt encoder's dense stream, ``slabs`` slabs of g g rows that meet ``nt`` tokens each, and what la_mask_embed[_pooled]
+        fills it from (prompt_encoder.py:631-644, 880-896) -> (pe32, src32, src16, srcpe16, masks (pcount, side, side) fp32, flags int32,
+        side).  Without mask prompts: None, None, 0."""
+        mk, mf, hm = None, None, 0
+        if masks is not None:
+            mk, mf = masks
+            if mk.shape[-1] != mk.shape[-2]:
+                raise ValueError("prompt masks must be square")
+            hm = mk.shape[-1]
+            mk = self.h2d(mk, torch.float32).reshape(pcount, hm, hm).contiguous()
+            mf = self.h2d(mf.reshape(pcount), torch.int32).contiguous()
+        return self.dense_pe(g), *self._stream_bufs("pe.src", slabs * g * g, self.fused_ok(nt)), mk, mf, hm
+
+    def _stream_bufs(self, name: str, rows: int, fused: bool):
+        """The image-side stream [rows, D] of a transformer call -> (fp32 stream, x, x + pe): the two GEMM-operand copies exist only for
+        the unfused chain, the fused kernels read the fp32 stream itself."""
+        d = self.cfg.embed_dim
+        return (self.f32(name + "32", (rows, d)), None if fused else self.ibuf(name + "16", rows, d),
+                None if fused else self.ibuf(name + "pe16", rows, d))
+
+    @staticmethod
+    def _prompt_result(flag_examples: Tensor, cls: Optional[Tensor], emb: Tensor, src: Tensor) -> Dict[str, Tensor]:
+        """The prompt encoder's result dictionary (prompt_encoder.py:310-313, 746-751); embedding_extraction has no class mean: cls None."""
+        res = {"flag_examples": flag_examples, "class_embeddings": cls, "class_examples_embeddings": emb, "class_examples_src": src}
+        return {k: v for k, v in res.items() if v is not None}
 
     def _merge_and_class_mean(self, emb: Tensor, fe: Tensor, b: int, m: int, c: int):
         """prompt_class_information_merge (the three optional merge attentions) and the flag-masked mean over the M examples
@@ -1386,20 +1387,8 @@ class LamEngine:
         example's embedding is the mean of its class's Ns output tokens, and class_examples_src is the image side, (B*M, hw, D)."""
         cfg, p, pe_ = self.cfg, self.p, "prompt_encoder"
         d, hw, s, nt, pcount = cfg.embed_dim, g * g, b * m, c * ns, b * m * c
-        pe32 = self.dense_pe(g)
-        src32 = self.f32("pe.src32", (s * hw, d))
-        fused = self.fused_ok(nt)           # above 32 tokens a support the unfused chain runs, on the GEMM-operand copies
-        src16 = None if fused else self.ibuf("pe.src16", s * hw, d)
-        srcpe16 = None if fused else self.ibuf("pe.srcpe16", s * hw, d)
-        mk = mf = None
-        hm = 0
-        if masks is not None:
-            mk, mf = masks
-            if mk.shape[-1] != mk.shape[-2]:
-                raise ValueError("prompt masks must be square")
-            hm = mk.shape[-1]
-            mk = self.h2d(mk, torch.float32).reshape(pcount, hm, hm).contiguous()
-            mf = self.h2d(mf.reshape(pcount), torch.int32).contiguous()
+        # one slab per support, c ns tokens each: above 32 tokens a support the unfused chain runs, on the GEMM-operand copies
+        pe32, src32, src16, srcpe16, mk, mf, hm = self._prompt_stream(s, nt, pcount, g, masks)
         L.mask_embed_pooled(mk, mf, s, c, hm, g, d, p[pe_ + ".mask_w"], support32, class_enc, pe32, src32, src16, srcpe16, self.idti)
         t32, _ = self.two_way(pe_ + ".transformer", sp, s, nt, src32, src16, srcpe16, hw, pe32, "pe.tw", want_tokens=True)
         if ns == 1:
@@ -1409,8 +1398,7 @@ class LamEngine:
             L.colmean(t32, pcount, ns, d, emb, self.f32("pe.colmean.part", (pcount, L.COLMEAN_SPLIT, d)))
         fe = self.h2d(flag_examples.reshape(b, m, c), torch.uint8).contiguous()
         emb, cls = self._merge_and_class_mean(emb, fe, b, m, c)
-        return {"flag_examples": flag_examples, "class_embeddings": cls,
-                "class_examples_embeddings": emb.view(b, m, c, d).clone(), "class_examples_src": src32.view(s, hw, d)}
+        return self._prompt_result(flag_examples, cls, emb.view(b, m, c, d).clone(), src32.view(s, hw, d))
 
     def extract_embeddings(self, src32: Tensor, b: int, m: int, c: int, hw: int) -> Tensor:
         """embedding_extraction = "cross_attention" (EmbeddingTransformer.forward, prompt_encoder.py:289-313): n learned queries per (b, c)
@@ -1445,12 +1433,8 @@ class LamEngine:
             if self.ddt != torch.float32:
                 o16 = self.dbuf("pe.xa.o16", (rows, di))
                 L.add_cast(o, out16=o16, dt=self.ddti)
-            L.gemm(o16, p[ca + ".out_proj.w"], bias=w[ca + ".out_proj.bias"], res=t32, out32=tnew)
-            self.dln(tnew, lp + ".norm1", 1e-5, out32=t32, out16=t16)
-            hbuf = self.dbuf("pe.xa.mlp", (rows, cfg.dec_mlp))
-            L.gemm(t16, p[lp + ".mlp.lin1.w"], bias=w[lp + ".mlp.lin1.bias"], out16=hbuf, act=L.ACT_RELU)
-            L.gemm(hbuf, p[lp + ".mlp.lin2.w"], bias=w[lp + ".mlp.lin2.bias"], res=t32, out32=tnew)
-            self.dln(tnew, lp + ".norm2", 1e-5, out32=t32, out16=t16)
+            self._token_sublayer(o16, ca + ".out_proj", lp + ".norm1", t32, tnew, t32, t16)
+            self._token_mlp(t16, lp + ".mlp", L.ACT_RELU, "pe.xa.mlp", lp + ".norm2", t32, tnew, t32, t16)
         # "(b c) n d -> b n c d"; always a copy: the arena buffer is overwritten by the next forward (with n = 1 the permutation is a view)
         return t32.view(b, c, n, d).permute(0, 2, 1, 3).clone(memory_format=torch.contiguous_format)
 
@@ -1468,51 +1452,62 @@ class LamEngine:
         """query32 [B*hw, D] NHWC fp32, class_emb (B,C,D) fp32 -> low-res logits (B, C, 4g, 4g) fp32.  segment_example_logits
         (mask_decoder.py:279-287,309-313): the tokens are the N C per-example embeddings ``examples`` (B,N,C,D) in (n, c) order and every
         pixel keeps the maximum over the examples that ``flag_examples`` (B,N,C) marks valid."""
-        cfg, w, p = self.cfg, self.w32, self.p
-        md = "mask_decoder"
-        d = cfg.embed_dim
-        hw = g * g
-        nex = 0
+        cfg, d, hw = self.cfg, self.cfg.embed_dim, g * g
+        ex = None
         if cfg.segment_example_logits:
             if examples is None or flag_examples is None:
                 raise ValueError("segment_example_logits needs the per-example embeddings and their flags (class_examples_embeddings, "
                                  "flag_examples of the prompt encoder's result)")
             nex, ncls = examples.shape[1], examples.shape[2]
-            fex = self.h2d(flag_examples, torch.uint8).reshape(b, nex, ncls).contiguous()
+            ex = (nex, ncls, self.h2d(flag_examples, torch.uint8).reshape(b, nex, ncls).contiguous())
             class_emb = examples.reshape(b, nex * ncls, d)
         c = class_emb.shape[1]
         pe32 = self.dense_pe(g)
-        img32 = self.f32("md.img32", (b * hw, d))
         fused = self.oneway_fused(c) if cfg.one_way else self.fused_ok(c)
-        img16 = imgpe16 = None
-        if fused:
-            L.add_cast(query32, out32=img32, dt=L.LA_F32)
-        else:
-            img16 = self.ibuf("md.img16", b * hw, d)
-            imgpe16 = self.ibuf("md.imgpe16", b * hw, d)
-            L.add_cast(query32, out32=img32, out16=img16, dt=self.idti)
-            L.add_cast(query32, pe32, hw, out16=imgpe16, dt=self.idti)
+        img32, img16, imgpe16 = self._decoder_stream(query32, pe32, b * hw, hw, fused)
         tok = self.h2d(class_emb, torch.float32).reshape(b * c, d).contiguous()
         if cfg.one_way:
-            t32, t16 = self.one_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.ow")
+            t32, t16 = self.one_way("mask_decoder.transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.ow")
         else:
-            t32, t16 = self.two_way(md + ".transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.tw", want_tokens=True)
-        levels = cfg.classification_levels == 2
-        if levels:
+            t32, t16 = self.two_way("mask_decoder.transformer", tok, b, c, img32, img16, imgpe16, hw, pe32, "md.tw", want_tokens=True)
+        cls1 = None
+        if cfg.classification_levels == 2:
             # coarse level (mask_decoder.py:345-346): the transformer's fp32 tokens before class_mlp against the fp32 D-channel stream
             # before the upscaler, at the grid resolution
             cls1 = self.f32("md.cls1", (b, c, g, g))
             L.classify_wide(t32, img32, b, hw, c, d, cls1)
-        # class_mlp (3 x Linear, ReLU between) -> prototypes
-        h1 = self.dbuf("md.cm1", (b * c, d))
+        protos = self._class_mlp(t16, b * c)
+        feat32, feat16 = self._upscale(img32, img16, b, g, fused)
+        if cfg.spatial_convs:
+            feat32 = self._spatial_convs(feat32, feat16, b, g)
+        return self._classify(feat32, protos, cls1, ex, b, c, g)
+
+    def _decoder_stream(self, query32: Tensor, pe32: Tensor, rows: int, hw: int, fused: bool):
+        """The mask decoder's image side (``_stream_bufs``), filled from the query embeddings; the transformer updates it in place."""
+        img32, img16, imgpe16 = self._stream_bufs("md.img", rows, fused)
+        if fused:
+            L.add_cast(query32, out32=img32, dt=L.LA_F32)
+        else:
+            L.add_cast(query32, out32=img32, out16=img16, dt=self.idti)
+            L.add_cast(query32, pe32, hw, out16=imgpe16, dt=self.idti)
+        return img32, img16, imgpe16
+
+    def _class_mlp(self, t16: Tensor, rows: int) -> Tensor:
+        """class_mlp (mask_decoder.py:290): 3 x Linear, ReLU between -> the prototypes [rows, class_width] fp32."""
+        w, p, md, d = self.w32, self.p, "mask_decoder", self.cfg.embed_dim
+        h1 = self.dbuf("md.cm1", (rows, d))
         L.gemm(t16, p[md + ".class_mlp.0.w"], bias=w[md + ".class_mlp.layers.0.bias"], out16=h1, act=L.ACT_RELU)
-        h2 = self.dbuf("md.cm2", (b * c, d))
+        h2 = self.dbuf("md.cm2", (rows, d))
         L.gemm(h1, p[md + ".class_mlp.1.w"], bias=w[md + ".class_mlp.layers.1.bias"], out16=h2, act=L.ACT_RELU)
-        cf = cfg.class_width
-        protos = self.f32("md.protos", (b * c, cf))
+        protos = self.f32("md.protos", (rows, self.cfg.class_width))
         L.gemm(h2, p[md + ".class_mlp.2.w"], bias=w[md + ".class_mlp.layers.2.bias"], out32=protos)
-        # output_upscaling: ConvT(k2,s2) -> LN2d -> GELU -> ConvT(k2,s2), both as pixel-shuffle GEMMs
-        c1 = cfg.up_mid
+        return protos
+
+    def _upscale(self, img32: Tensor, img16, b: int, g: int, fused: bool):
+        """output_upscaling (mask_decoder.py:291): ConvT(k2,s2) -> LN2d -> GELU -> ConvT(k2,s2), both as pixel-shuffle GEMMs ->
+        (feat32, feat16): the [B*16hw, class_width] map in fp32 and as the first spatial convolution's operand."""
+        cfg, w, p, md = self.cfg, self.w32, self.p, "mask_decoder"
+        hw, c1, cf = g * g, cfg.up_mid, cfg.class_width
         up1 = self.f32("md.up1", (b * 4 * hw, c1))
         if fused:       # the stream itself is the (fp32) operand: there is no separate copy to read
             L.gemm(img32, p[md + ".up0.w"], bias=w[md + ".output_upscaling.0.bias"], out32=up1, map=L.MAP_CONVT2X2, p=(g, g, c1, 0, 0))
@@ -1525,30 +1520,44 @@ class LamEngine:
         feat16 = self.f32("md.feat16f", (b * npix, cf)) if self.isplit else self.dbuf("md.feat16", (b * npix, cf))
         self.igemm(up1h, md + ".up3.w", bias=w[md + ".output_upscaling.3.bias"], out32=feat32, out16=None if self.isplit else feat16,
                    map=L.MAP_CONVT2X2, p=(2 * g, 2 * g, cf, 0, 0))
-        if cfg.spatial_convs:
-            implicit = self.ddt == torch.float32 and cf % 32 == 0
-            col = None if implicit else self.dbuf("md.col", (b * npix, 9 * cf))
-            if self.isplit:       # the up3 GEMM cannot emit a second fp32 copy in split mode: the first conv reads its fp32 output
-                L.add_cast(feat32, out32=feat16, dt=L.LA_F32)
-            for i in range(cfg.spatial_convs):
-                if implicit:      # fp32 implicit GEMM: no im2col buffer (feat16 IS fp32 here)
-                    nxt = self.f32("md.feat32b" if i % 2 == 0 else "md.feat32", (b * npix, cf))
-                    # (32 -> 32 channels, the D = 256 decoder: three fp16 products on plane pairs - fp32-class accuracy at ~3x the rate of
-                    # the exact-fp32 MFMA, which bounds la_conv3x3_f32; other widths keep that kernel)
-                    conv = L.conv3x3_split if (self.conv_split and L.conv3x3_split_ok(cf, cf)) else L.conv3x3_f32
-                    conv(feat16, b, 4 * g, 4 * g, cf, p[f"{md}.sc{i}.w"], w[f"{md}.spatial_convs.{3 * i}.bias"], cf, nxt)
-                    feat32 = nxt
-                else:
-                    L.im2col_3x3(feat16, b, 4 * g, 4 * g, cf, col)
-                    L.gemm(col, p[f"{md}.sc{i}.w"], bias=w[f"{md}.spatial_convs.{3 * i}.bias"], out32=feat32)
-                if i < cfg.spatial_convs - 1:
-                    self.dln(feat32, f"{md}.spatial_convs.{3 * i + 1}", 1e-6, gelu=True, out16=feat16)
-        if nex:
+        return feat32, feat16
+
+    def _spatial_convs(self, feat32: Tensor, feat16: Tensor, b: int, g: int) -> Tensor:
+        """spatial_convs (mask_decoder.py:294-297): cfg.spatial_convs x Conv2d(3 x 3), LN2d + GELU between -> the map the pixels are
+        classified on, fp32.  Three operand modes: la_conv3x3_split, la_conv3x3_f32 (both implicit GEMMs on an fp32 map), im2col + GEMM."""
+        cfg, w, p, md = self.cfg, self.w32, self.p, "mask_decoder"
+        cf, npix = cfg.class_width, 16 * g * g
+        implicit = self.ddt == torch.float32 and cf % 32 == 0
+        col = None if implicit else self.dbuf("md.col", (b * npix, 9 * cf))
+        if self.isplit:       # the up3 GEMM cannot emit a second fp32 copy in split mode: the first conv reads its fp32 output
+            L.add_cast(feat32, out32=feat16, dt=L.LA_F32)
+        for i in range(cfg.spatial_convs):
+            if implicit:      # fp32 implicit GEMM: no im2col buffer (feat16 IS fp32 here)
+                nxt = self.f32("md.feat32b" if i % 2 == 0 else "md.feat32", (b * npix, cf))
+                # (32 -> 32 channels, the D = 256 decoder: three fp16 products on plane pairs - fp32-class accuracy at ~3x the rate of
+                # the exact-fp32 MFMA, which bounds la_conv3x3_f32; other widths keep that kernel)
+                conv = L.conv3x3_split if (self.conv_split and L.conv3x3_split_ok(cf, cf)) else L.conv3x3_f32
+                conv(feat16, b, 4 * g, 4 * g, cf, p[f"{md}.sc{i}.w"], w[f"{md}.spatial_convs.{3 * i}.bias"], cf, nxt)
+                feat32 = nxt
+            else:
+                L.im2col_3x3(feat16, b, 4 * g, 4 * g, cf, col)
+                L.gemm(col, p[f"{md}.sc{i}.w"], bias=w[f"{md}.spatial_convs.{3 * i}.bias"], out32=feat32)
+            if i < cfg.spatial_convs - 1:
+                self.dln(feat32, f"{md}.spatial_convs.{3 * i + 1}", 1e-6, gelu=True, out16=feat16)
+        return feat32
+
+    def _classify(self, feat32: Tensor, protos: Tensor, cls1: Optional[Tensor], ex, b: int, c: int, g: int) -> Tensor:
+        """The classification head (mask_decoder.py:299-314, 353-362) -> low-res logits (B, C, 4g, 4g), a fresh tensor.  ex: (N, C, flags)
+        of segment_example_logits; cls1: the coarse logits of classification_levels = 2."""
+        cfg, w, md = self.cfg, self.w32, "mask_decoder"
+        cf, npix = cfg.class_width, 16 * g * g
+        if ex is not None:
+            nex, ncls, fex = ex
             seg = torch.empty(b, ncls, 4 * g, 4 * g, device=self.dev, dtype=torch.float32)
             L.classify_max(feat32, protos, fex, b, npix, nex, ncls, cf, seg)
             return seg
         seg = torch.empty(b, c, 4 * g, 4 * g, device=self.dev, dtype=torch.float32)
-        if levels:      # level_reducer over [fine logits, x4 enlargement of the coarse ones] (mask_decoder.py:358-362)
+        if cls1 is not None:            # level_reducer over [fine logits, x4 enlargement of the coarse ones] (mask_decoder.py:358-362)
             cls0 = self.f32("md.cls0", (b, c, 4 * g, 4 * g))
             L.classify(feat32, protos, b, npix, c, cf, cls0)
             L.level_reduce(cls0, cls1, w[md + ".level_reducer.weight"], w[md + ".level_reducer.bias"], b, c, g, g, seg)

@@ -27,7 +27,29 @@ epilogues with la_gemm_fused_act_ok answering yes and no; then exact-fp32 weight
 (tn16 off), GELU passes (fused_gelu off), the gradient slots laid out and handed over back to front (negative stride between query,
 key and value: three la_gemm_tn16 products per block on purpose, none with gsize), 32-wide heads padded to 64, bf16.  SAM: sam_tiny (one padded-window block, one global block), the same with rel-pos tables of another
 length (longer for block 0, shorter for block 1), 768 wide at 448 px (two window blocks of one geometry + one global) with the GELU
-epilogues on and off, 80-wide heads padded to 128."""
+epilogues on and off, 80-wide heads padded to 128.
+
+The DECODER half of LamEngine has the third table, EXPECTED_DECODER, in the same form: ``prompt_encoder``, ``mask_decoder`` and
+``postprocess_dev`` (with ``example_valid`` where segment_example_logits is set) on zero tensors, called with the arguments ``Lam._run``
+passes; the last line records every tensor of the prompt encoder's result and of the output, so which results are arena views and which
+clones is pinned too.  ``Tensor.pin_memory`` is an identity while a row runs, ``selected_rows`` is always passed, and the host predicates
+that ask the shared library answer what the row states: la_stream_mlp_ok yes, la_extract_pool_plan (64, 2, 4096), la_conv3x3_split_ok yes
+except in the last row.  The table was recorded from the decoder drivers as they stood BEFORE their repeated launch groups became shared
+steps (one hand-written copy per method), with this tool unchanged; the shared steps reproduce it.
+
+What the rows reach.  One episode, 2 supports, 3 classes, a 4 x 4 grid (16 stream rows a slab), 2 points + 1 box + a 16 x 16 mask per
+(support, class) pair; the encoder (sam_tiny) is built and never run.  64 wide - the unfused chain on an fp32 decoder, im2col spatial
+convolutions: all three prompt kinds, points only (adds the padding token), boxes only, masks only (the single "no sparse" token), the
+three merge attentions with a class-encoder bank.  256 wide, all prompts: the fused two-way kernels + la_conv3x3_split (default), "f16x2"
+(plane-pair image-side operands: in the upscaler behind the fused kernels, and throughout the chain with fuse_twoway off),
+decoder_dtype=None (16-bit operands, im2col convolutions), fuse_twoway off, conv_split off
+(la_conv3x3_f32), 33 classes (the mask decoder above fused_ok's 32 tokens, the prompt encoder still fused), no spatial convolutions.
+OneWayTransformer: fused with the chain MLP (the default threshold at this size), fused with la_stream_mlp (ONEWAY_MLP_MIN_ROWS = 0),
+fuse_oneway off, "f16x2" (the chain through the fp32 hidden layer) with fuse_oneway on and off.  TokenPool: with masks, without, masks
+only (ns = 1: no token mean), 9 classes x 4 tokens = 36 with a bank (the unfused chain on pooled slabs).  Heads and extraction:
+cross_attention with 2 queries and segment_example_logits (fp32, and 16-bit operands: the extra cast of the pooled output),
+embeddings_per_example = 4 (2 x 2 region means, la_classify_max), two levels, conv classification, downsample rate 1 (256-channel map:
+la_conv3x3_split_ok answers no, la_classify_wide)."""
 import os
 import sys
 
@@ -97,10 +119,71 @@ EXPECTED_TRAIN = {
                                '18b3eb1b5aa65ea525d915cf0406ba7afd5e641732c9076079b0355d1297e91a'),
 }
 
+# name: (number of lines, sha256 of the full trace, sha256 of the shape trace) - python tools/encoder_trace.py --decoder-table
+EXPECTED_DECODER = {
+    'dec 64 all prompts': (127, 'ae4e528f5dab571f4801a1773a1358d0716526d03ec703ff42a4a07f4de88b42',
+                               '2d8446eda767b2b48e39165311e04def36eaa283d55fb96966c36de66140ff11'),
+    'dec 64 points': (127, '89fe4d5aedc7a9fda1229281894298ce0c7a155202c6730213272adf53bf555f',
+                          '414cb9ba5fc728e9262ac82f97353c5442151de338799fce51b1bed5478496f0'),
+    'dec 64 boxes': (127, '62228987496626888e911a2a0dcb4e72287fbe0dbd0c3c916b5d7681c0494064',
+                         '20c719bace5faf4fde350b9e908c0c032ef46aeb23d2ab03654ccb08e41af173'),
+    'dec 64 masks': (127, '61adbcc496adf451d706fe27a7acb838acfcf2c134cf824aaa989347752549b2',
+                         '3ca3c362443bb59d0192da42aed4e0501c5a8e2356c563e7af46a950538d787e'),
+    'dec 64 merge attentions bank': (144, '8109518c8bd1d64469541ab4365413e23fe35165e28215658ce67bb9150748fa',
+                                         '6041c5489cfae342107690940d356b8527f977af474f6ab21d63fc76f5c870c9'),
+    'dec 256 fused': (122, 'ee90592bb085432a241210a97fc9cd6f588058dba8643128cfbbaf1c33386eae',
+                          '2266f7552c3660949a58ff4bf6612ff7a0fcbb1fd4a873dd33eb9fb40e6e20f6'),
+    'dec 256 f16x2': (123, '9bf49e687145700f99f5e151c18705f1be0ebe8dfa17d341653db7f9d89e4ba7',
+                          '665a295f05d664c4f39ee73585bc35e8d6222f936bd901493e8705b13838a2a6'),
+    'dec 256 f16x2 unfused': (128, '7b96dc6d18a5cae5b8f4e6e0e6e19fa208dbb418bb97812399c66513c8022a02',
+                                  '455d8c9c731f01cbce06bea3b67a25238bbb64976f2d409e8698c07081630317'),
+    'dec 256 16-bit im2col': (127, '6eead523d8d61a20a9abdc2504f8f0bda63565f41b742e6245ee441c4bf9ecfd',
+                                  'a1955dc189fe53b9ce52e04f35ebf1d83818a9214d857883468bf28777455168'),
+    'dec 256 unfused': (127, 'bc6ba4e4bd9885c5a385a5048fec0fa893cd0c27ce16e2409e40b8e59a26c02b',
+                            '4db6758efedd6cc87750ce9f1d9a65cd9713bc2d51bacdfef404332020dfe89f'),
+    'dec 256 conv_split off': (119, '2f9e76c7b324a04d2c6a8e8927447c73c757cabbb6d7e0395fc0cbb2a6b56348',
+                                   'ef3481ff7ffa7ceef5a5628eb6d68df03310a6d018d71c2d65c50582cb98f7d7'),
+    'dec 256 33 classes': (125, '3c169210fc835e53a96aed9fca84de0e05458753444b0466421fd024b4ab503d',
+                               '02a1a00a0e5366984586b5f843a52f4a4cca7cf2c07b890c512eda6abf6226cf'),
+    'dec 256 no spatial convs': (114, 'ee764d315941b3f234ee7d8d151ab820f47a3308314dd9e597955c1fc4320156',
+                                     'b77497a6ecf93fd07b0e6406f8b9371622522dc5b55a8c3d9cf46d948d8f1cc7'),
+    'dec oneway fused chain mlp': (98, '2df5e9c722e1dfb018c8df3ac26764b5b76651dac3f394fe3a8d5bea54c964f0',
+                                       '4e110a886515da875d8c5ab61c871af4ea00526acf2b81d300ee4e44ddef26ba'),
+    'dec oneway fused stream_mlp': (92, '3fc49dc2e43a3cba56a8cd1e7a85a8758d8664f768e603b5b8bb152f33edf618',
+                                        '52a54f90fb2bed7ea61b3a72466359fc7d45b73ef4526b2f90cb44d7c0f7e50f'),
+    'dec oneway unfused': (98, '33fc66631317a2eff085d0ec82ccfbe9614310734293bd867d8fcbebe6eaf606',
+                               'ef78ea88d810ee3b2863813f4859900cb41381ef1351b636d38fbc0eed4fde02'),
+    'dec oneway f16x2': (101, '97b140ff19de732a5bd63ed19b67b530a855079cb0617f034d4dd9cdd34feecd',
+                             '164b7d1c8afc2a70ea281bedda89e7b7f79f0972303663d135e45ac60a58dddb'),
+    'dec oneway f16x2 unfused': (101, '6a7278c8626d5e94111a9048dbd09c0bbd5870144129b1de91dbb767d8d883a8',
+                                     '473e3607132c57f8fa2baf80c7289a60050866b9540f0e04db45f26943f6cc09'),
+    'dec pool masks': (128, '1a4175a3d60576c2679391c94e04989391b4689d8d7e8f0e5f4a1e7553be2d99',
+                           '3b194c4db13cfa373daf969e1bf62ad8bc9bfb89321a325af8dc4bbb0dd0a6ee'),
+    'dec pool no masks': (128, 'caa2fba432e0cc4277d4c238c6974fab41f9ccaad9d34c5374d5aedfe62b3bed',
+                              '638d55b7e0c339c71ed07a2cc79adc68e25cc8e74ed6f5c6640b1fac55f0b6d7'),
+    'dec pool masks only': (127, '2c38e6be36362ff6e15ce65d37207515d443afd2151b6ab3367d4f1788432b30',
+                                'f1c61ea1af3d714358572fcbb45d42582523b7d4e684ee195a3bc7306849d809'),
+    'dec pool 36 tokens bank': (131, '1660aba993fe0b30d650cfad490321d726365378bc83f1f7bea541bfc4139ab6',
+                                    '0a9676ac32d5a218fe63c9cd9013ccabc0b9360e1b50c82f9a85c4444d068858'),
+    'dec cross_attention 2 queries': (131, 'ae1fb7273323c230eeff34abace44f9721a091f547d50006168455e7c176995b',
+                                          '815641cb0a45ae8d32fc63e6179dc19933fe2c189113b8b8116548dd622d55d4'),
+    'dec cross_attention 16-bit': (138, '68cca3e2d2116691471ff2398a24d6affa5be4871baca0c7c335778af369f0ed',
+                                       'a5ac5e432450941fcff6e8fa291ce754c5da596db454f2b05ab9f6961b035ccb'),
+    'dec 4 embeddings per example': (122, '5f6ea3f5771512c49f07f5886cb92349af6319305ae3388cb7c3e72265a0a937',
+                                         '0fdf9d7bfb11e4f95c359f9a40f39b686204788f53deffb74be7d888e843d3a9'),
+    'dec two levels': (124, '99025002481bf3680c3e1803e183f078eaf66b8a13a2c7b667805cd9507941b1',
+                           '030f0bf474122d1483f00f57761bc469a3ae75998f835fc85b256338c46b0e52'),
+    'dec conv classification': (123, '3986697b0a4c8b687983b0e059a5095767f848a77f00f813a9db074b537bd59b',
+                                    '163839c610b38101de9b527bcaea990dff92fba2e3bef0f322cedb6d3b2e832b'),
+    'dec downsample rate 1': (122, '039a04eb614e47a38017310cf76292dc164d189befb547153fa57588e6f17fde',
+                                  'ffa082d1884931c3800c3f40df13c08d5b9217400bbafd1f024eb2c516f71bb5'),
+}
+
 
 def test_the_table_covers_the_matrix():
     assert list(T.matrix()) == list(EXPECTED)
     assert list(T.train_matrix()) == list(EXPECTED_TRAIN)
+    assert list(T.decoder_matrix()) == list(EXPECTED_DECODER)
 
 
 @pytest.mark.parametrize("name", list(EXPECTED))
@@ -120,3 +203,13 @@ def test_training_graph_launch_trace_is_unchanged(name, monkeypatch):
         print(f"training launch trace of {name!r} changed: {got} != {EXPECTED_TRAIN[name]}; inspect it with\n"
               f"  python tools/encoder_trace.py --print {name!r}")
     assert got == EXPECTED_TRAIN[name]
+
+
+@pytest.mark.parametrize("name", list(EXPECTED_DECODER))
+def test_decoder_launch_trace_is_unchanged(name, monkeypatch):
+    rec = T.decoder_trace(T.decoder_matrix()[name], monkeypatch.setattr)
+    got = rec.digest() + rec.digest(shape=True)[1:]
+    if got != EXPECTED_DECODER[name]:
+        print(f"decoder launch trace of {name!r} changed: {got} != {EXPECTED_DECODER[name]}; inspect it with\n"
+              f"  python tools/encoder_trace.py --print {name!r}")
+    assert got == EXPECTED_DECODER[name]

@@ -12,9 +12,15 @@ A second matrix (``train_matrix``) does the same for the TRAINING graphs of ``tr
 gradient, with the gradient slots laid out in one flat buffer as FlatAdamW does.  Each of its rows is pinned twice: the full trace, and
 a shape trace whose storage numbers are masked (which launches, on which shapes - whatever the buffers alias).
 
+A third matrix (``decoder_matrix``) does it for the DECODER half of ``LamEngine``: ``prompt_encoder``, ``mask_decoder`` and
+``postprocess_dev`` on zero tensors, called as ``Lam._run`` calls them, pinned twice like the training rows.  The host predicates that ask
+the shared library (la_conv3x3_split_ok, la_stream_mlp_ok, la_extract_pool_plan) are stand-ins whose answers the row states; the last line
+holds every tensor of the prompt encoder's result and of the output - which are views of arena buffers, which clones.
+
   python tools/encoder_trace.py --table             name, number of calls, sha256 of the trace for the whole matrix
   python tools/encoder_trace.py --train-table       the same for the training matrix: full and shape digest per row
-  python tools/encoder_trace.py --print NAME        one trace
+  python tools/encoder_trace.py --decoder-table     the same for the decoder matrix
+  python tools/encoder_trace.py --print NAME        one trace (a row of any of the three matrices)
   python tools/encoder_trace.py --packed NAME       key, shape, dtype, sha256 of the bytes of every packed weight of NAME's engine
 """
 from __future__ import annotations
@@ -34,8 +40,9 @@ if ROOT not in sys.path:
 from labelanything_amd import _lib as L                                            # noqa: E402
 from labelanything_amd.config import EncoderSpec, LamConfig, register_encoder     # noqa: E402
 
-# host arithmetic only (or never reached by the encoder): these keep working
-PURE = ("ln_cs_chunks", "norm_cs_chunks", "conv3x3_split_ok", "extract_pool_plan", "twoway_part_size", "dt_of")
+# host arithmetic only: these keep working.  (The host predicates that ask the shared library - gemm_fused_act_ok, conv3x3_split_ok,
+# stream_mlp_ok, extract_pool_plan - are recorder stand-ins like the launchers: a row states their answers in ``returns``.)
+PURE = ("ln_cs_chunks", "norm_cs_chunks", "twoway_part_size", "dt_of")
 LAUNCHERS = {n: inspect.signature(f) for n, f in vars(L).items()
              if not n.startswith("_") and n not in PURE and inspect.isfunction(f) and f.__module__ == L.__name__}
 # the ``**epilogue`` keywords of gemm / gemm_plan are those of _gemm_epilogue, defaults included
@@ -154,7 +161,7 @@ def engine(row: dict):
     from labelanything_amd.engine import LamEngine
     from labelanything_amd.weights import init_state_dict
     _specs()
-    cfg = LamConfig(spatial_convs=3, custom_preprocess=False, **row["cfg"])
+    cfg = LamConfig(**{"spatial_convs": 3, "custom_preprocess": False, **row["cfg"]})
     eng = LamEngine(cfg, init_state_dict(cfg, 0), torch.device("cpu"), **row["ctor"])
     for k, v in row["attrs"].items():
         assert hasattr(eng, k), k
@@ -247,6 +254,89 @@ def train_trace(row: dict, setattr_=setattr) -> Recorder:
     return rec
 
 
+def decoder_matrix() -> dict:
+    """name -> configuration of one decoder row: one episode of ``m`` supports and ``c`` classes on a 4 x 4 grid (16 stream rows a slab),
+    2 points, 1 box and 16 x 16 masks a (support, class) pair - ``prompts`` says which kinds are passed.  The encoder (sam_tiny) is built
+    and never run.  See the module docstring of tests/test_encoder_trace_cpu.py for what each row reaches."""
+    def row(d=256, prompts="pbm", m=2, c=3, ctor=None, attrs=None, split_ok=True, **cfg) -> dict:
+        returns = {"conv3x3_split_ok": split_ok, "stream_mlp_ok": True, "extract_pool_plan": (64, 2, 4096)}
+        cfg = dict(encoder="sam_tiny", image_size=64, image_embed_dim=96, embed_dim=d, **cfg)
+        return dict(cfg=cfg, ctor=ctor or {}, attrs=attrs or {}, returns=returns, prompts=prompts, m=m, c=c)
+
+    def bank(d):
+        return {"name": "RandomMatrixEncoder", "bank_size": 10, "embed_dim": d}
+
+    f16x2, one_way, pool = {"decoder_dtype": "f16x2"}, {"fusion_transformer": "OneWayTransformer"}, {"prompt_encoder": "TokenPool"}
+    return {
+        "dec 64 all prompts": row(64),
+        "dec 64 points": row(64, "p"),
+        "dec 64 boxes": row(64, "b"),
+        "dec 64 masks": row(64, "m"),
+        "dec 64 merge attentions bank": row(64, class_attention=True, example_attention=True, example_class_attention=True,
+                                            class_encoder=bank(64)),
+        "dec 256 fused": row(),
+        "dec 256 f16x2": row(ctor=f16x2),
+        "dec 256 f16x2 unfused": row(ctor={"fuse_twoway": False, **f16x2}),
+        "dec 256 16-bit im2col": row(ctor={"decoder_dtype": None}),
+        "dec 256 unfused": row(ctor={"fuse_twoway": False}),
+        "dec 256 conv_split off": row(attrs={"conv_split": False}),
+        "dec 256 33 classes": row(c=33),
+        "dec 256 no spatial convs": row(spatial_convs=0),
+        "dec oneway fused chain mlp": row(**one_way),
+        "dec oneway fused stream_mlp": row(attrs={"ONEWAY_MLP_MIN_ROWS": 0}, **one_way),
+        "dec oneway unfused": row(ctor={"fuse_oneway": False}, **one_way),
+        "dec oneway f16x2": row(ctor=f16x2, **one_way),
+        "dec oneway f16x2 unfused": row(ctor={"fuse_oneway": False, **f16x2}, **one_way),
+        "dec pool masks": row(prompts="pbm", **pool),
+        "dec pool no masks": row(prompts="pb", **pool),
+        "dec pool masks only": row(prompts="m", **pool),
+        "dec pool 36 tokens bank": row(prompts="pbm", c=9, class_encoder=bank(256), **pool),
+        "dec cross_attention 2 queries": row(embedding_extraction="cross_attention", embeddings_per_example=2, segment_example_logits=True),
+        "dec cross_attention 16-bit": row(ctor={"decoder_dtype": None}, embedding_extraction="cross_attention", embeddings_per_example=2,
+                                          segment_example_logits=True),
+        "dec 4 embeddings per example": row(embeddings_per_example=4, segment_example_logits=True),
+        "dec two levels": row(classification_levels=2),
+        "dec conv classification": row(conv_classification=True),
+        "dec downsample rate 1": row(classification_layer_downsample_rate=1, split_ok=False),
+    }
+
+
+def _tensors(prefix: str, v):
+    """(name, tensor) of every tensor in a result: a dictionary, a tuple or a tensor."""
+    if isinstance(v, torch.Tensor):
+        yield prefix, v
+    elif isinstance(v, dict):
+        for k in sorted(v):
+            yield from _tensors(f"{prefix}.{k}" if prefix else k, v[k])
+    elif isinstance(v, (tuple, list)):
+        for i, x in enumerate(v):
+            yield from _tensors(f"{prefix}[{i}]", x)
+
+
+def decoder_trace(row: dict, setattr_=setattr) -> Recorder:
+    """Prompt encoder, mask decoder and post-processing of one decoder row under a fresh recorder, called as ``Lam._run`` calls them.
+    ``Tensor.pin_memory`` is an identity meanwhile (``LamEngine.h2d`` pins, which needs a GPU) and ``selected_rows`` is always passed
+    (``sample_rows`` draws a permutation).  The last line holds every tensor of the prompt encoder's result and of the output: which
+    are arena views, which clones."""
+    rec = Recorder(row["returns"])
+    rec.patch(setattr_)
+    setattr_(torch.Tensor, "pin_memory", lambda t, *a, **k: t)
+    eng = engine(row)
+    cfg = eng.cfg
+    b, m, c, g, d, s = 1, row["m"], row["c"], 4, cfg.embed_dim, cfg.image_size
+    z = torch.zeros
+    points = (z(b, m, c, 2, 2), z(b, m, c, 2, dtype=torch.int32)) if "p" in row["prompts"] else None
+    boxes = (z(b, m, c, 1, 4), z(b, m, c, 1, dtype=torch.int32)) if "b" in row["prompts"] else None
+    masks = (z(b, m, c, 4 * g, 4 * g), z(b, m, c, dtype=torch.int32)) if "m" in row["prompts"] else None
+    flag_examples = z(b, m, c, dtype=torch.uint8)
+    res = eng.prompt_encoder(z(b * m * g * g, d), b, m, g, points, boxes, masks, flag_examples, torch.arange(c))
+    seg = eng.mask_decoder(z(b * g * g, d), b, g, res.get("class_embeddings"), res["class_examples_embeddings"], res["flag_examples"])
+    fg = eng.example_valid(res["flag_examples"]) if cfg.segment_example_logits else None
+    out = eng.postprocess_dev(seg, torch.tensor([[s, s, s, s]] * b, dtype=torch.int32), s, s, fg, True)
+    rec.note("return", list(_tensors("", {"prompt_encoder": res, "low_res_logits": seg, "post": out})))
+    return rec
+
+
 def _sha_entries(key: str, v):
     if isinstance(v, torch.Tensor):
         raw = v.detach().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()
@@ -262,6 +352,7 @@ def main() -> None:
     g.add_argument("--print", dest="show", metavar="NAME")
     g.add_argument("--table", action="store_true")
     g.add_argument("--train-table", action="store_true")
+    g.add_argument("--decoder-table", action="store_true")
     g.add_argument("--packed", metavar="NAME")
     a = ap.parse_args()
     rows = matrix()
@@ -269,13 +360,15 @@ def main() -> None:
         for name, row in rows.items():
             n, h = trace(row).digest()
             print(f"{name!r}: ({n}, {h!r}),")
-    elif a.train_table:
-        for name, row in train_matrix().items():
-            rec = train_trace(row)
+    elif a.train_table or a.decoder_table:
+        for name, row in (train_matrix() if a.train_table else decoder_matrix()).items():
+            rec = train_trace(row) if a.train_table else decoder_trace(row)
             n, h = rec.digest()
             print(f"{name!r}: ({n}, {h!r},\n{'':{len(name) + 9}}{rec.digest(shape=True)[1]!r}),")
     elif a.show in train_matrix():
         print("\n".join(train_trace(train_matrix()[a.show]).lines))
+    elif a.show in decoder_matrix():
+        print("\n".join(decoder_trace(decoder_matrix()[a.show]).lines))
     elif a.show:
         print("\n".join(trace(rows[a.show]).lines))
     else:
