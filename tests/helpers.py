@@ -2,12 +2,24 @@
 from __future__ import annotations
 
 import json
+import math
 import os
 
+import pytest
 import torch
 from safetensors.torch import load_file
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NAN = float("nan")
+GUARD = 64                   # guard elements on either side of an output view (keeps the view 16-byte aligned for every dtype)
+
+
+@pytest.fixture(scope="module")
+def L():
+    """The bound C ABI, loaded: a test module imports this fixture by name."""
+    from labelanything_amd import _lib
+    _lib.lib()
+    return _lib
 
 
 def load_golden(name: str):
@@ -69,3 +81,100 @@ def reference_logits(case: dict, gold: dict, batch: dict) -> torch.Tensor:
     from oracle import lam_oracle as O
     from tests.cases import geometry_for
     return O.postprocess(geometry_for(case["cfg"]), gold["low_res_logits"].float(), batch["dims"], batch.get("flag_gts"))
+
+
+def make_gt(batch, n_classes, seed=0):
+    """A ground-truth map per episode at the padded output size: random blocky labels, some ignored pixels."""
+    g = torch.Generator().manual_seed(seed)
+    dims = batch["dims"]
+    b = dims.shape[0]
+    hmax, wmax = int(dims[..., 0].max()), int(dims[..., 1].max())
+    gt = torch.randint(0, n_classes, (b, (hmax + 15) // 16, (wmax + 15) // 16), generator=g)
+    gt = gt.repeat_interleave(16, 1).repeat_interleave(16, 2)[:, :hmax, :wmax].contiguous()
+    for i in range(b):
+        h, w = int(dims[i, 0, 0]), int(dims[i, 0, 1])
+        gt[i, h:, :] = -100
+        gt[i, :, w:] = -100
+    gt[torch.rand(gt.shape, generator=g) < 0.02] = -100
+    return gt
+
+
+def dataset_batch(case, seed=0, prompts=None):
+    """make_episode's model input widened to the dataset's layout: the query gets prompts too (a copy of the first support's),
+    ground truths for all M+1 images."""
+    from labelanything_amd.episodes import make_episode
+    ep = dict(case["episode"])
+    if prompts is not None:
+        ep["prompts"] = prompts
+    batch = make_episode(**ep)
+    out = dict(batch)
+    for k in ("prompt_points", "flag_points", "prompt_bboxes", "flag_bboxes", "prompt_masks", "flag_masks", "flag_examples"):
+        if k in batch:
+            out[k] = torch.cat([batch[k][:, :1], batch[k]], dim=1)
+    if "prompt_points" not in out:
+        b, m1, c = out["flag_examples"].shape
+        out["prompt_points"] = torch.zeros(b, m1, c, 1, 2)
+        out["flag_points"] = torch.zeros(b, m1, c, 1)
+    dims = out["dims"]
+    b, m1 = dims.shape[:2]
+    c = out["flag_examples"].shape[2]
+    hmax, wmax = int(dims[..., 0].max()), int(dims[..., 1].max())
+    g = torch.Generator().manual_seed(seed)
+    gts = torch.randint(0, c, (b, m1, (hmax + 15) // 16, (wmax + 15) // 16), generator=g)
+    gts = gts.repeat_interleave(16, 2).repeat_interleave(16, 3)[:, :, :hmax, :wmax].contiguous()
+    for i in range(b):
+        for m in range(m1):
+            gts[i, m, int(dims[i, m, 0]):] = -100
+            gts[i, m, :, int(dims[i, m, 1]):] = -100
+    return out, gts
+
+
+def rnd(*shape, seed=0, scale=1.0):
+    """Seeded normal data, on the device."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * scale).cuda()
+
+
+def rint(*shape, seed=0, lo=-8, hi=9):
+    """Small integers as fp32, on the device: sums of a few thousand of them are exact in fp32."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(lo, hi, shape, generator=g).float().cuda()
+
+
+def guarded(*shape, dtype=torch.float32, fill=NAN):
+    """(buffer, view): an output view between GUARD sentinel elements on either side, itself filled with the sentinel."""
+    n = math.prod(shape)
+    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
+    return buf, buf[GUARD:GUARD + n].view(*shape)
+
+
+def guarded_zero(*shape):
+    """An ACCUMULATED destination: zeros between NaN guards."""
+    buf, view = guarded(*shape)
+    view.zero_()
+    return buf, view
+
+
+def check_guards(buf, view, fill=NAN, may_hold_fill=False):
+    torch.cuda.synchronize()
+    n = view.numel()
+    edge = torch.cat([buf[:GUARD], buf[GUARD + n:]])
+    if fill != fill:
+        assert bool(torch.isnan(edge).all()), "guard elements were overwritten"
+        assert not bool(torch.isnan(view).any()), "part of the output was not written"
+    else:
+        assert bool((edge == fill).all()), "guard elements were overwritten"
+        assert may_hold_fill or not bool((view == fill).any()), "part of the output was not written"
+
+
+def untouched(buf, fill=NAN):
+    torch.cuda.synchronize()
+    return bool(torch.isnan(buf).all()) if fill != fill else bool((buf == fill).all())
+
+
+def within_1ulp(got, exact64):
+    """got is the correctly rounded fp32 value of exact64 or one of its two fp32 neighbours."""
+    e = exact64.float()
+    g = got.detach().cpu()
+    up, dn = torch.nextafter(e, torch.full_like(e, math.inf)), torch.nextafter(e, torch.full_like(e, -math.inf))
+    return bool(((g == e) | (g == up) | (g == dn)).all())

@@ -14,19 +14,12 @@ import pytest
 import torch
 
 from tests import softmax_profiles as SP
+from tests.helpers import L, NAN
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 FWD = SP.forward_cases()
 BWD = SP.backward_cases()
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def fam(cases, name):

@@ -17,17 +17,9 @@ import pytest
 import torch
 
 from tests import softmax_profiles as SP
+from tests.helpers import L, NAN
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def check_rows(tag, got, ref_rows, heads, tol):

@@ -15,17 +15,14 @@ Two kinds of input.
     second).  The gradients of the kernel composition nest two sums and take the total: 18 cf for dprotos (9 cf for dk1, 9 cf over it),
     cf + 9 BC for dW2 (k1 inside), 9 cf + BC for dW1 (dk1 inside).  Printed as [derived] with the worst measured ratio to the bound.
 """
-import math
-
 import pytest
 import torch
 
 from tests import convcls_ref as R
+from tests.helpers import L, check_guards, guarded, guarded_zero, untouched
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-GUARD = 64
 U = 2.0 ** -24
 EXACT_LIMIT = 2.0 ** 24
 
@@ -41,13 +38,6 @@ BWD_SHAPES = FWD_SHAPES[:4] + [(2, 3, 256, 16, 16)]
 PROTO_SHAPES = [(1, 32), (6, 32), (3, 64), (6, 256)]
 
 
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
 def gen(seed):
     return torch.Generator().manual_seed(seed)
 
@@ -58,31 +48,6 @@ def rnd(*shape, seed=0, scale=1.0):
 
 def rint(*shape, seed=0, lo=-2, hi=3):
     return torch.randint(lo, hi, shape, generator=gen(seed)).float()
-
-
-def guarded(*shape):
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), NAN, dtype=torch.float32, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def guarded_zero(*shape):
-    buf, view = guarded(*shape)
-    view.zero_()
-    return buf, view
-
-
-def check_guards(buf, view):
-    torch.cuda.synchronize()
-    n = view.numel()
-    edge = torch.cat([buf[:GUARD], buf[GUARD + n:]])
-    assert bool(torch.isnan(edge).all()), "guard elements were overwritten"
-    assert not bool(torch.isnan(view).any()), "part of the output was not written"
-
-
-def untouched(buf):
-    torch.cuda.synchronize()
-    return bool(torch.isnan(buf).all())
 
 
 def worst_ratio(got, ref, bound):

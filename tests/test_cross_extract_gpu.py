@@ -15,11 +15,10 @@ import math
 
 import pytest
 import torch
+from tests.helpers import GUARD, L, check_guards, guarded, untouched, within_1ulp
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-GUARD = 64
 U = 2.0 ** -24
 EPS_E = 2.0 ** -23
 HEADS = 8
@@ -31,40 +30,8 @@ SHAPES = [((1, 3, 2), 30, 4, 256), ((2, 1, 3), 5, 1, 64), ((2, 1, 3), 16, 5, 256
 IDS = [f"B{b}M{m}C{c}-g{g}-n{n}-D{d}" for (b, m, c), g, n, d in SHAPES]
 
 
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
 def rnd(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def guarded(*shape, fill=NAN):
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=torch.float32, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def check_guards(buf, view):
-    torch.cuda.synchronize()
-    n = view.numel()
-    assert bool(torch.isnan(torch.cat([buf[:GUARD], buf[GUARD + n:]])).all()), "guard elements were overwritten"
-    assert not bool(torch.isnan(view).any()), "part of the output was not written"
-
-
-def untouched(buf):
-    torch.cuda.synchronize()
-    return bool(torch.isnan(buf).all())
-
-
-def within_1ulp(got, exact64):
-    e = exact64.float()
-    g = got.detach().cpu()
-    up, dn = torch.nextafter(e, torch.full_like(e, math.inf)), torch.nextafter(e, torch.full_like(e, -math.inf))
-    return bool(((g == e) | (g == up) | (g == dn)).all())
 
 
 def pair_rows(x, b, m, c):

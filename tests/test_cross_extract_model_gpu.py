@@ -4,15 +4,13 @@ the REFERENCE's fixtures tests/golden/cross_extract_* (tools/make_golden_cross_e
 Bounds, as in tests/test_multi_embedding_model_gpu.py: 2e-5 max-norm for decoder-only forward quantities (the bound of
 tools/make_golden.py for decoder-only cases); argmax exact outside the project's 2e-3 margin band.
 """
-import dataclasses
-
 import pytest
 import torch
 
 from labelanything_amd.episodes import make_episode
-from labelanything_amd.models import Lam
+from tests import model_checks as MC
 from tests.cases_cross_extract import XE_CASES
-from tests.helpers import argmax_disagreement, load_golden, rel_err
+from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +19,7 @@ ARGMAX_MARGIN = 2e-3
 
 
 def model_for(name):
-    case = XE_CASES[name]
-    gold, meta = load_golden(f"cross_extract_{name}")
-    lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()
-    lam.selected_rows = gold.get("selected_rows")
-    return lam, case, gold, meta
+    return MC.load_model(XE_CASES, name, "cross_extract_")
 
 
 @pytest.mark.parametrize("name", list(XE_CASES))
@@ -42,49 +36,25 @@ def test_forward_matches_the_reference_fixture(name):
             "low_res_logits": rel_err(seg, gold["low_res_logits"]), "logits": rel_err(out["logits"], gold["logits"])}
     print(f"[{name}] {meta['folded_queries']} folded queries per pair: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()) + f" (bound {TOL:.0e})")
     assert all(v <= TOL for v in errs.values()), errs
-    assert torch.equal(out["logits"].argmax(dim=1).cpu(), out["argmax"].cpu())
-    n_diff, n_real = argmax_disagreement(out["logits"], gold["argmax"].long(), gold["logits"], margin_rel=ARGMAX_MARGIN)
-    print(f"[{name}] argmax differs on {n_diff} pixels, {n_real} outside the {ARGMAX_MARGIN:.0e} margin band")
-    assert n_real == 0
+    MC.check_argmax(name, out, gold, ARGMAX_MARGIN)
     assert set(out) == {"logits", "class_examples_embeddings", "argmax"}     # the reference's keys (+ the fused argmax)
     assert torch.equal(out["class_examples_embeddings"], pe["class_examples_embeddings"])
 
 
 @pytest.mark.parametrize("name", list(XE_CASES))
 def test_graph_replay_is_bit_identical_and_tracks_new_inputs(name):
-    lam, case, gold, _ = model_for(name)
-    b1 = make_episode(**case["episode"])
-    b2 = make_episode(**{**case["episode"], "seed": 778})
-    e1, e2 = lam.forward_argmax(b1), lam.forward_argmax(b2)
-    lam.use_graphs = True
-    g1 = lam.forward_argmax(b1)       # capture
-    g2 = lam.forward_argmax(b2)       # replay with new inputs
-    g1b = lam.forward_argmax(b1)
-    torch.cuda.synchronize()
-    for k in ("logits", "argmax", "class_examples_embeddings"):
-        assert torch.equal(e1[k], g1[k]) and torch.equal(e2[k], g2[k]) and torch.equal(e1[k], g1b[k]), k
-    assert len(lam._graphs) == 1
-    assert not torch.equal(e1["logits"], e2["logits"])
+    lam, case, _, _ = model_for(name)
+    MC.check_graph_replay(lam, case, keys=("logits", "argmax", "class_examples_embeddings"))
 
 
 @pytest.mark.parametrize("name", ["x4", "x1"])
 def test_predict_from_cached_example_embeddings_matches_forward(name):
     """generate_class_embeddings keeps the extracted embeddings and their (B, n, C) flags; predict decodes against them.  (The cached path
     takes post-neck embeddings, lam.py:193-213: the two cases without a neck.)"""
-    from labelanything_amd.cache import set_class_embeddings
-    lam, case, gold, meta = model_for(name)
-    batch = make_episode(**case["episode"])
-    full = lam(batch)["logits"]
-    examples = {k: (v[:, 1:] if k in ("embeddings", "dims") else v) for k, v in batch.items()}
-    ce = lam.generate_class_embeddings(examples)
+    lam, case, gold, _ = model_for(name)
+    ce, _ = MC.check_cached_predict(lam, case, exact=True)
     assert tuple(ce["class_examples_embeddings"].shape) == tuple(gold["class_examples_embeddings"].shape)
     assert tuple(ce["flag_examples"].shape) == tuple(gold["flag_examples"].shape) and "class_embeddings" not in ce
-    q = {"embeddings": batch["embeddings"][:, :1], "dims": batch["dims"][:, 0]}
-    pred = lam.predict(q, ce)
-    torch.cuda.synchronize()
-    assert torch.equal(pred, full)
-    set_class_embeddings(lam, {k: v[0] for k, v in examples.items()})
-    assert torch.equal(lam.predict(q), full)
 
 
 def test_padded_supports_take_part_like_the_reference_s():

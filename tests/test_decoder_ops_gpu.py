@@ -19,55 +19,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import lam_oracle as O
-from tests.helpers import rel_err
+from tests.helpers import L, NAN, check_guards, guarded, rel_err, rint, rnd, untouched, within_1ulp
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 NINF = float("-inf")
-GUARD = 64                   # guard elements on either side of an output view (keeps the view 16-byte aligned for every dtype)
 U = 2.0 ** -24               # unit roundoff of fp32
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).cuda()
-
-
-def rint(*shape, seed=0, lo=-8, hi=9):
-    """Small integers as fp32: sums of a few thousand of them are exact in fp32."""
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(lo, hi, shape, generator=g).float().cuda()
-
-
-def guarded(*shape, dtype=torch.float32, fill=NAN):
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def check_guards(buf, view, fill=NAN):
-    torch.cuda.synchronize()
-    n = view.numel()
-    edge = torch.cat([buf[:GUARD], buf[GUARD + n:]])
-    if fill != fill:
-        assert bool(torch.isnan(edge).all()), "guard elements were overwritten"
-        assert not bool(torch.isnan(view).any()), "part of the output was not written"
-    else:
-        assert bool((edge == fill).all()), "guard elements were overwritten"
-        assert not bool((view == fill).any()), "part of the output was not written"
-
-
-def untouched(buf):
-    torch.cuda.synchronize()
-    return bool(torch.isnan(buf).all())
 
 
 def check_measured(name, got, ref64, ref32):
@@ -78,14 +35,6 @@ def check_measured(name, got, ref64, ref32):
     bound = 4.0 * e32 + 1e-6
     print(f"[measured] {name}: e32 {e32:.3e}  kernel {err:.3e}  bound {bound:.3e}")
     assert err <= bound, (name, err, bound)
-
-
-def within_1ulp(got, exact64):
-    """got is the correctly rounded fp32 value of exact64 or one of its two fp32 neighbours."""
-    e = exact64.float()
-    g = got.detach().cpu()
-    up, dn = torch.nextafter(e, torch.full_like(e, math.inf)), torch.nextafter(e, torch.full_like(e, -math.inf))
-    return bool(((g == e) | (g == up) | (g == dn)).all())
 
 
 def split_planes_ok(planes, v32, d):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from labelanything_amd import _lib as L
-from tests.test_multi_embedding_gpu import NAN, check_guards, guarded
+from tests.helpers import NAN, check_guards, guarded, make_gt
 
 pytestmark = pytest.mark.gpu
 
@@ -170,7 +170,6 @@ def test_training_step_with_trainable_encoder_matches_oracle_autograd():
     from oracle import lam_oracle as O
     from oracle import loss_oracle as LO
     from tests.cases import CASES, geometry_for
-    from tests.test_train_gpu import make_gt
     case = CASES["hf_tiny_1w1s_masks"]
     cfg = case["cfg"]
     batch = make_episode(**case["episode"])
@@ -220,7 +219,6 @@ def test_backbone_lr_is_its_own_parameter_group():
     from labelanything_amd.models import Lam
     from labelanything_amd.train import LamTrainer
     from tests.cases import CASES
-    from tests.test_train_gpu import make_gt
     case = CASES["hf_tiny_1w1s_masks"]
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=3)
@@ -416,7 +414,6 @@ def test_trainer_leaves_the_models_inference_numerics_alone():
     from labelanything_amd.models import Lam
     from labelanything_amd.train import LamTrainer
     from tests.cases import CASES
-    from tests.test_train_gpu import make_gt
     case = CASES["hf_tiny_1w1s_masks"]
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=3)
@@ -449,7 +446,6 @@ def test_bf16_training_through_the_encoder_as_baseline_cfg3_words_it():
     from labelanything_amd.weights import init_state_dict
     from oracle import lam_oracle as O
     from tests.cases import CASES, geometry_for
-    from tests.test_train_gpu import make_gt
     cfg = _hf_cfg(224)
     g = torch.Generator().manual_seed(224)
     images = torch.randn(3, 3, 224, 224, generator=g)
@@ -513,7 +509,6 @@ def test_checkpoint_restore_between_steps_reaches_the_trainers_encoder():
     from labelanything_amd.models import Lam
     from labelanything_amd.train import LamTrainer
     from tests.cases import CASES
-    from tests.test_train_gpu import make_gt
     case = CASES["hf_tiny_1w1s_masks"]
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=3)
@@ -558,7 +553,6 @@ def test_decoder_graph_behind_the_trainable_encoder_is_exact_at_its_own_embeddin
     from labelanything_amd.weights import init_state_dict
     from oracle import lam_oracle as O, loss_oracle as LO
     from tests.cases import TRAIN_ENC_CASE as case, geometry_for
-    from tests.test_train_gpu import make_gt
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=3)
     lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()

@@ -15,8 +15,8 @@ import math
 import pytest
 import torch
 
-from labelanything_amd import _lib
 from tests import gemm_ref as R
+from tests.helpers import L
 from tests.test_gemm_plan_cpu import A, BF16, BIAS, BIG, F16, F32, NSO, O16, O32, RES, RVEC, TABLE, VT, W, call
 
 TORCH_DT = {F16: torch.float16, BF16: torch.bfloat16, F32: torch.float32}
@@ -254,12 +254,6 @@ def run_case(L, name, c, want=None):
             assert r["ratio"] <= 1.0
     finally:
         L.gemm_variant(prev)
-
-
-@pytest.fixture(scope="module")
-def L():
-    _lib.lib()
-    return _lib
 
 
 @pytest.mark.gpu

@@ -13,17 +13,14 @@ Two kinds of input.
     tap), D for the wide classify, C for dimg, Npix for dtok, 9 for dcls0, 9 + 64 for dcls1 (a 9-tap sum inside a sum over the 8 x 8 fine
     pixels that read a coarse pixel), the number of pixels of the whole batch (+ 4) for dw and dbias.  Printed as [derived].
 """
-import math
-
 import pytest
 import torch
 
 from tests import levels_ref as R
+from tests.helpers import L, NAN, check_guards, guarded, guarded_zero, untouched
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-GUARD = 64
 U = 2.0 ** -24
 EXACT_LIMIT = 2.0 ** 24 / 64
 
@@ -32,13 +29,6 @@ SHAPES = [(2, 3, 5, 7),        # odd, not square, smaller than a tile, several p
           (1, 1, 30, 30),      # the Pascal grid: 4 x 4 tiles, the last ones partial
           (1, 1, 1, 1)]        # every source index clamps
 WIDTHS = [64, 256, 512]
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def gen(seed):
@@ -51,32 +41,6 @@ def rnd(*shape, seed=0, scale=1.0):
 
 def rint(*shape, seed=0, lo=-4, hi=5):
     return torch.randint(lo, hi, shape, generator=gen(seed)).float()
-
-
-def guarded(*shape):
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), NAN, dtype=torch.float32, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def check_guards(buf, view):
-    torch.cuda.synchronize()
-    n = view.numel()
-    edge = torch.cat([buf[:GUARD], buf[GUARD + n:]])
-    assert bool(torch.isnan(edge).all()), "guard elements were overwritten"
-    assert not bool(torch.isnan(view).any()), "part of the output was not written"
-
-
-def untouched(buf):
-    torch.cuda.synchronize()
-    return bool(torch.isnan(buf).all())
-
-
-def guarded_zero(*shape):
-    """An ACCUMULATED destination: zeros between NaN guards."""
-    buf, view = guarded(*shape)
-    view.zero_()
-    return buf, view
 
 
 # =========================================================================================================================

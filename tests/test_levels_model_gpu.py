@@ -12,16 +12,15 @@ e_kink or of the relative comparisons; the test bounds it by what summing the ``
 (n + 2) 2^-24 sum|d loss / d low_res_logits| with the sum from the reference's fp64 run - a partial sum that misses a tile is larger.
 """
 import dataclasses
-import json
-import os
 
 import pytest
 import torch
 
 from labelanything_amd.episodes import make_episode
 from labelanything_amd.models import Lam
+from tests import model_checks as MC
 from tests.cases_levels import LV_CASES, LV_TRAIN
-from tests.helpers import GOLDEN, argmax_disagreement, load_golden, rel_err
+from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +30,7 @@ NEW_KEYS = ["mask_decoder.level_reducer.weight", "mask_decoder.level_reducer.bia
 
 
 def model_for(name):
-    case = LV_CASES[name]
-    gold, meta = load_golden(f"levels_{name}")
-    lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()
-    lam.selected_rows = gold.get("selected_rows")
-    return lam, case, gold, meta
+    return MC.load_model(LV_CASES, name, "levels_")
 
 
 def one_level_twin(case, gold):
@@ -52,34 +47,10 @@ def one_level_twin(case, gold):
 def test_one_level_model_is_untouched_by_the_new_code(monkeypatch):
     """With classification_levels = 1 no new kernel is launched, and the logits are the same bits before and after the new kernels (forward
     and backward) have run in the process."""
-    from labelanything_amd import _lib as L
-    from labelanything_amd.train import LamTrainer
-    from tests.test_train_gpu import make_gt
     lam, case, gold, _ = model_for("l2")
-    batch = make_episode(**case["episode"])
-    plain = one_level_twin(case, gold)
-
-    def forbidden(*a, **kw):
-        raise AssertionError("a kernel of the two-level head was launched by a classification_levels=1 model")
-
-    with monkeypatch.context() as mp:
-        for fn in ("classify_wide", "classify_wide_bwd", "level_reduce", "level_reduce_bwd"):
-            mp.setattr(L, fn, forbidden)
-        before = plain.forward_argmax(batch)
-        before = {k: before[k].clone() for k in ("logits", "argmax")}
-        tr = LamTrainer(one_level_twin(case, gold))
-        tr.zero_grad()
-        tr.forward_backward(batch, make_gt(batch, batch["flag_examples"].shape[2], seed=3))
-        torch.cuda.synchronize()
-        assert not any("level_reducer" in k for k in tr.names)
-    two = lam.forward_argmax(batch)
-    tr2 = LamTrainer(lam)
-    tr2.zero_grad()
-    tr2.forward_backward(batch, make_gt(batch, batch["flag_examples"].shape[2], seed=3))
-    after = one_level_twin(case, gold).forward_argmax(batch)
-    torch.cuda.synchronize()
-    assert torch.equal(after["logits"], before["logits"]) and torch.equal(after["argmax"], before["argmax"])
-    assert rel_err(two["logits"], before["logits"]) > 1e-2                       # the head is not a no-op
+    MC.check_default_model_untouched(monkeypatch, lam, case, lambda: one_level_twin(case, gold),
+                                     ("classify_wide", "classify_wide_bwd", "level_reduce", "level_reduce_bwd"), "level_reducer",
+                                     "a kernel of the two-level head was launched by a classification_levels=1 model")
 
 
 @pytest.mark.parametrize("name", list(LV_CASES))
@@ -97,44 +68,20 @@ def test_forward_matches_the_reference_fixture(name):
             "logits": rel_err(out["logits"], gold["logits"])}
     print(f"[{name}] " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()) + f" (bound {TOL:.0e}); scales {meta['scale']}")
     assert all(v <= TOL for v in errs.values()), errs
-    assert torch.equal(out["logits"].argmax(dim=1).cpu(), out["argmax"].cpu())
-    n_diff, n_real = argmax_disagreement(out["logits"], gold["argmax"].long(), gold["logits"], margin_rel=ARGMAX_MARGIN)
-    print(f"[{name}] argmax differs on {n_diff} pixels, {n_real} outside the {ARGMAX_MARGIN:.0e} margin band")
-    assert n_real == 0
+    MC.check_argmax(name, out, gold, ARGMAX_MARGIN)
 
 
 @pytest.mark.parametrize("name", list(LV_CASES))
 def test_graph_replay_is_bit_identical_and_tracks_new_inputs(name):
-    lam, case, gold, _ = model_for(name)
-    b1 = make_episode(**case["episode"])
-    b2 = make_episode(**{**case["episode"], "seed": 778})
-    e1, e2 = lam.forward_argmax(b1), lam.forward_argmax(b2)
-    lam.use_graphs = True
-    g1 = lam.forward_argmax(b1)       # capture
-    g2 = lam.forward_argmax(b2)       # replay with new inputs
-    g1b = lam.forward_argmax(b1)
-    torch.cuda.synchronize()
-    for k in ("logits", "argmax"):
-        assert torch.equal(e1[k], g1[k]) and torch.equal(e2[k], g2[k]) and torch.equal(e1[k], g1b[k]), k
-    assert len(lam._graphs) == 1
-    assert not torch.equal(e1["logits"], e2["logits"])
+    lam, case, _, _ = model_for(name)
+    MC.check_graph_replay(lam, case)
 
 
 @pytest.mark.parametrize("name", list(LV_CASES))
 def test_predict_from_cached_embeddings_matches_forward(name):
-    from labelanything_amd.cache import set_class_embeddings
-    lam, case, gold, meta = model_for(name)
-    batch = make_episode(**case["episode"])
-    full = lam(batch)["logits"]
-    examples = {k: (v[:, 1:] if k in ("embeddings", "dims") else v) for k, v in batch.items()}
-    ce = lam.generate_class_embeddings(examples)
-    q = {"embeddings": batch["embeddings"][:, :1], "dims": batch["dims"][:, 0]}
-    pred = lam.predict(q, ce)
-    torch.cuda.synchronize()
-    assert rel_err(pred, full) <= 1e-6
+    lam, case, gold, _ = model_for(name)
+    _, full = MC.check_cached_predict(lam, case)
     assert rel_err(full, gold["logits"]) <= TOL
-    set_class_embeddings(lam, {k: v[0] for k, v in examples.items()})
-    assert rel_err(lam.predict(q), full) <= 1e-6
 
 
 def test_other_level_reducer_weights_change_the_logits():
@@ -158,17 +105,10 @@ def test_other_level_reducer_weights_change_the_logits():
 
 
 def test_one_training_step_matches_the_reference():
-    from labelanything_amd.train import LamTrainer
-    from tests.test_train_gpu import make_gt
     name = LV_TRAIN["case"]
     lam, case, gold_fwd, _ = model_for(name)
-    from safetensors.torch import load_file
-    gold = load_file(os.path.join(GOLDEN, f"levels_{name}_train.safetensors"))
-    with open(os.path.join(GOLDEN, f"levels_{name}_train.json")) as fh:
-        meta = json.load(fh)
-    batch = make_episode(**case["episode"])
-    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=meta["seed_gt"])
-    tr = LamTrainer(lam)
+    gold, meta = MC.load_train_fixture(f"levels_{name}")
+    tr, _, grads = MC.run_training_step(lam, case, gold_fwd, gold, meta, TOL, label=name)
     # live parameters of the decoder span: in the trainer's names, in front of the dead tail, inside the decoder bucket
     dead = [i for i, k in enumerate(tr.names) if k.startswith(("prompt_encoder.transformer.final_attn_token_to_image.",
                                                                 "prompt_encoder.transformer.norm_final_attn."))]
@@ -178,19 +118,11 @@ def test_one_training_step_matches_the_reference():
     for i in where:
         off = sum(p.numel() for p in tr.opt.grad_views[:i])
         assert lo <= off and off + tr.opt.grad_views[i].numel() <= hi
-    tr.zero_grad()
-    res = tr.forward_backward(batch, gt)
-    torch.cuda.synchronize()
-    assert rel_err(res["logits"], gold_fwd["logits"]) <= TOL
-    loss = float(res["loss"])
-    print(f"[train {name}] loss {loss:.8f} reference {meta['loss']:.8f}")
-    assert abs(loss - meta["loss"]) <= TOL * max(1.0, abs(meta["loss"]))
     e_kink = float(meta["e_kink"])
     tol = max(3e-4, 4 * e_kink)
     print(f"[train {name}] gradient bound max(3e-4, 4 * e_kink = {4 * e_kink:.3e}) = {tol:.3e}")
-    grads = dict(zip(tr.names, tr.opt.grad_views))
     keys = meta["keys"]
-    assert set(keys) <= set(tr.names) and NEW_KEYS[0] in keys and meta["inert"] == [NEW_KEYS[1]] and NEW_KEYS[1] not in keys
+    assert NEW_KEYS[0] in keys and meta["inert"] == [NEW_KEYS[1]] and NEW_KEYS[1] not in keys
     assert float(grads[NEW_KEYS[0]].abs().min()) > 0
     for k in NEW_KEYS:
         assert tr._touched[tr.names.index(k)], k
@@ -199,21 +131,8 @@ def test_one_training_step_matches_the_reference():
     print(f"[train {name}] inert level_reducer.bias gradient {dbias:.3e} (reference fp32 {meta['inert_reference_fp32']:.3e}); "
           f"[derived] bound {noise:.3e}")
     assert dbias <= noise
-    for k in meta["dead"]:                                           # never reached by the reference's forward either
-        assert float(grads[k].abs().max()) == 0.0, k
-    gn = torch.stack([grads[k].norm() for k in keys]).cpu()
-    floor = 1e-2 * float(gold["grad_norm"].max())
-    rel_n = (gn - gold["grad_norm"]).abs() / gold["grad_norm"].clamp_min(floor)
-    print(f"[train {name}] worst gradient-norm difference {float(rel_n.max()):.3e} at {keys[int(rel_n.argmax())]}")
-    assert float(rel_n.max()) <= tol
-    full = {k[5:]: v for k, v in gold.items() if k.startswith("grad.")}
-    assert set(NEW_KEYS) <= set(full)
-    full.pop(NEW_KEYS[1])                                            # inert: bounded above
-    gmax = max(float(v.abs().max()) for v in full.values())
-    worst = {k: float((grads[k].cpu() - v).abs().max()) / max(float(v.abs().max()), 1e-2 * gmax) for k, v in full.items()}
-    print(f"[train {name}] worst entry-wise gradient difference {max(worst.values()):.3e} at {max(worst, key=worst.get)}")
-    bad = {k: v for k, v in worst.items() if v > tol}
-    assert not bad, bad
+    assert {"grad." + k for k in NEW_KEYS} <= set(gold)
+    MC.compare_gradients(tr.names, grads, gold, meta, tol, label=name)       # (leaves the inert bias, bounded above, out of both comparisons)
     # the optimizer moves them
     before = {k: lam.state_dict()[k].clone() for k in NEW_KEYS}
     tr.apply_update()

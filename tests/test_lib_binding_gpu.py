@@ -2,18 +2,12 @@
 call still computes, and the stream a call is enqueued on is the current one."""
 import pytest
 import torch
+from tests.helpers import L
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24               # unit roundoff of fp32
 P, HW, D = 2, 4, 8
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 @pytest.fixture(scope="module")

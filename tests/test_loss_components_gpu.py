@@ -231,7 +231,7 @@ def test_three_steps_match_the_reference_fixture():
 def test_accumulated_substitution_returns_the_standalone_loss_per_step():
     from labelanything_amd.substitution import Substitutor
     from tests.cases import CASES
-    from tests.test_substitution_gpu import dataset_batch
+    from tests.helpers import dataset_batch
     case = CASES["novit_d256_2w3s"]
     batch, gts = dataset_batch(case, seed=4)
     comps = {k: dict(v) for k, v in COMPOSITE.items()}
@@ -257,7 +257,7 @@ def test_accumulated_substitution_returns_the_standalone_loss_per_step():
 def test_trainable_encoder_step_with_the_composite_loss():
     from labelanything_amd.episodes import make_episode
     from tests.cases import TRAIN_ENC_CASE as case
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=3)
     crit = LabelAnythingLoss({k: dict(v) for k, v in COMPOSITE.items()}, class_weighting=True)

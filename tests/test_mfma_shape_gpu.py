@@ -13,19 +13,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import rel_err
+from tests.helpers import L, rel_err
 
 pytestmark = pytest.mark.gpu
 
 KS = (64, 128, 768, 3072)
 DTYPES = (torch.float16, torch.bfloat16)
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def _operands(k, dt, seed):

@@ -17,20 +17,12 @@ import pytest
 import torch
 
 from tests import multi_embedding_ref as R
+from tests.helpers import GUARD, L, NAN, check_guards, guarded, untouched, within_1ulp
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 NINF = float("-inf")
-GUARD = 64
 U = 2.0 ** -24
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def rnd(*shape, seed=0):
@@ -39,36 +31,6 @@ def rnd(*shape, seed=0):
 
 def rint(*shape, seed=0, lo=-8, hi=9):
     return torch.randint(lo, hi, shape, generator=torch.Generator().manual_seed(seed)).float()
-
-
-def guarded(*shape, dtype=torch.float32, fill=NAN):
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def check_guards(buf, view, fill=NAN, may_hold_fill=False):
-    torch.cuda.synchronize()
-    n = view.numel()
-    edge = torch.cat([buf[:GUARD], buf[GUARD + n:]])
-    if fill != fill:
-        assert bool(torch.isnan(edge).all()), "guard elements were overwritten"
-        assert not bool(torch.isnan(view).any()), "part of the output was not written"
-    else:
-        assert bool((edge == fill).all()), "guard elements were overwritten"
-        assert may_hold_fill or not bool((view == fill).any()), "part of the output was not written"
-
-
-def untouched(buf, fill=NAN):
-    torch.cuda.synchronize()
-    return bool(torch.isnan(buf).all()) if fill != fill else bool((buf == fill).all())
-
-
-def within_1ulp(got, exact64):
-    e = exact64.float()
-    g = got.detach().cpu()
-    up, dn = torch.nextafter(e, torch.full_like(e, math.inf)), torch.nextafter(e, torch.full_like(e, -math.inf))
-    return bool(((g == e) | (g == up) | (g == dn)).all())
 
 
 # =========================================================================================================================

@@ -8,16 +8,15 @@ decoder-only bound of test_gradients_match_oracle_autograd and e_kink what the g
 fp64 gradients (the maximum over examples is a kink: where two examples tie to rounding, fp32 and fp64 pick different winners).
 """
 import dataclasses
-import json
-import os
 
 import pytest
 import torch
 
 from labelanything_amd.episodes import make_episode
 from labelanything_amd.models import Lam
+from tests import model_checks as MC
 from tests.cases_multi_embedding import ME_CASES, ME_TRAIN
-from tests.helpers import GOLDEN, argmax_disagreement, load_golden, rel_err
+from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +25,7 @@ ARGMAX_MARGIN = 2e-3
 
 
 def model_for(name):
-    case = ME_CASES[name]
-    gold, meta = load_golden(f"multi_embedding_{name}")
-    lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()
-    lam.selected_rows = gold.get("selected_rows")
-    return lam, case, gold, meta
+    return MC.load_model(ME_CASES, name, "multi_embedding_")
 
 
 @pytest.mark.parametrize("name", list(ME_CASES))
@@ -46,48 +41,23 @@ def test_forward_matches_the_reference_fixture(name):
             "low_res_logits": rel_err(seg, gold["low_res_logits"]), "logits": rel_err(out["logits"], gold["logits"])}
     print(f"[{name}] {meta['decoder_tokens']} decoder tokens: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()) + f" (bound {TOL:.0e})")
     assert all(v <= TOL for v in errs.values()), errs
-    assert torch.equal(out["logits"].argmax(dim=1).cpu(), out["argmax"].cpu())
-    n_diff, n_real = argmax_disagreement(out["logits"], gold["argmax"].long(), gold["logits"], margin_rel=ARGMAX_MARGIN)
-    print(f"[{name}] argmax differs on {n_diff} pixels, {n_real} outside the {ARGMAX_MARGIN:.0e} margin band")
-    assert n_real == 0
+    MC.check_argmax(name, out, gold, ARGMAX_MARGIN)
     assert torch.equal(out["class_examples_embeddings"], pe["class_examples_embeddings"])
 
 
 @pytest.mark.parametrize("name", ["e4", "e9_attn"])
 def test_graph_replay_is_bit_identical_and_tracks_new_inputs(name):
-    lam, case, gold, _ = model_for(name)
-    b1 = make_episode(**case["episode"])
-    b2 = make_episode(**{**case["episode"], "seed": 778})
-    e1, e2 = lam.forward_argmax(b1), lam.forward_argmax(b2)
-    lam.use_graphs = True
-    g1 = lam.forward_argmax(b1)       # capture
-    g2 = lam.forward_argmax(b2)       # replay with new inputs
-    g1b = lam.forward_argmax(b1)
-    torch.cuda.synchronize()
-    for k in ("logits", "argmax", "class_examples_embeddings"):
-        assert torch.equal(e1[k], g1[k]) and torch.equal(e2[k], g2[k]) and torch.equal(e1[k], g1b[k]), k
-    assert len(lam._graphs) == 1
-    assert not torch.equal(e1["logits"], e2["logits"])
+    lam, case, _, _ = model_for(name)
+    MC.check_graph_replay(lam, case, keys=("logits", "argmax", "class_examples_embeddings"))
 
 
 @pytest.mark.parametrize("name", ["e4", "e1"])
 def test_predict_from_cached_example_embeddings_matches_forward(name):
     """generate_class_embeddings keeps the per-example embeddings and the (repeated) flags; predict decodes against them."""
-    from labelanything_amd.cache import set_class_embeddings
-    lam, case, gold, meta = model_for(name)
-    batch = make_episode(**case["episode"])
-    full = lam(batch)["logits"]
-    examples = {k: (v[:, 1:] if k in ("embeddings", "dims") else v) for k, v in batch.items()}
-    ce = lam.generate_class_embeddings(examples)
+    lam, case, gold, _ = model_for(name)
+    ce, _ = MC.check_cached_predict(lam, case)
     assert tuple(ce["class_examples_embeddings"].shape) == tuple(gold["class_examples_embeddings"].shape)
     assert tuple(ce["flag_examples"].shape) == tuple(gold["flag_examples"].shape)
-    q = {"embeddings": batch["embeddings"][:, :1], "dims": batch["dims"][:, 0]}
-    pred = lam.predict(q, ce)
-    torch.cuda.synchronize()
-    assert rel_err(pred, full) <= 1e-6
-    # the test-time prototype cache (experiment/utils.py:210-249) serves the same
-    set_class_embeddings(lam, {k: v[0] for k, v in examples.items()})
-    assert rel_err(lam.predict(q), full) <= 1e-6
 
 
 def test_state_dict_of_the_one_prototype_model_loads():
@@ -125,46 +95,15 @@ def test_class_without_a_valid_example_is_minus_infinity():
 
 
 def test_one_training_step_matches_the_reference():
-    from labelanything_amd.train import LamTrainer
-    from tests.test_train_gpu import make_gt
     name = ME_TRAIN["case"]
     lam, case, gold_fwd, _ = model_for(name)
-    from safetensors.torch import load_file
-    gold = load_file(os.path.join(GOLDEN, f"multi_embedding_{name}_train.safetensors"))
-    with open(os.path.join(GOLDEN, f"multi_embedding_{name}_train.json")) as fh:
-        meta = json.load(fh)
-    batch = make_episode(**case["episode"])
-    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=meta["seed_gt"])
-    tr = LamTrainer(lam)
-    tr.zero_grad()
-    res = tr.forward_backward(batch, gt)
-    torch.cuda.synchronize()
-    assert rel_err(res["logits"], gold_fwd["logits"]) <= TOL
-    loss = float(res["loss"])
-    print(f"[train {name}] loss {loss:.8f} reference {meta['loss']:.8f}")
-    assert abs(loss - meta["loss"]) <= TOL * max(1.0, abs(meta["loss"]))
+    gold, meta = MC.load_train_fixture(f"multi_embedding_{name}")
+    tr, _, grads = MC.run_training_step(lam, case, gold_fwd, gold, meta, TOL, label=name)
     e_kink = float(meta["e_kink"])
     tol = max(3e-4, 4 * e_kink)
     print(f"[train {name}] gradient bound max(3e-4, 4 * e_kink = {4 * e_kink:.3e}) = {tol:.3e}")
-    grads = dict(zip(tr.names, tr.opt.grad_views))
-    keys = meta["keys"]
-    assert set(keys) <= set(tr.names)
-    for k in meta["dead"]:                                           # never reached by the reference's forward either
-        assert float(grads[k].abs().max()) == 0.0, k
-    # every tensor by its norm: | ||g|| - ||ref|| | <= ||g - ref||, relative to the tensor's own norm floored at 1e-2 of the largest
-    gn = torch.stack([grads[k].norm() for k in keys]).cpu()
-    floor = 1e-2 * float(gold["grad_norm"].max())
-    rel_n = (gn - gold["grad_norm"]).abs() / gold["grad_norm"].clamp_min(floor)
-    print(f"[train {name}] worst gradient-norm difference {float(rel_n.max()):.3e} at {keys[int(rel_n.argmax())]}")
-    assert float(rel_n.max()) <= tol
-    # the stored tensors entry by entry, relative to the tensor's scale floored at 1e-2 of the largest stored gradient
-    full = {k[5:]: v for k, v in gold.items() if k.startswith("grad.")}
-    assert "mask_decoder.class_mlp.layers.2.weight" in full
-    gmax = max(float(v.abs().max()) for v in full.values())
-    worst = {k: float((grads[k].cpu() - v).abs().max()) / max(float(v.abs().max()), 1e-2 * gmax) for k, v in full.items()}
-    print(f"[train {name}] worst entry-wise gradient difference {max(worst.values()):.3e} at {max(worst, key=worst.get)}")
-    bad = {k: v for k, v in worst.items() if v > tol}
-    assert not bad, bad
+    assert "grad.mask_decoder.class_mlp.layers.2.weight" in gold
+    MC.compare_gradients(tr.names, grads, gold, meta, tol, label=name)
 
 
 def test_trainer_refuses_prompt_contrastive_with_region_embeddings():

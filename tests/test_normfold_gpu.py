@@ -10,21 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import rel_err
+from tests.helpers import L, rel_err, rnd
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).cuda()
 
 
 def _producer(L, m, n, k, rpg, res_mod=0, a_kmod=0, with_rvec=True, with_res=True):

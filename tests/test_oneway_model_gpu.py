@@ -8,17 +8,15 @@ gradients within 3e-4 of the tensor's scale floored at 1e-2 of the largest gradi
 (``e_ref32`` of the fixture's json) is printed beside the measured figure.
 """
 import dataclasses
-import json
-import os
 
 import pytest
 import torch
-from safetensors.torch import load_file
 
 from labelanything_amd.episodes import make_episode
 from labelanything_amd.models import Lam, build_lam_no_vit
+from tests import model_checks as MC
 from tests.cases_oneway import MARGIN, MAX_BAND_SHARE, OW_CASES, OW_TRAIN, SRC_STRIDE
-from tests.helpers import GOLDEN, argmax_disagreement, load_golden, rel_err
+from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +26,7 @@ NORM3 = tuple(f"mask_decoder.transformer.layers.{l}.norm3." for l in range(2))
 
 
 def model_for(name):
-    case = OW_CASES[name]
-    gold, meta = load_golden(f"oneway_{name}")
-    lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()
-    lam.selected_rows = gold.get("selected_rows")
-    return lam, case, gold, meta
+    return MC.load_model(OW_CASES, name, "oneway_")
 
 
 def engine_with(lam, **kw):
@@ -59,12 +53,7 @@ def forward_errors(lam, case, gold):
 
 
 def check_argmax(name, out, gold, meta):
-    assert 0 <= meta["margin_band_share"] <= MAX_BAND_SHARE and meta["margin"] == MARGIN        # the generator's figure, not ours
-    assert torch.equal(out["logits"].argmax(dim=1).cpu(), out["argmax"].cpu())
-    n_diff, n_real = argmax_disagreement(out["logits"], gold["argmax"].long(), gold["logits"], margin_rel=MARGIN)
-    print(f"[{name}] argmax differs on {n_diff} pixels, {n_real} outside the {MARGIN:.0e} margin band "
-          f"({meta['margin_band_share']:.2%} of the reference's pixels lie inside it)")
-    assert n_real == 0
+    MC.check_argmax(name, out, gold, MARGIN, band_share=(meta, MAX_BAND_SHARE))
 
 
 @pytest.mark.parametrize("name", list(OW_CASES))
@@ -129,36 +118,15 @@ def test_more_than_32_classes_take_the_chain():
 
 @pytest.mark.parametrize("name", ["ow_d256", "ow_d64"])
 def test_graph_replay_is_bit_identical_and_tracks_new_inputs(name):
-    lam, case, gold, _ = model_for(name)
-    b1 = make_episode(**case["episode"])
-    b2 = make_episode(**{**case["episode"], "seed": 778})
-    e1, e2 = lam.forward_argmax(b1), lam.forward_argmax(b2)
-    lam.use_graphs = True
-    g1 = lam.forward_argmax(b1)       # capture
-    g2 = lam.forward_argmax(b2)       # replay with new inputs
-    g1b = lam.forward_argmax(b1)
-    torch.cuda.synchronize()
-    for k in ("logits", "argmax"):
-        assert torch.equal(e1[k], g1[k]) and torch.equal(e2[k], g2[k]) and torch.equal(e1[k], g1b[k]), k
-    assert len(lam._graphs) == 1
-    assert not torch.equal(e1["logits"], e2["logits"])
+    lam, case, _, _ = model_for(name)
+    MC.check_graph_replay(lam, case)
 
 
 @pytest.mark.parametrize("name", ["ow_d256", "ow_masks"])
 def test_predict_from_cached_class_embeddings_matches_forward(name):
-    from labelanything_amd.cache import set_class_embeddings
-    lam, case, gold, meta = model_for(name)
-    batch = make_episode(**case["episode"])
-    full = lam(batch)["logits"]
-    examples = {k: (v[:, 1:] if k in ("embeddings", "dims") else v) for k, v in batch.items()}
-    ce = lam.generate_class_embeddings(examples)
+    lam, case, gold, _ = model_for(name)
+    ce, _ = MC.check_cached_predict(lam, case)
     assert rel_err(ce["class_embeddings"], gold["class_embeddings"]) <= TOL
-    q = {"embeddings": batch["embeddings"][:, :1], "dims": batch["dims"][:, 0]}
-    pred = lam.predict(q, ce)
-    torch.cuda.synchronize()
-    assert rel_err(pred, full) <= 1e-6
-    set_class_embeddings(lam, {k: v[0] for k, v in examples.items()})
-    assert rel_err(lam.predict(q), full) <= 1e-6
 
 
 def test_classes_without_a_valid_support_are_treated_as_in_the_plain_model():
@@ -203,50 +171,20 @@ def test_the_recipe_builds_loads_and_runs_and_is_not_the_two_way_decoder():
 
 
 def test_one_training_step_matches_the_reference():
-    from labelanything_amd.train import LamTrainer
-    from tests.test_train_gpu import make_gt
     name = OW_TRAIN["case"]
     lam, case, gold_fwd, _ = model_for(name)
-    gold = load_file(os.path.join(GOLDEN, f"oneway_{name}_train.safetensors"))
-    with open(os.path.join(GOLDEN, f"oneway_{name}_train.json")) as fh:
-        meta = json.load(fh)
-    assert torch.equal(gold["selected_rows"], gold_fwd["selected_rows"])
-    batch = make_episode(**case["episode"])
-    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=meta["seed_gt"])
-    tr = LamTrainer(lam)
-    assert sorted(tr.names) == sorted(meta["keys"] + meta["dead"])
+    gold, meta = MC.load_train_fixture(f"oneway_{name}")
+    lin1 = "mask_decoder.transformer.layers.1.mlp.lin1.weight"
+    before = {k: p.detach().clone() for k, p in lam.named_parameters() if k.startswith(NORM3) or k == lin1}
+    tr, _, grads = MC.run_training_step(lam, case, gold_fwd, gold, meta, TOL, label=name)
     # norm3 sits in the dead tail of the flat buffer, with the plain prompt encoder's final attention
     tail = [k for k in tr.names if k.startswith(NORM3)]
     assert len(tail) == 4 and tr.names.index(tail[0]) > tr.names.index("mask_decoder.class_mlp.layers.2.bias")
-    lin1 = "mask_decoder.transformer.layers.1.mlp.lin1.weight"
-    before = {k: p.detach().clone() for k, p in lam.named_parameters() if k.startswith(NORM3) or k == lin1}
-    tr.zero_grad()
-    res = tr.forward_backward(batch, gt)
-    torch.cuda.synchronize()
-    assert rel_err(res["logits"], gold_fwd["logits"]) <= TOL
-    loss = float(res["loss"])
-    print(f"[train {name}] loss {loss:.8f} reference {meta['loss']:.8f} (fp64 {meta['loss_fp64']:.8f})")
-    assert abs(loss - meta["loss"]) <= TOL * abs(meta["loss"])
     e_ref = float(meta["e_ref32"])
     print(f"[train {name}] gradient bound {GRAD_TOL:.0e}; the reference's own fp32-vs-fp64 error {e_ref:.3e} (x4 = {4 * e_ref:.3e})")
-    grads = dict(zip(tr.names, tr.opt.grad_views))
-    keys = meta["keys"]
-    assert set(keys) <= set(tr.names)
-    for k in meta["dead"]:                                           # never reached by the reference's forward either
-        assert float(grads[k].abs().max()) == 0.0, k
     assert all(any(k.startswith(p) for k in meta["dead"]) for p in NORM3)
-    gn = torch.stack([grads[k].norm() for k in keys]).cpu()
-    floor = 1e-2 * float(gold["grad_norm"].max())
-    rel_n = (gn - gold["grad_norm"]).abs() / gold["grad_norm"].clamp_min(floor)
-    print(f"[train {name}] worst gradient-norm difference {float(rel_n.max()):.3e} at {keys[int(rel_n.argmax())]}")
-    full = {k[5:]: v for k, v in gold.items() if k.startswith("grad.")}
-    assert "mask_decoder.transformer.layers.1.mlp.lin1.weight" in full
-    gmax = max(float(v.abs().max()) for v in full.values())
-    worst = {k: float((grads[k].cpu() - v).abs().max()) / max(float(v.abs().max()), 1e-2 * gmax) for k, v in full.items()}
-    print(f"[train {name}] worst entry-wise gradient difference {max(worst.values()):.3e} at {max(worst, key=worst.get)}")
-    assert float(rel_n.max()) <= GRAD_TOL
-    bad = {k: v for k, v in worst.items() if v > GRAD_TOL}
-    assert not bad, bad
+    assert "grad." + lin1 in gold
+    MC.compare_gradients(tr.names, grads, gold, meta, GRAD_TOL, label=name)
     # an optimizer step leaves norm3 where it was: no gradient, and the trainer skips tensors that never received one
     tr.apply_update()
     torch.cuda.synchronize()

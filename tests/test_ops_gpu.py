@@ -14,25 +14,13 @@ import torch
 import torch.nn.functional as F
 
 from oracle import lam_oracle as O
-from tests.helpers import rel_err
+from tests.helpers import L, rel_err, rnd
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
 TOL16 = {torch.float16: 2e-3, torch.bfloat16: 1.6e-2}
 TOL32 = {torch.float16: 1e-3, torch.bfloat16: 4e-3}
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).cuda()
 
 
 @pytest.mark.parametrize("dt", DTYPES)

@@ -15,20 +15,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_decoder_ops_gpu import check_guards, guarded, rint, rnd, untouched
+from tests.helpers import L, check_guards, guarded, rint, rnd, untouched
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 256, 384), (50, 256, 256), (129, 256, 128), (200, 256, 2048), (900, 256, 2048)]
 EPS = 1e-5
 BOUND = 2e-5                 # the bound tests/test_ops_gpu.py holds la_twoway_i2t to: same operand splitting, same LayerNorm epilogue
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def planes(w):

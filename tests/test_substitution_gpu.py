@@ -16,6 +16,7 @@ import torch
 from safetensors.torch import load_file
 
 from labelanything_amd.substitution import Substitutor, generate_points_from_errors
+from tests.helpers import dataset_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -217,36 +218,6 @@ def test_preds_out_is_torch_argmax():
 
 
 # ---- 6 - 8. the trainer ----------------------------------------------------------------------------------------------------------
-def dataset_batch(case, seed=0, prompts=None):
-    """make_episode's model input widened to the dataset's layout: the query gets prompts too (a copy of the first support's),
-    ground truths for all M+1 images."""
-    from labelanything_amd.episodes import make_episode
-    ep = dict(case["episode"])
-    if prompts is not None:
-        ep["prompts"] = prompts
-    batch = make_episode(**ep)
-    out = dict(batch)
-    for k in ("prompt_points", "flag_points", "prompt_bboxes", "flag_bboxes", "prompt_masks", "flag_masks", "flag_examples"):
-        if k in batch:
-            out[k] = torch.cat([batch[k][:, :1], batch[k]], dim=1)
-    if "prompt_points" not in out:
-        b, m1, c = out["flag_examples"].shape
-        out["prompt_points"] = torch.zeros(b, m1, c, 1, 2)
-        out["flag_points"] = torch.zeros(b, m1, c, 1)
-    dims = out["dims"]
-    b, m1 = dims.shape[:2]
-    c = out["flag_examples"].shape[2]
-    hmax, wmax = int(dims[..., 0].max()), int(dims[..., 1].max())
-    g = torch.Generator().manual_seed(seed)
-    gts = torch.randint(0, c, (b, m1, (hmax + 15) // 16, (wmax + 15) // 16), generator=g)
-    gts = gts.repeat_interleave(16, 2).repeat_interleave(16, 3)[:, :, :hmax, :wmax].contiguous()
-    for i in range(b):
-        for m in range(m1):
-            gts[i, m, int(dims[i, m, 0]):] = -100
-            gts[i, m, :, int(dims[i, m, 1]):] = -100
-    return out, gts
-
-
 def make_trainer(case, rows, **kw):
     from labelanything_amd.models import Lam
     from labelanything_amd.train import LamTrainer

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from oracle import lam_oracle as O
 from tests import test_decoder_ops_gpu as T
+from tests.helpers import GUARD, L, NAN, check_guards, guarded, untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +28,6 @@ SHAPES = {
 PATTERNS = ("valid", "mixed", "zero")
 _inputs = {}
 _refs = {}
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def flags_of(pattern, s, c):
@@ -116,17 +110,17 @@ def call(L, name, pattern, *, has_masks=True, has_support=True, has_class=True, 
         masks, flags, support, s = masks[sup * c:(sup + 1) * c], flags[sup:sup + 1], support[sup:sup + 1], 1
     code, tdt = getattr(L, T.DTS[dt][0]), T.DTS[dt][1]
     cols16 = 2 * d if dt == "f16x2" else d
-    b32, src32 = T.guarded(s * hw, d)
-    b16, src16 = T.guarded(s * hw, cols16, dtype=tdt) if with16 else (None, None)
-    bpe, srcpe16 = T.guarded(s * hw, cols16, dtype=tdt) if with16 else (None, None)
+    b32, src32 = guarded(s * hw, d)
+    b16, src16 = guarded(s * hw, cols16, dtype=tdt) if with16 else (None, None)
+    bpe, srcpe16 = guarded(s * hw, cols16, dtype=tdt) if with16 else (None, None)
     pe = inp["pe"].cuda()
     L.mask_embed_pooled(masks.contiguous().cuda() if has_masks else None, flags.reshape(-1).contiguous().cuda() if has_masks else None, s, c,
                         hm if has_masks else 0, g, d, wlist_of(inp["w"]), support.contiguous().cuda() if has_support else None,
                         inp["class_enc"].cuda() if has_class else None, pe, src32, src16, srcpe16, code)
-    T.check_guards(b32, src32)
+    check_guards(b32, src32)
     if with16:
-        T.check_guards(b16, src16)
-        T.check_guards(bpe, srcpe16)
+        check_guards(b16, src16)
+        check_guards(bpe, srcpe16)
     return src32.view(s, hw, d), src16, srcpe16, pe
 
 
@@ -174,10 +168,10 @@ def test_one_class_is_la_mask_embed(L, pattern):
     hw = g * g
     inp = inputs(name)
     got, _, _, pe = call(L, name, pattern, with16=False)
-    b32, plain = T.guarded(s * hw, d)
+    b32, plain = guarded(s * hw, d)
     L.mask_embed(inp["masks"].cuda(), flags_of(pattern, s, c).reshape(-1).cuda(), s, 1, hm, g, d, wlist_of(inp["w"]), inp["support"].cuda(),
                  inp["class_enc"].cuda(), pe, plain, None, None, L.LA_F16)
-    T.check_guards(b32, plain)
+    check_guards(b32, plain)
     a, b = got.reshape(-1).cpu(), plain.reshape(-1).cpu()
     inf = torch.full_like(b, float("inf"))
     ok = (a == b) | (a == torch.nextafter(b, inf)) | (a == torch.nextafter(b, -inf))
@@ -208,10 +202,10 @@ def test_counting_is_exact(L):
     flags = torch.tensor([[1, 1, 1, 1, 1], [1, 0, 1, 0, 1], [0, 0, 0, 0, 0], [0, 1, 1, 1, 1]], dtype=torch.int32)
     masks = (torch.rand(s * c, hm, hm, generator=torch.Generator().manual_seed(77)) < 0.5).float().cuda()
     class_enc = (8.0 * (torch.arange(c) + 1)).view(c, 1).expand(c, d).contiguous().cuda()
-    b32, src32 = T.guarded(s * hw, d)
+    b32, src32 = guarded(s * hw, d)
     L.mask_embed_pooled(masks, flags.reshape(-1).cuda(), s, c, hm, g, d, wlist_of(w), torch.zeros(s, hw, d, device="cuda"), class_enc,
                         torch.zeros(hw, d, device="cuda"), src32, None, None, L.LA_F32)
-    T.check_guards(b32, src32)
+    check_guards(b32, src32)
     want = ((flags == 0).sum(dim=1).float() + 8.0 * c * (c + 1) / 2).view(s, 1, 1).expand(s, hw, d)
     assert torch.equal(src32.view(s, hw, d).cpu(), want)
 
@@ -232,10 +226,10 @@ def test_refused_arguments_write_nothing(L, bad):
     hm, g, d, s, c = SHAPES["identity_c1"]
     hw = g * g
     inp = inputs("identity_c1")
-    buf = torch.full((s * hw * d + 2 * T.GUARD,), T.NAN, device="cuda")
-    b16 = torch.full((s * hw * d + 2 * T.GUARD,), T.NAN, device="cuda", dtype=torch.float16)
-    out = buf[T.GUARD:T.GUARD + s * hw * d].view(s * hw, d)
-    o16 = b16[T.GUARD:T.GUARD + s * hw * d].view(s * hw, d)
+    buf = torch.full((s * hw * d + 2 * GUARD,), NAN, device="cuda")
+    b16 = torch.full((s * hw * d + 2 * GUARD,), NAN, device="cuda", dtype=torch.float16)
+    out = buf[GUARD:GUARD + s * hw * d].view(s * hw, d)
+    o16 = b16[GUARD:GUARD + s * hw * d].view(s * hw, d)
     a = dict(masks=inp["masks"].cuda(), flags=flags_of("valid", s, c).reshape(-1).cuda(), s=s, c=c, hm=hm, g=g, d=d, pe=inp["pe"].cuda(), out=out,
              dt=L.LA_F16)
     a.update({"S=0": dict(s=0), "C=0": dict(c=0), "C<0": dict(c=-1), "g=0": dict(g=0), "D=0": dict(d=0), "Hm%4": dict(hm=30), "Hm=0": dict(hm=0),
@@ -243,4 +237,4 @@ def test_refused_arguments_write_nothing(L, bad):
     with pytest.raises(RuntimeError, match="la_mask_embed_pooled"):
         L.mask_embed_pooled(a["masks"], a["flags"], a["s"], a["c"], a["hm"], a["g"], a["d"], wlist_of(inp["w"]), inp["support"].cuda(),
                             inp["class_enc"].cuda(), a["pe"], a["out"], o16, None, a["dt"])
-    assert T.untouched(buf) and bool(torch.isnan(b16).all())
+    assert untouched(buf) and bool(torch.isnan(b16).all())

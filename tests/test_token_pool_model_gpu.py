@@ -7,17 +7,14 @@ cases); argmax exact outside the project's 2e-3 margin band; gradients within 3e
 gradient, the decoder-only bound of test_gradients_match_oracle_autograd (there is no max-over-examples kink on this path).  The
 reference's own fp32-vs-fp64 gradient error (``e_ref32`` of the fixture's json) is printed beside the measured figure.
 """
-import json
-import os
-
 import pytest
 import torch
-from safetensors.torch import load_file
 
 from labelanything_amd.episodes import make_episode
-from labelanything_amd.models import Lam, build_lam_no_vit
+from labelanything_amd.models import build_lam_no_vit
+from tests import model_checks as MC
 from tests.cases_token_pool import SRC_STRIDE, TP_CASES, TP_TRAIN
-from tests.helpers import GOLDEN, argmax_disagreement, load_golden, rel_err
+from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +25,7 @@ FINAL = ("prompt_encoder.transformer.final_attn_token_to_image.", "prompt_encode
 
 
 def model_for(name):
-    case = TP_CASES[name]
-    gold, meta = load_golden(f"token_pool_{name}")
-    lam = Lam(case["cfg"], seed=case["weight_seed"]).cuda()
-    lam.selected_rows = gold.get("selected_rows")
-    return lam, case, gold, meta
+    return MC.load_model(TP_CASES, name, "token_pool_")
 
 
 def forward_errors(lam, case, gold):
@@ -62,10 +55,7 @@ def test_forward_matches_the_reference_fixture(name):
           + f" (bound {TOL:.0e})")
     assert tuple(pe["class_examples_embeddings"].shape) == tuple(gold["class_examples_embeddings"].shape)
     assert all(v <= TOL for v in errs.values()), errs
-    assert torch.equal(out["logits"].argmax(dim=1).cpu(), out["argmax"].cpu())
-    n_diff, n_real = argmax_disagreement(out["logits"], gold["argmax"].long(), gold["logits"], margin_rel=ARGMAX_MARGIN)
-    print(f"[{name}] argmax differs on {n_diff} pixels, {n_real} outside the {ARGMAX_MARGIN:.0e} margin band")
-    assert n_real == 0
+    MC.check_argmax(name, out, gold, ARGMAX_MARGIN)
     assert torch.equal(out["class_examples_embeddings"], pe["class_examples_embeddings"])
 
 
@@ -89,37 +79,16 @@ def test_fused_and_unfused_two_way_paths_agree(name):
 
 @pytest.mark.parametrize("name", ["tp_d256", "tp_d64"])
 def test_graph_replay_is_bit_identical_and_tracks_new_inputs(name):
-    lam, case, gold, _ = model_for(name)
-    b1 = make_episode(**case["episode"])
-    b2 = make_episode(**{**case["episode"], "seed": 778})
-    e1, e2 = lam.forward_argmax(b1), lam.forward_argmax(b2)
-    lam.use_graphs = True
-    g1 = lam.forward_argmax(b1)       # capture
-    g2 = lam.forward_argmax(b2)       # replay with new inputs
-    g1b = lam.forward_argmax(b1)
-    torch.cuda.synchronize()
-    for k in ("logits", "argmax", "class_examples_embeddings"):
-        assert torch.equal(e1[k], g1[k]) and torch.equal(e2[k], g2[k]) and torch.equal(e1[k], g1b[k]), k
-    assert len(lam._graphs) == 1
-    assert not torch.equal(e1["logits"], e2["logits"])
+    lam, case, _, _ = model_for(name)
+    MC.check_graph_replay(lam, case, keys=("logits", "argmax", "class_examples_embeddings"))
 
 
 @pytest.mark.parametrize("name", ["tp_d256", "tp_masks"])
 def test_predict_from_cached_class_embeddings_matches_forward(name):
-    from labelanything_amd.cache import set_class_embeddings
-    lam, case, gold, meta = model_for(name)
-    batch = make_episode(**case["episode"])
-    full = lam(batch)["logits"]
-    examples = {k: (v[:, 1:] if k in ("embeddings", "dims") else v) for k, v in batch.items()}
-    ce = lam.generate_class_embeddings(examples)
+    lam, case, gold, _ = model_for(name)
+    ce, _ = MC.check_cached_predict(lam, case)
     assert tuple(ce["class_embeddings"].shape) == tuple(gold["class_embeddings"].shape)
     assert rel_err(ce["class_embeddings"], gold["class_embeddings"]) <= TOL
-    q = {"embeddings": batch["embeddings"][:, :1], "dims": batch["dims"][:, 0]}
-    pred = lam.predict(q, ce)
-    torch.cuda.synchronize()
-    assert rel_err(pred, full) <= 1e-6
-    set_class_embeddings(lam, {k: v[0] for k, v in examples.items()})
-    assert rel_err(lam.predict(q), full) <= 1e-6
 
 
 def test_the_recipe_builds_loads_and_runs():
@@ -146,46 +115,16 @@ def test_the_recipe_builds_loads_and_runs():
 
 
 def test_one_training_step_matches_the_reference():
-    from labelanything_amd.train import LamTrainer
-    from tests.test_train_gpu import make_gt
     name = TP_TRAIN["case"]
     lam, case, gold_fwd, _ = model_for(name)
-    gold = load_file(os.path.join(GOLDEN, f"token_pool_{name}_train.safetensors"))
-    with open(os.path.join(GOLDEN, f"token_pool_{name}_train.json")) as fh:
-        meta = json.load(fh)
-    assert torch.equal(gold["selected_rows"], gold_fwd["selected_rows"])
-    batch = make_episode(**case["episode"])
-    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=meta["seed_gt"])
-    tr = LamTrainer(lam)
-    # the final attention of the prompt encoder's transformer is live here: inside the active span, in front of nothing dead
-    assert sorted(tr.names) == sorted(meta["keys"] + meta["dead"])
-    tr.zero_grad()
-    res = tr.forward_backward(batch, gt)
-    torch.cuda.synchronize()
-    assert rel_err(res["logits"], gold_fwd["logits"]) <= TOL
-    loss = float(res["loss"])
-    print(f"[train {name}] loss {loss:.8f} reference {meta['loss']:.8f} (fp64 {meta['loss_fp64']:.8f})")
-    assert abs(loss - meta["loss"]) <= TOL * abs(meta["loss"])
+    gold, meta = MC.load_train_fixture(f"token_pool_{name}")
+    tr, _, grads = MC.run_training_step(lam, case, gold_fwd, gold, meta, TOL, label=name)
     e_ref = float(meta["e_ref32"])
     print(f"[train {name}] gradient bound {GRAD_TOL:.0e}; the reference's own fp32-vs-fp64 error {e_ref:.3e} (x4 = {4 * e_ref:.3e})")
-    grads = dict(zip(tr.names, tr.opt.grad_views))
-    keys = meta["keys"]
-    assert set(keys) <= set(tr.names)
-    for k in meta["dead"]:                                           # never reached by the reference's forward either
-        assert float(grads[k].abs().max()) == 0.0, k
+    # the final attention of the prompt encoder's transformer is live here: inside the active span, in front of nothing dead
     assert not any(k.startswith(FINAL) for k in meta["dead"])
-    for k in keys:
+    for k in meta["keys"]:
         if k.startswith(FINAL):
             assert float(grads[k].abs().max()) > 0.0, k
-    gn = torch.stack([grads[k].norm() for k in keys]).cpu()
-    floor = 1e-2 * float(gold["grad_norm"].max())
-    rel_n = (gn - gold["grad_norm"]).abs() / gold["grad_norm"].clamp_min(floor)
-    print(f"[train {name}] worst gradient-norm difference {float(rel_n.max()):.3e} at {keys[int(rel_n.argmax())]}")
-    full = {k[5:]: v for k, v in gold.items() if k.startswith("grad.")}
-    assert "prompt_encoder.transformer.final_attn_token_to_image.out_proj.weight" in full
-    gmax = max(float(v.abs().max()) for v in full.values())
-    worst = {k: float((grads[k].cpu() - v).abs().max()) / max(float(v.abs().max()), 1e-2 * gmax) for k, v in full.items()}
-    print(f"[train {name}] worst entry-wise gradient difference {max(worst.values()):.3e} at {max(worst, key=worst.get)}")
-    assert float(rel_n.max()) <= GRAD_TOL
-    bad = {k: v for k, v in worst.items() if v > GRAD_TOL}
-    assert not bad, bad
+    assert "grad.prompt_encoder.transformer.final_attn_token_to_image.out_proj.weight" in gold
+    MC.compare_gradients(tr.names, grads, gold, meta, GRAD_TOL, label=name)

@@ -161,7 +161,7 @@ def _enc_trainer(buckets: int):
 
 def _enc_episode(rank: int, step: int):
     from tests.cases import TRAIN_ENC_CASE as case
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     ep = dict(case["episode"])
     ep.update(seed=700 + 10 * step + rank, prompts=("mask", "point") if rank == 0 else ("mask",))
     batch = make_episode(**ep)

@@ -13,26 +13,9 @@ from labelanything_amd.weights import init_state_dict
 from oracle import lam_oracle as O
 from oracle import loss_oracle as LO
 from tests.cases import CASES, geometry_for
-from tests.helpers import GOLDEN, load_golden, rel_err
-from tests.test_multi_embedding_gpu import NAN, check_guards, guarded
+from tests.helpers import GOLDEN, NAN, check_guards, guarded, load_golden, make_gt, rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def make_gt(batch, n_classes, seed=0):
-    """A ground-truth map per episode at the padded output size: random blocky labels, some ignored pixels."""
-    g = torch.Generator().manual_seed(seed)
-    dims = batch["dims"]
-    b = dims.shape[0]
-    hmax, wmax = int(dims[..., 0].max()), int(dims[..., 1].max())
-    gt = torch.randint(0, n_classes, (b, (hmax + 15) // 16, (wmax + 15) // 16), generator=g)
-    gt = gt.repeat_interleave(16, 1).repeat_interleave(16, 2)[:, :hmax, :wmax].contiguous()
-    for i in range(b):
-        h, w = int(dims[i, 0, 0]), int(dims[i, 0, 1])
-        gt[i, h:, :] = -100
-        gt[i, :, w:] = -100
-    gt[torch.rand(gt.shape, generator=g) < 0.02] = -100
-    return gt
 
 
 def oracle_grads(case, batch, gt, rows, dtype=torch.float32):

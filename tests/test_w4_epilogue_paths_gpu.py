@@ -9,22 +9,11 @@ import math
 
 import pytest
 import torch
+from tests.helpers import L, rnd
 
 pytestmark = pytest.mark.gpu
 
 SENT = -3.0e4          # (exact in fp16 and fp32; no output of these cases comes near it)
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).cuda()
 
 
 def _ext(x, rows):

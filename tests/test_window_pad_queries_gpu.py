@@ -8,17 +8,11 @@ skipped: every image token is written, nothing but image tokens is written, ever
 """
 import pytest
 import torch
+from tests.helpers import L
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
-
-
-@pytest.fixture(scope="module")
-def L():
-    from labelanything_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def _all_padding_blocks(nimg, ih, iw, gg):

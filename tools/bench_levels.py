@@ -101,7 +101,7 @@ def bench_step(iters, repeats, batch_size):
     from labelanything_amd.models import Lam
     from labelanything_amd.train import LamTrainer
     from tests.cases_levels import LV_CASES
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     case = LV_CASES["l2_noeca"]
     ep = {**case["episode"], "batch": batch_size}
     batch = make_episode(**ep)

@@ -155,7 +155,7 @@ def grads_of(case, gt, double: bool):
 
 def run_train(name, case, seed_gt, full):
     from labelanything_amd.episodes import make_episode
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     batch = make_episode(**case["episode"])
     gt = make_gt(batch, batch["flag_examples"].shape[2], seed=seed_gt)
     loss32, g32, _ = grads_of(case, gt, double=False)

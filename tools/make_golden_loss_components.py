@@ -140,7 +140,7 @@ def make_loss():
 def make_train():
     from label_anything.experiment.utils import WrapperModule
     from transformers import get_scheduler
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     from labelanything_amd.episodes import make_episode
 
     case = TRAIN_LC_CASE

@@ -76,7 +76,7 @@ def run(case, out_name, full, seed_gt):
     from label_anything.loss import LabelAnythingLoss
     from transformers import get_scheduler
     from tests.cases import geometry_for
-    from tests.test_train_gpu import make_gt
+    from tests.helpers import make_gt
     from oracle import lam_oracle as O
     from oracle import loss_oracle as LO
     from labelanything_amd.episodes import make_episode

@@ -8,7 +8,8 @@ import bench
 from labelanything_amd.config import LamConfig
 from labelanything_amd.models import Lam
 from labelanything_amd.train import LamTrainer
-from tests.test_train_gpu import make_episode, make_gt, oracle_grads
+from tests.helpers import make_gt
+from tests.test_train_gpu import make_episode, oracle_grads
 
 wl = bench.WORKLOADS["cfg3_train"]
 cfg = LamConfig(**wl["model"])
