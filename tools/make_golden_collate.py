@@ -7,7 +7,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import tools.make_golden as MG           # noqa: E402,F401  (stub finder, reference first on sys.path)
+import tools.golden_lib             # noqa: E402,F401  (stub finder, reference first on sys.path)
 
 import numpy as np                        # noqa: E402
 import torch                              # noqa: E402

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Golden vectors of ``embedding_extraction="cross_attention"`` from the REFERENCE (build container only; builds on tools/make_golden.py's
-stub finder):
+"""Golden vectors of ``embedding_extraction="cross_attention"`` from the REFERENCE (build container only; tools/golden_lib.py
+imports it):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_cross_extract.py [--only NAME]
 
@@ -14,52 +14,28 @@ layer, the smallest and largest score spread (max - min along the keys) over all
 refuses a fixture in which some row's spread is below the case's ``min_spread`` (1.5; 0.5 for the heads of width 4 of the D = 64 case, see
 tests/cases_cross_extract.py) or the largest below 5 - a near-uniform softmax would hide a wrong softmax.
 """
-import argparse
-import json
 import math
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import tools.make_golden as MG          # noqa: E402,F401  (installs the stub finder, puts the reference first on sys.path)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tools.golden_lib as GL          # noqa: E402  (makes the reference importable)
 
 import torch                            # noqa: E402
-from safetensors.torch import save_file  # noqa: E402
-from label_anything.models.build_lam import _build_lam   # noqa: E402  (the reference)
+from tests.cases_cross_extract import XE_CASES   # noqa: E402
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 PRE = "prompt_encoder.embedding_extraction."
 MAX_SPREAD = 5.0
 
 
-def build_reference(case):
-    from labelanything_amd.weights import init_state_dict
+def run(name, case):
     cfg = case["cfg"]
-    assert cfg.encoder_spec is None, "decoder-only cases"
-    lam = _build_lam(
-        build_vit=None, use_vit=False, image_embed_dim=cfg.image_embed_dim, embed_dim=cfg.embed_dim, image_size=cfg.image_size,
-        class_attention=cfg.class_attention, example_attention=cfg.example_attention, example_class_attention=cfg.example_class_attention,
-        spatial_convs=cfg.spatial_convs, class_encoder=dict(cfg.class_encoder) if cfg.class_encoder else None,
-        custom_preprocess=cfg.custom_preprocess,
+    lam, sd, batch, rows = GL.reference_episode(
+        case, embedding_extraction="cross_attention",
         # handed over UNRESOLVED where the case is segment_example_logits alone, so that the reference's own builder resolves them
         segment_example_logits=cfg.segment_example_logits,
-        embeddings_per_example=cfg.embeddings_per_example if cfg.embeddings_per_example > 1 else None,
-        embedding_extraction="cross_attention")
-    lam.eval()
-    sd = init_state_dict(cfg, case["weight_seed"])
-    lam.load_state_dict(sd, strict=True)
-    return lam, sd
-
-
-def run(name, case):
-    from labelanything_amd.episodes import make_episode
-    from tools.make_golden_multi_embedding import fixed_rows
-    lam, sd = build_reference(case)
-    cfg = case["cfg"]
-    batch = make_episode(**case["episode"])
+        embeddings_per_example=cfg.embeddings_per_example if cfg.embeddings_per_example > 1 else None)
     b, m, c = batch["flag_examples"].shape
-    rows = fixed_rows(lam, case, c)
     module = lam.prompt_encoder.embedding_extraction
     seen = {}
     spreads = [[], []]
@@ -108,41 +84,22 @@ def run(name, case):
     tensors = {
         "class_examples_embeddings": cee.contiguous(),
         "flag_examples": flags.to(torch.uint8).contiguous(),
-        "low_res_logits": seg_low.contiguous(),
-        "logits": ref["logits"].contiguous(),
-        "argmax": ref["logits"].argmax(dim=1).to(torch.uint8).contiguous(),
+        **GL.logit_tensors(seg_low, ref),
     }
-    if rows is not None:
-        tensors["selected_rows"] = rows
-    path = os.path.join(GOLDEN, f"cross_extract_{name}.safetensors")
-    save_file(tensors, path)
     # NHWC rows, as the engine holds the stream: (B M C, h' w', D)
     stream = sub.flatten(2).transpose(1, 2).contiguous()
-    spath = os.path.join(GOLDEN, f"cross_extract_{name}_stream.safetensors")
-    save_file({"stream": stream, "sub_embeddings": sub_emb.contiguous(), "flag_examples_in": seen["flags"].to(torch.uint8).contiguous()}, spath)
+    stream_size = GL.write_fixture(f"cross_extract_{name}_stream", {"stream": stream, "sub_embeddings": sub_emb.contiguous(),
+                                                                    "flag_examples_in": seen["flags"].to(torch.uint8).contiguous()}, None)
     added = [k for k in sd if k.startswith(PRE)]
     assert len(added) == 37 and list(sd)[-37:] == added
     meta = {"case": name, "weight_seed": case["weight_seed"], "episode": case["episode"], "queries": int(n), "folded_queries": 8 * int(n),
             "stream_stride": st, "stream_shape": list(stream.shape), "full_stream_shape": list(seen["src"].shape),
             "added_keys": added, "added_shapes": {k: list(sd[k].shape) for k in added}, "score_spread": stats, "min_spread_required": case["min_spread"],
             "key_mask_is_a_no_op": mask_noop, "embedding_scale": float(cee.abs().max()),
-            "nan_fraction_of_invalid_classes": float(torch.isnan(ref["logits"]).double().mean()),
-            "torch": torch.__version__, "generated_by": "tools/make_golden_cross_extract.py"}
-    with open(os.path.join(GOLDEN, f"cross_extract_{name}.json"), "w") as fh:
-        json.dump(meta, fh, indent=1, default=list)
-    print(f"[{name}] n {n} spreads {stats} bytes {os.path.getsize(path)} + {os.path.getsize(spath)} scale {meta['embedding_scale']:.3f}")
-
-
-def main():
-    from tests.cases_cross_extract import XE_CASES
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default=None)
-    a = ap.parse_args()
-    torch.manual_seed(0)
-    for name, case in XE_CASES.items():
-        if a.only in (None, name):
-            run(name, case)
+            "nan_fraction_of_invalid_classes": float(torch.isnan(ref["logits"]).double().mean())}
+    size = GL.write_fixture(f"cross_extract_{name}", tensors, meta, rows)
+    print(f"[{name}] n {n} spreads {stats} bytes {size} + {stream_size} scale {meta['embedding_scale']:.3f}")
 
 
 if __name__ == "__main__":
-    main()
+    GL.main(XE_CASES, run)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Golden vectors of the two-level classification head (``classification_levels=2``) from the REFERENCE (build container only; builds on
-tools/make_golden.py's stub finder):
+"""Golden vectors of the two-level classification head (``classification_levels=2``) from the REFERENCE (build container only;
+tools/golden_lib.py imports it):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_levels.py [--only NAME] [--no-train]
 
@@ -25,22 +25,17 @@ rounding noise (1e-7 against a largest gradient of 2e-2, 1e-17 in fp64).  It is 
 (it is listed under ``inert``), and the json carries what a test needs to bound that noise instead: ``dseg_abs_sum`` = sum |d loss /
 d low_res_logits| and ``dseg_numel``, from the fp64 run.
 """
-import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import tools.make_golden as MG          # noqa: E402,F401  (installs the stub finder, puts the reference first on sys.path)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tools.golden_lib as GL          # noqa: E402  (makes the reference importable)
 
 import torch                            # noqa: E402
 import torch.nn.functional as F         # noqa: E402
-from safetensors.torch import save_file  # noqa: E402
-from label_anything.models.build_lam import _build_lam   # noqa: E402  (the reference)
-import label_anything.models.mask_decoder as REF_MD      # noqa: E402
+import label_anything.models.mask_decoder as REF_MD      # noqa: E402  (the reference)
+from tests.cases_levels import LV_CASES, LV_TRAIN, LV_TRAIN_FULL   # noqa: E402
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 INERT = "mask_decoder.level_reducer.bias"      # zero gradient under a softmax objective: see the docstring
 RESIZE_STAND_IN = 'F.interpolate(img, size, mode="bilinear", align_corners=False, antialias=True)'
 
@@ -52,52 +47,13 @@ def resize_stand_in(img, size, *a, **kw):
 REF_MD.resize = resize_stand_in
 
 
-def build_reference(case):
-    from labelanything_amd.weights import init_state_dict
-    cfg = case["cfg"]
-    assert cfg.encoder_spec is None, "decoder-only cases"
-    lam = _build_lam(
-        build_vit=None, use_vit=False, image_embed_dim=cfg.image_embed_dim, embed_dim=cfg.embed_dim, image_size=cfg.image_size,
-        class_attention=cfg.class_attention, example_attention=cfg.example_attention, example_class_attention=cfg.example_class_attention,
-        spatial_convs=cfg.spatial_convs, class_encoder=dict(cfg.class_encoder) if cfg.class_encoder else None,
-        custom_preprocess=cfg.custom_preprocess, classification_levels=cfg.classification_levels)
-    lam.eval()
-    sd = init_state_dict(cfg, case["weight_seed"])
-    lam.load_state_dict(sd, strict=True)
-    return lam, sd
-
-
-def fixed_rows(lam, case, c):
-    cfg = case["cfg"]
-    if not cfg.bank_size:
-        return None
-    gr = torch.Generator().manual_seed(case["weight_seed"] + 7)
-    rows = torch.cat([torch.zeros(1, dtype=torch.long), torch.randperm(cfg.bank_size - 1, generator=gr)[: c - 1] + 1])
-    lam.prompt_encoder.class_encoder.sample_rows = lambda C, device, _r=rows: _r.to(device)
-    return rows
-
-
 def run_forward(name, case):
-    from labelanything_amd.episodes import make_episode
-    lam, _ = build_reference(case)
-    batch = make_episode(**case["episode"])
-    c = batch["flag_examples"].shape[2]
-    rows = fixed_rows(lam, case, c)
-    calls = []
-    md = lam.mask_decoder
-    orig = md._classify
-
-    def spy(query_embeddings, class_embeddings, flag_examples):
-        out = orig(query_embeddings, class_embeddings, flag_examples)
-        calls.append((query_embeddings.detach().clone(), class_embeddings.detach().clone(), out.detach().clone()))
-        return out
-
-    md._classify = spy
+    lam, _, batch, rows = GL.reference_episode(case, classification_levels=case["cfg"].classification_levels)
+    calls = GL.spy_classify(lam)
     with torch.no_grad():
         seg_low, _ = lam._forward(batch)
         n_calls = len(calls)
         ref = lam(batch)
-    md._classify = orig
     assert n_calls == 2, n_calls
     (img, tok, cls1), (_, _, cls0) = calls[:2]
     b, d, g, _ = img.shape
@@ -106,95 +62,41 @@ def run_forward(name, case):
         "image_rows": img.flatten(2).transpose(1, 2).contiguous(),              # (B, g*g, D) NHWC: the transformer's image stream
         "cls1": cls1.contiguous(),                                              # (B, C, g, g)
         "cls0": cls0.contiguous(),                                              # (B, C, 4g, 4g)
-        "low_res_logits": seg_low.contiguous(),
-        "logits": ref["logits"].contiguous(),
-        "argmax": ref["logits"].argmax(dim=1).to(torch.uint8).contiguous(),
+        **GL.logit_tensors(seg_low, ref),
     }
-    if rows is not None:
-        tensors["selected_rows"] = rows
-    path = os.path.join(GOLDEN, f"levels_{name}.safetensors")
-    save_file(tensors, path)
     meta = {"case": name, "weight_seed": case["weight_seed"], "episode": case["episode"], "grid": int(g),
             "resize_stand_in": RESIZE_STAND_IN,
             "resize_note": "mask_decoder.py:359 calls torchvision's resize; torchvision is not installed where the fixture was made, this one "
                            "call is the stand-in above and not the reference's own",
-            "scale": {"cls1": float(cls1.abs().max()), "cls0": float(cls0.abs().max()), "low_res_logits": float(seg_low.abs().max())},
-            "torch": torch.__version__, "generated_by": "tools/make_golden_levels.py"}
-    with open(os.path.join(GOLDEN, f"levels_{name}.json"), "w") as fh:
-        json.dump(meta, fh, indent=1, default=list)
-    print(f"[{name}] grid {g} bytes {os.path.getsize(path)} scale {meta['scale']}")
+            "scale": {"cls1": float(cls1.abs().max()), "cls0": float(cls0.abs().max()), "low_res_logits": float(seg_low.abs().max())}}
+    size = GL.write_fixture(f"levels_{name}", tensors, meta, rows)
+    print(f"[{name}] grid {g} bytes {size} scale {meta['scale']}")
 
 
-def grads_of(case, gt, double: bool):
-    from label_anything.experiment.utils import WrapperModule
-    from label_anything.loss import LabelAnythingLoss
-    from labelanything_amd.episodes import make_episode
-    lam, sd = build_reference(case)
-    lam.train()
-    batch = make_episode(**case["episode"])
-    if double:
-        lam.double()
-        batch = {k: (v.double() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in batch.items()}
-    fixed_rows(lam, case, batch["flag_examples"].shape[2])
-    model = WrapperModule(lam, LabelAnythingLoss({"focal": {"weight": 1.0}}, class_weighting=True))
+def reducer_output(lam):
+    """The level reducer's output with its gradient retained: d loss / d low_res_logits."""
     seen = []
 
     def keep(module, inputs, output):
         output.retain_grad()
         seen.append(output)
 
-    hook = lam.mask_decoder.level_reducer.register_forward_hook(keep)
-    res = model(batch, gt)
-    hook.remove()
-    loss = res["loss"]["value"]
-    loss.backward()
-    grads = {k: (p.grad.detach().clone() if p.grad is not None else None) for k, p in lam.named_parameters()}
-    assert all(k in sd for k in grads) and len(seen) == 1
-    return float(loss), grads, seen[0].grad.detach()
+    lam.mask_decoder.level_reducer.register_forward_hook(keep)
+    return seen
 
 
-def run_train(name, case, seed_gt, full):
-    from labelanything_amd.episodes import make_episode
-    from tests.helpers import make_gt
-    batch = make_episode(**case["episode"])
-    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=seed_gt)
-    loss32, g32, _ = grads_of(case, gt, double=False)
-    loss64, g64, dseg64 = grads_of(case, gt, double=True)
-    assert sorted(k for k, g in g32.items() if g is not None) == sorted(k for k, g in g64.items() if g is not None)
-    assert float(g64[INERT].abs().max()) <= 1e-12 * max(float(g.abs().max()) for g in g64.values() if g is not None)     # zero analytically
-    keys = sorted(k for k, g in g32.items() if g is not None and k != INERT)
-    gmax = max(float(g64[k].abs().max()) for k in keys)
-    kink = {k: float((g32[k].double() - g64[k]).abs().max()) / max(float(g64[k].abs().max()), 1e-2 * gmax) for k in keys}
-    e_kink = max(kink.values())
-    # (the ground truth is not stored: tests rebuild it with make_gt(seed_gt), as test_gradients_match_oracle_autograd does)
-    out = {"loss": torch.tensor([loss32]), "grad_norm": torch.stack([g32[k].norm() for k in keys])}
-    for k in full:
-        out["grad." + k] = g32[k].contiguous()
-    path = os.path.join(GOLDEN, f"levels_{name}_train.safetensors")
-    save_file(out, path)
-    with open(os.path.join(GOLDEN, f"levels_{name}_train.json"), "w") as fh:
-        json.dump({"keys": keys, "dead": sorted(k for k, g in g32.items() if g is None), "loss": loss32, "loss_fp64": loss64, "e_kink": e_kink,
-                   "e_kink_worst_tensor": max(kink, key=kink.get), "seed_gt": seed_gt, "inert": [INERT],
-                   "inert_reference_fp32": float(g32[INERT].abs().max()), "inert_reference_fp64": float(g64[INERT].abs().max()),
-                   "dseg_abs_sum": float(dseg64.abs().sum()), "dseg_numel": int(dseg64.numel()), "resize_stand_in": RESIZE_STAND_IN,
-                   "torch": torch.__version__, "generated_by": "tools/make_golden_levels.py"}, fh, indent=1)
-    print(f"[{name} train] loss {loss32:.8f} (fp64 {loss64:.8f}) e_kink {e_kink:.3e} at {max(kink, key=kink.get)} tensors {len(keys)} "
-          f"bytes {os.path.getsize(path)}")
-
-
-def main():
-    from tests.cases_levels import LV_CASES, LV_TRAIN, LV_TRAIN_FULL
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--no-train", action="store_true")
-    a = ap.parse_args()
-    torch.manual_seed(0)
-    for name, case in LV_CASES.items():
-        if a.only in (None, name):
-            run_forward(name, case)
-    if not a.no_train and a.only in (None, LV_TRAIN["case"]):
-        run_train(LV_TRAIN["case"], LV_CASES[LV_TRAIN["case"]], LV_TRAIN["seed_gt"], LV_TRAIN_FULL)
+def train():
+    name = LV_TRAIN["case"]
+    step = GL.run_train(LV_CASES[name], LV_TRAIN["seed_gt"], watch=reducer_output,
+                        classification_levels=LV_CASES[name]["cfg"].classification_levels)
+    assert len(step.watched64) == 1
+    dseg64 = step.watched64[0].grad.detach()
+    assert float(step.g64[INERT].abs().max()) <= 1e-12 * max(float(step.g64[k].abs().max()) for k in step.keys)     # zero analytically
+    inert32, inert64 = step.g32.pop(INERT), step.g64.pop(INERT)               # out of keys, grad_norm and e_kink
+    GL.write_train(f"levels_{name}", step, [k for k in LV_TRAIN_FULL if k != INERT], "e_kink", tensors={"grad." + INERT: inert32.contiguous()},
+                   meta={"inert": [INERT], "inert_reference_fp32": float(inert32.abs().max()), "inert_reference_fp64": float(inert64.abs().max()),
+                         "dseg_abs_sum": float(dseg64.abs().sum()), "dseg_numel": int(dseg64.numel()), "resize_stand_in": RESIZE_STAND_IN})
 
 
 if __name__ == "__main__":
-    main()
+    GL.main(LV_CASES, run_forward, [(LV_TRAIN["case"], train)])

@@ -7,14 +7,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.make_golden_metrics import import_reference   # noqa: E402  (stub finder + path order)
+import tools.golden_lib                                    # noqa: E402,F401  (stub finder + path order)
 
 import torch                                                # noqa: E402
 from safetensors.torch import save_file                    # noqa: E402
 
 
 def main():
-    import_reference()
     from label_anything.loss import LabelAnythingLoss
     from oracle import loss_oracle as LO
     g = torch.Generator().manual_seed(5)

@@ -17,7 +17,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import tools.make_golden as MG                              # noqa: E402  (stub finder, the reference first on sys.path)
+import tools.golden_lib as GL                               # noqa: E402  (stub finder, the reference first on sys.path)
 
 import torch                                                # noqa: E402
 from safetensors.torch import save_file                     # noqa: E402
@@ -144,7 +144,7 @@ def make_train():
     from labelanything_amd.episodes import make_episode
 
     case = TRAIN_LC_CASE
-    lam, sd = MG.build_reference(case)
+    lam, sd = GL.build_reference(case)
     lam.train()
     cfg = case["cfg"]
     batch = make_episode(**case["episode"])

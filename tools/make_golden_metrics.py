@@ -10,58 +10,15 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.dont_write_bytecode = True
-os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
+sys.path.insert(0, ROOT)
+import tools.golden_lib             # noqa: E402,F401  (stub finder, reference first on sys.path)
 
-import types
-import importlib.abc
-import importlib.machinery
-
-import numpy as np
-import torch
-from transformers import ViTModel, AutoModel, AutoBackbone, get_scheduler  # noqa: F401  (real imports before the stubs)
-import accelerate, huggingface_hub, safetensors.torch  # noqa: F401,E401
-from safetensors.torch import save_file
-
-_STUB_ROOTS = {"ruamel", "torchvision", "pycocotools", "torchmetrics", "wandb", "easydict", "cv2", "timm", "dropblock",
-               "lovely_tensors", "captum", "optuna", "wget", "nicegui", "streamlit", "colorlog", "skimage", "kornia",
-               "streamlit_drawable_canvas", "sklearn"}
-
-
-class _Stub(types.ModuleType):
-    def __getattr__(self, k):
-        if k.startswith("__"):
-            raise AttributeError(k)
-        return type(k, (object,), {"__init__": lambda s, *a, **kw: None, "__call__": lambda s, *a, **kw: None,
-                                   "__getattr__": lambda s, k: (lambda *a, **kw: None)})
-
-
-class _Loader(importlib.abc.Loader):
-    def create_module(self, spec):
-        m = _Stub(spec.name)
-        m.__path__ = []
-        return m
-
-    def exec_module(self, module):
-        pass
-
-
-class _Finder(importlib.abc.MetaPathFinder):
-    def find_spec(self, name, path, target=None):
-        if name.split(".")[0] in _STUB_ROOTS:
-            return importlib.machinery.ModuleSpec(name, _Loader(), is_package=True)
-
-
-def import_reference():
-    """The reference package must win over this repo's same-named shim: its root goes FIRST on sys.path."""
-    sys.meta_path.insert(0, _Finder())
-    sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != ROOT]
-    sys.path.insert(0, "/root/reference")
-    sys.path.append(ROOT)
+import numpy as np                  # noqa: E402
+import torch                        # noqa: E402
+from safetensors.torch import save_file   # noqa: E402
 
 
 def main():
-    import_reference()
     from label_anything.data.utils import to_global_multiclass as ref_fn
     from oracle import metrics_oracle as MO
     g = torch.Generator().manual_seed(77)

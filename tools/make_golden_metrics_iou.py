@@ -122,10 +122,9 @@ def install_torchmetrics_standin() -> None:
 
 
 def main():
-    import tools.make_golden_metrics as G
-    G._STUB_ROOTS.discard("torchmetrics")
+    import tools.golden_lib as GL                            # stub finder + path order
+    GL.STUB_ROOTS.discard("torchmetrics")
     install_torchmetrics_standin()
-    G.import_reference()
     from label_anything.utils import metrics as RM           # the REFERENCE's module (first on sys.path now)
     assert RM.__file__.startswith("/root/reference/"), RM.__file__
     from oracle import metrics_oracle as MO

@@ -16,7 +16,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import tools.make_golden as MG          # noqa: E402,F401  (installs the stub finder, puts the reference first)
+import tools.golden_lib            # noqa: E402,F401  (installs the stub finder, puts the reference first)
 
 import torch                            # noqa: E402
 from safetensors.torch import save_file  # noqa: E402

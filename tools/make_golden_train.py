@@ -12,12 +12,10 @@ change for EVERY learnable tensor, and the full first gradient + final value of 
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import tools.make_golden as MG          # noqa: E402  (installs the stub finder, puts /root/reference first)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tools.golden_lib as GL          # noqa: E402  (makes the reference importable)
 
 import torch                            # noqa: E402
-from safetensors.torch import save_file  # noqa: E402
 
 FULL = ["neck.0.weight", "neck.3.bias", "prompt_encoder.mask_downscaling.0.weight", "prompt_encoder.mask_downscaling.4.weight",
         "prompt_encoder.point_embeddings.1.weight", "prompt_encoder.not_a_mask_embed.weight", "prompt_encoder.class_encoder.pos_embedding",
@@ -59,7 +57,7 @@ def main():
 
 def _to_4x(k: str) -> str:
     """This container's transformers names the ViT tensors differently from the 4.x names the repo (and the published checkpoints)
-    use; inverse of tools/make_golden.py:_hf_4x_to_local."""
+    use; inverse of tools/golden_lib.py:_hf_4x_to_local."""
     if not k.startswith("image_encoder."):
         return k
     k = k.replace("image_encoder.encoder.layers.", "image_encoder.layers.")
@@ -72,27 +70,17 @@ def _to_4x(k: str) -> str:
 
 
 def run(case, out_name, full, seed_gt):
-    from label_anything.experiment.utils import WrapperModule
-    from label_anything.loss import LabelAnythingLoss
     from transformers import get_scheduler
     from tests.cases import geometry_for
     from tests.helpers import make_gt
     from oracle import lam_oracle as O
     from oracle import loss_oracle as LO
-    from labelanything_amd.episodes import make_episode
 
-    lam, sd = MG.build_reference(case)
+    lam, sd, batch, rows = GL.reference_episode(case)
     lam.train()                                     # dropout is 0 everywhere on this path; train() as the reference's loop does
     cfg = case["cfg"]
-    batch = make_episode(**case["episode"])
-    c = batch["flag_examples"].shape[2]
-    gt = make_gt(batch, c, seed=seed_gt)
-    gr = torch.Generator().manual_seed(case["weight_seed"] + 7)
-    rows = None
-    if cfg.bank_size:
-        rows = torch.cat([torch.zeros(1, dtype=torch.long), torch.randperm(cfg.bank_size - 1, generator=gr)[: c - 1] + 1])
-        lam.prompt_encoder.class_encoder.sample_rows = lambda C, device, _r=rows: _r.to(device)
-    model = WrapperModule(lam, LabelAnythingLoss({"focal": {"weight": 1.0}}, class_weighting=True))
+    gt = make_gt(batch, batch["flag_examples"].shape[2], seed=seed_gt)
+    model = GL.focal_wrapper(lam)
     # no freeze_backbone (mae_noembs.yaml): every parameter is learnable, the image encoder included (lam.py:321-347)
     params = model.get_learnable_params({})
     named = {_to_4x(k): p for k, p in lam.named_parameters()}
@@ -100,8 +88,6 @@ def run(case, out_name, full, seed_gt):
     opt = torch.optim.AdamW(params, lr=case["lr"], weight_decay=case["weight_decay"])
     sched = get_scheduler("constant_with_warmup", opt, num_warmup_steps=case["warmup"], num_training_steps=100)
     out = {"gt": gt}
-    if rows is not None:
-        out["selected_rows"] = rows
     start = {k: p.detach().clone() for k, p in named.items()}
     losses = []
     for step in range(case["steps"]):
@@ -133,11 +119,9 @@ def run(case, out_name, full, seed_gt):
     for k in full:
         out["grad." + k] = grads[k].contiguous()
         out["final." + k] = named[k].detach().clone().contiguous()
-    save_file(out, os.path.join(ROOT, "tests", "golden", out_name + ".safetensors"))
-    with open(os.path.join(ROOT, "tests", "golden", out_name + ".json"), "w") as fh:
-        import json
-        json.dump({"keys": keys, "losses": losses, "generated_by": "tools/make_golden_train.py", "torch": torch.__version__}, fh, indent=1)
-    print("losses", losses, "tensors", len(keys), "bytes", sum(v.numel() * v.element_size() for v in out.values()))
+    # (generated_by and torch are named in the order of the committed json; write_fixture fills them in)
+    size = GL.write_fixture(out_name, out, {"keys": keys, "losses": losses, "generated_by": None, "torch": None}, rows)
+    print("losses", losses, "tensors", len(keys), "bytes", size)
 
 
 if __name__ == "__main__":
