@@ -780,6 +780,38 @@ int la_extract_pool(const float* x, const float* qt, int qt_broadcast, int B, in
 int la_extract_fold(const float* q, const float* Wk, int BC, int n, int D, float* qt, void* stream);
 int la_extract_unfold(const float* pooled, const float* Wv, const float* bv, int BC, int n, int D, float* o, void* stream);
 
+/* Training of embedding_extraction = "cross_attention": the backward of the three entry points above, for EmbeddingTransformer.forward in
+ * train mode (prompt_encoder.py:289-313; its query dropout, prompt_encoder.py:301-307, only changes the returned flags and lives on the
+ * host).  Notation for pair z = b C + c: x_l its L = M hw stream rows, j its R = 8 n folded queries.
+ *
+ * la_extract_pool_lse: la_extract_pool - the same kernels, `out` bit-identical - which also writes lse fp32 [B C, R],
+ * lse[z][j] = max_l s_jl + log sum_l exp(s_jl - max) with s_jl = qt_j . x_l, from the merge step.
+ * la_extract_pool_bwd: x, qt (and qt_broadcast) as in the forward, out and lse as the forward left them, dout fp32 [B C, R, D].  With
+ * p_jl = exp(s_jl - lse_j), t_jl = dout_j . x_l, delta_j = dout_j . out_j, ds_jl = p_jl (t_jl - delta_j):
+ *   dx_l = sum_j (p_jl dout_j + ds_jl qt_j) -> dx fp32 [B M C, hw, D] (the layout of x), every row of every slab WRITTEN exactly once with
+ *   plain stores;   dqt_j = sum_l ds_jl x_l -> dqt fp32 [B C, R, D], WRITTEN; with qt_broadcast != 0 dqt is [R, D], the sum of the
+ *   per-pair rows over the pairs in z order.
+ * The four products run on the exact-fp32 MFMA 16x16x4, the exponential is expf; the stream is read once, nothing projected or transposed
+ * is written.  One workgroup per tile of `tile_rows` stream rows of a pair; the dqt partials of the tiles go to `scratch` and a second
+ * small launch adds them in index order: no atomics, every sum has an order fixed by (M, hw, D, R), two runs give the same bits, and a
+ * pair computed alone gives the dx rows and per-pair dqt it gives inside a batch.  la_extract_pool_bwd_plan gives tile_rows, the number
+ * of tiles and the scratch size in floats PER PAIR (scratch holds B C times that).  Sizes as for la_extract_pool: D in {64, 128, 256},
+ * 1 <= n <= 16, any hw, M >= 1; x, qt, dout, scratch, dx 16-byte aligned; anything else is refused with a message and nothing is written.
+ * la_extract_fold_bwd: dqt fp32 [BC, R, D], q fp32 [BC n, D / 2], Wk fp32 [D / 2, D] -> dq fp32 [BC n, D / 2] (WRITTEN; includes the
+ * 1 / sqrt(hd) factor) and dWk [D / 2, D], ADDED to what the buffer holds (the convention of la_gemm_tn and the other parameter
+ * gradients, which accumulate into the flat gradient buffer), each head on its own rows; dbk [D / 2], the k_proj.bias gradient, is
+ * WRITTEN as zero: the key bias is constant along the keys and cancels in the softmax (Attention.forward, common.py:105-146), so every contribution is zero.
+ * la_extract_unfold_bwd: do fp32 [BC n, D / 2], pooled fp32 [BC, R, D], Wv fp32 [D / 2, D] -> dpooled fp32 [BC, R, D] (WRITTEN), dWv
+ * [D / 2, D] and dbv [D / 2] (both ADDED to).  All sums of the two run in index order ((z, j) for the weight gradients). */
+int la_extract_pool_lse(const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n, float* scratch, float* out,
+                        float* lse, void* stream);
+int la_extract_pool_bwd_plan(int M, int hw, int D, int R, int* tile_rows, int* ntiles, long long* scratch_floats_per_pair);
+int la_extract_pool_bwd(const float* x, const float* qt, int qt_broadcast, const float* out, const float* lse, const float* dout, int B, int M,
+                        int C, int hw, int D, int n, float* scratch, float* dx, float* dqt, void* stream);
+int la_extract_fold_bwd(const float* dqt, const float* q, const float* Wk, int BC, int n, int D, float* dq, float* dWk, float* dbk, void* stream);
+int la_extract_unfold_bwd(const float* dov, const float* pooled, const float* Wv, int BC, int n, int D, float* dpooled, float* dWv, float* dbv,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

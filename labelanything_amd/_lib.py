@@ -152,6 +152,11 @@ SIGNATURES = dict(line.split() for line in """
     la_extract_pool                         ppiiiiiiipps
     la_extract_fold                         ppiiips
     la_extract_unfold                       pppiiips
+    la_extract_pool_lse                     ppiiiiiiippps
+    la_extract_pool_bwd_plan                iiiihhh
+    la_extract_pool_bwd                     ppipppiiiiiippps
+    la_extract_fold_bwd                     pppiiippps
+    la_extract_unfold_bwd                   pppiiippps
 """.strip().splitlines())
 EXPORTS = list(SIGNATURES)                  # (tests check the .so exports all of them)
 _CTYPE = {"p": C.c_void_p, "h": C.c_void_p, "s": C.c_void_p, "i": C.c_int, "l": C.c_long, "q": C.c_longlong, "f": C.c_float}
@@ -1100,15 +1105,7 @@ def extract_pool(x, qt, b: int, m: int, c: int, hw: int, d: int, n: int, scratch
     """out [b c, 8 n, d] = softmax-weighted means of the m hw stream rows of every pair under the folded queries qt ([b c, 8 n, d], or
     one [8 n, d] block for all pairs).  scratch: fp32, at least b c times the per-pair size of ``extract_pool_plan``."""
     _f32c(x, qt, scratch, out)
-    r = EXTRACT_HEADS * n
-    bcast = qt.numel() == r * d and b * c != 1
-    if x.numel() != b * m * c * hw * d or out.numel() != b * c * r * d or qt.numel() not in (r * d, b * c * r * d):
-        raise ValueError(f"extract_pool: x must hold [{b * m * c}, {hw}, {d}], qt [{b * c}, {r}, {d}] or [{r}, {d}] and out [{b * c}, {r}, {d}] "
-                         f"elements (got {x.numel()}, {qt.numel()}, {out.numel()})")
-    if 1 <= n <= 16 and d in (64, 128, 256):
-        need = b * c * extract_pool_plan(m, hw, d, r)[2]
-        if scratch.numel() < need:
-            raise ValueError(f"extract_pool: scratch holds {scratch.numel()} floats, {need} needed")
+    bcast = _extract_pool_sizes("extract_pool", x, qt, out, scratch, extract_pool_plan, b, m, c, hw, d, n)
     _call(lib().la_extract_pool, x, qt, 1 if bcast else 0, b, m, c, hw, d, n, scratch, out)
 
 
@@ -1124,3 +1121,62 @@ def extract_unfold(pooled, wv, bv, bc: int, n: int, d: int, o) -> None:
     _f32c(pooled, wv, bv, o)
     _numel("extract_unfold", pooled=(pooled, bc * EXTRACT_HEADS * n * d), wv=(wv, (d // 2) * d), bv=(bv, d // 2), o=(o, bc * n * (d // 2)))
     _call(lib().la_extract_unfold, pooled, wv, bv, bc, n, d, o)
+
+
+# ---- training of the extraction (csrc/extract_bwd.hip) --------------------------------------------------------------------------------
+def _extract_pool_sizes(who: str, x, qt, out, scratch, plan, b: int, m: int, c: int, hw: int, d: int, n: int) -> bool:
+    """The size checks of the three passes over the stream (``plan``: the pass's own scratch plan) -> qt is the broadcast form."""
+    r = EXTRACT_HEADS * n
+    if x.numel() != b * m * c * hw * d or out.numel() != b * c * r * d or qt.numel() not in (r * d, b * c * r * d):
+        raise ValueError(f"{who}: x must hold [{b * m * c}, {hw}, {d}], qt [{b * c}, {r}, {d}] or [{r}, {d}] and out [{b * c}, {r}, {d}] "
+                         f"elements (got {x.numel()}, {qt.numel()}, {out.numel()})")
+    if 1 <= n <= 16 and d in (64, 128, 256):
+        need = b * c * plan(m, hw, d, r)[2]
+        if scratch.numel() < need:
+            raise ValueError(f"{who}: scratch holds {scratch.numel()} floats, {need} needed")
+    return qt.numel() == r * d and b * c != 1
+
+
+def extract_pool_lse(x, qt, b: int, m: int, c: int, hw: int, d: int, n: int, scratch, out, lse) -> None:
+    """``extract_pool`` (the same kernels, ``out`` bit-identical) which also writes lse [b c, 8 n] = max + log(sum) of every folded query's
+    scores: what ``extract_pool_bwd`` rebuilds the softmax weights from."""
+    _f32c(x, qt, scratch, out, lse)
+    bcast = _extract_pool_sizes("extract_pool_lse", x, qt, out, scratch, extract_pool_plan, b, m, c, hw, d, n)
+    _numel("extract_pool_lse", lse=(lse, b * c * EXTRACT_HEADS * n))
+    _call(lib().la_extract_pool_lse, x, qt, 1 if bcast else 0, b, m, c, hw, d, n, scratch, out, lse)
+
+
+def extract_pool_bwd_plan(m: int, hw: int, d: int, r: int):
+    """(tile_rows, ntiles, scratch floats per pair) of ``extract_pool_bwd``: one workgroup per tile of tile_rows stream rows of a pair.  A
+    function of these four sizes only."""
+    rows, nt, per = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _call(lib().la_extract_pool_bwd_plan, m, hw, d, r, C.byref(rows), C.byref(nt), C.byref(per))
+    return rows.value, nt.value, per.value
+
+
+def extract_pool_bwd(x, qt, out, lse, dout, b: int, m: int, c: int, hw: int, d: int, n: int, scratch, dx, dqt) -> None:
+    """dx (the layout of x) and dqt (the layout of qt: [b c, 8 n, d], or [8 n, d] summed over the pairs in the broadcast form) from
+    dout [b c, 8 n, d]; out and lse as ``extract_pool_lse`` left them.  Both are written.  scratch: fp32, at least b c times the
+    per-pair size of ``extract_pool_bwd_plan``."""
+    _f32c(x, qt, out, lse, dout, scratch, dx, dqt)
+    r = EXTRACT_HEADS * n
+    _numel("extract_pool_bwd", lse=(lse, b * c * r), dout=(dout, b * c * r * d), dx=(dx, x.numel()), dqt=(dqt, qt.numel()))
+    bcast = _extract_pool_sizes("extract_pool_bwd", x, qt, out, scratch, extract_pool_bwd_plan, b, m, c, hw, d, n)
+    _call(lib().la_extract_pool_bwd, x, qt, 1 if bcast else 0, out, lse, dout, b, m, c, hw, d, n, scratch, dx, dqt)
+
+
+def extract_fold_bwd(dqt, q, wk, bc: int, n: int, d: int, dq, dwk, dbk) -> None:
+    """dq [bc n, d / 2] is written (with the 1 / sqrt(d / 16) factor), dwk [d / 2, d] is ADDED to, dbk [d / 2] is written as zero (the key
+    bias cancels in the softmax)."""
+    _f32c(dqt, q, wk, dq, dwk, dbk)
+    _numel("extract_fold_bwd", dqt=(dqt, bc * EXTRACT_HEADS * n * d), q=(q, bc * n * (d // 2)), wk=(wk, (d // 2) * d), dq=(dq, bc * n * (d // 2)),
+           dwk=(dwk, (d // 2) * d), dbk=(dbk, d // 2))
+    _call(lib().la_extract_fold_bwd, dqt, q, wk, bc, n, d, dq, dwk, dbk)
+
+
+def extract_unfold_bwd(do, pooled, wv, bc: int, n: int, d: int, dpooled, dwv, dbv) -> None:
+    """dpooled [bc, 8 n, d] is written; dwv [d / 2, d] and dbv [d / 2] are ADDED to."""
+    _f32c(do, pooled, wv, dpooled, dwv, dbv)
+    _numel("extract_unfold_bwd", do=(do, bc * n * (d // 2)), pooled=(pooled, bc * EXTRACT_HEADS * n * d), wv=(wv, (d // 2) * d),
+           dpooled=(dpooled, bc * EXTRACT_HEADS * n * d), dwv=(dwv, (d // 2) * d), dbv=(dbv, d // 2))
+    _call(lib().la_extract_unfold_bwd, do, pooled, wv, bc, n, d, dpooled, dwv, dbv)

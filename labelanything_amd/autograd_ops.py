@@ -18,6 +18,9 @@ index_select, expand); every arithmetic node of the prompt encoder / mask decode
     level_reduce  la_level_reduce                      bwd: la_level_reduce_bwd        (level_reducer over [fine, enlarged coarse])
     proto_kernels la_proto_kernels                     bwd: la_proto_kernels_bwd       (conv_classification: prototype_tconv)
     classify_conv la_classify_conv                     bwd: la_classify_conv_bwd       (conv_classification: 5 x 5 correlation per episode)
+    extract_fold  la_extract_fold                      bwd: la_extract_fold_bwd        (embedding_extraction: q_proj rows -> folded queries)
+    extract_pool  la_extract_pool_lse                  bwd: la_extract_pool_bwd        (embedding_extraction: the pass over the stream)
+    extract_unfold la_extract_unfold                   bwd: la_extract_unfold_bwd      (embedding_extraction: pooled rows -> what out_proj takes)
 
 All tensors are fp32, contiguous, on the device; 2-D activations are [rows, channels] (NHWC rows), as in the inference engine.
 Reference graph: label_anything/models/{common,transformer,prompt_encoder,mask_decoder}.py under experiment/utils.py:266-303.
@@ -721,3 +724,95 @@ def rows_to_planes(x: Tensor, n: int, c: int, hw: int) -> Tensor:
 
 def planes_to_rows(x: Tensor, n: int, c: int, hw: int) -> Tensor:
     return _PlanesToRows.apply(x, n, c, hw)
+
+
+class _ExtractFold(Function):
+    """q [BC n, D / 2] (= q_proj(E)), k_proj weight and bias -> folded queries [BC, 8 n, D] (la_extract_fold).  The bias takes no part
+    in the forward - it cancels in the softmax - and its gradient is the exact zero la_extract_fold_bwd writes, so that the parameter
+    counts as reached, as it is in the reference.  The weight gradient goes straight into the gradient sink when one is installed."""
+
+    @staticmethod
+    def forward(ctx, q, wk, bk, bc, n):
+        q, wk, bk = _c(q), _c(wk), _c(bk)
+        d = wk.shape[1]
+        qt = q.new_empty(bc, L.EXTRACT_HEADS * n, d)
+        L.extract_fold(q, wk, bc, n, d, qt)
+        ctx.save_for_backward(q, wk, bk)
+        ctx.dims = (bc, n, d)
+        return qt
+
+    @staticmethod
+    def backward(ctx, dqt):
+        q, wk, bk = ctx.saved_tensors
+        bc, n, d = ctx.dims
+        dq = torch.empty_like(q)
+        gw, gb = SINK.find(wk), SINK.find(bk)
+        dw = torch.zeros_like(wk) if gw is None else None
+        db = torch.empty_like(bk) if gb is None else None
+        L.extract_fold_bwd(_c(dqt), q, wk, bc, n, d, dq, gw if gw is not None else dw, gb if gb is not None else db)
+        return dq, dw, db, None, None
+
+
+def extract_fold(q: Tensor, wk: Tensor, bk: Tensor, bc: int, n: int) -> Tensor:
+    return _ExtractFold.apply(q, wk, bk, bc, n)
+
+
+class _ExtractPool(Function):
+    """x [B M C hw, D] (slabs in (b, m, c) order), qt [B C, 8 n, D] or one [8 n, D] block for every pair -> pooled [B C, 8 n, D]
+    (la_extract_pool_lse; la_extract_pool_bwd).  Saves x, qt, out and lse; the backward returns dx and dqt in the layouts of x and qt."""
+
+    @staticmethod
+    def forward(ctx, x, qt, b, m, c, hw, n):
+        x, qt = _c(x), _c(qt)
+        d = x.shape[-1]
+        r = L.EXTRACT_HEADS * n
+        out = x.new_empty(b * c, r, d)
+        lse = x.new_empty(b * c, r)
+        scratch = x.new_empty(b * c * L.extract_pool_plan(m, hw, d, r)[2])
+        L.extract_pool_lse(x, qt, b, m, c, hw, d, n, scratch, out, lse)
+        ctx.save_for_backward(x, qt, out, lse)
+        ctx.dims = (b, m, c, hw, d, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, qt, out, lse = ctx.saved_tensors
+        b, m, c, hw, d, n = ctx.dims
+        dx, dqt = torch.empty_like(x), torch.empty_like(qt)
+        scratch = x.new_empty(b * c * L.extract_pool_bwd_plan(m, hw, d, L.EXTRACT_HEADS * n)[2])
+        L.extract_pool_bwd(x, qt, out, lse, _c(dout), b, m, c, hw, d, n, scratch, dx, dqt)
+        return dx, dqt, None, None, None, None, None
+
+
+def extract_pool(x: Tensor, qt: Tensor, b: int, m: int, c: int, hw: int, n: int) -> Tensor:
+    return _ExtractPool.apply(x, qt, b, m, c, hw, n)
+
+
+class _ExtractUnfold(Function):
+    """pooled [BC, 8 n, D], v_proj weight and bias -> o [BC n, D / 2], the recombined heads that out_proj takes (la_extract_unfold).  The
+    parameter gradients go straight into the gradient sink when one is installed."""
+
+    @staticmethod
+    def forward(ctx, pooled, wv, bv, bc, n):
+        pooled, wv, bv = _c(pooled), _c(wv), _c(bv)
+        d = wv.shape[1]
+        o = pooled.new_empty(bc * n, d // 2)
+        L.extract_unfold(pooled, wv, bv, bc, n, d, o)
+        ctx.save_for_backward(pooled, wv, bv)
+        ctx.dims = (bc, n, d)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        pooled, wv, bv = ctx.saved_tensors
+        bc, n, d = ctx.dims
+        dpooled = torch.empty_like(pooled)
+        gw, gb = SINK.find(wv), SINK.find(bv)
+        dw = torch.zeros_like(wv) if gw is None else None
+        db = torch.zeros_like(bv) if gb is None else None
+        L.extract_unfold_bwd(_c(do), pooled, wv, bc, n, d, dpooled, gw if gw is not None else dw, gb if gb is not None else db)
+        return dpooled, dw, db, None, None
+
+
+def extract_unfold(pooled: Tensor, wv: Tensor, bv: Tensor, bc: int, n: int) -> Tensor:
+    return _ExtractUnfold.apply(pooled, wv, bv, bc, n)

@@ -10,6 +10,8 @@
 //   la_extract_fold    q [BC n, D / 2], W_k [D / 2, D]            -> qt [BC, R, D]
 //   la_extract_pool    x [B M C, hw, D], qt [BC, R, D] or [R, D]  -> pooled [BC, R, D]      (the pass over the stream)
 //   la_extract_unfold  pooled, W_v [D / 2, D], b_v                -> o [BC n, D / 2]        (what out_proj takes)
+// la_extract_pool_lse is la_extract_pool that also hands out lse = max + log(sum) per folded query; the backward of all three lives in
+// extract_bwd.hip.
 //
 // NO KEY IS MASKED.  The reference hands the module a key mask built from flag_examples, but with only a key mask Attention.forward
 // builds an all-False score mask (common.py:120-124), so the rows of padded supports take part in the softmax like any others; the
@@ -20,7 +22,7 @@
 // computed in - and every sum has a fixed order: no atomics, two runs give the same bits.
 //
 // MFMA 16x16x4 f32 operand layout (lane l, q = l / 16, n = l % 16): A[row n][k q], B[k q][col n], D register r = [row 4 q + r][col n].
-#include "la_common.h"
+#include "extract_shared.h"
 #include "../../include/la_hip.h"
 
 #include <cmath>
@@ -28,12 +30,8 @@
 
 namespace la {
 
-__device__ __forceinline__ f32x4 ex_mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float ex_comp(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
-
 constexpr int EX_TK = 64;                 // stream rows per LDS tile: 16 per wave
 constexpr int EX_SPLIT = 4 * EX_TK;       // stream rows per workgroup
-constexpr int EX_HEADS = 8;
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // One workgroup = one piece of EX_SPLIT rows of one pair z = (b, c) and one chunk of RT row tiles (16 folded queries each).  The four
@@ -215,8 +213,9 @@ __global__ __launch_bounds__(256) void extract_pool_kernel(const float* __restri
 }
 
 // out[z][j][:] = sum_s w_s acc_s / sum_s w_s sum_s with w_s = exp(max_s - max), pieces in index order.  One workgroup per (row, pair).
+// lse (la_extract_pool_lse; null otherwise): lse[z][j] = max + log(sum), what the backward rebuilds the weights from.
 __global__ void extract_merge_kernel(const float* __restrict__ pacc, const float* __restrict__ pms, int nsplit, int RP, int D, int R,
-                                     float* __restrict__ out) {
+                                     float* __restrict__ out, float* __restrict__ lse) {
   const int j = blockIdx.x, z = blockIdx.y, d = threadIdx.x;
   const size_t base = (size_t)z * nsplit * RP + j;
   float mg = pms[base * 2];
@@ -229,6 +228,7 @@ __global__ void extract_merge_kernel(const float* __restrict__ pacc, const float
     den += w * pms[o * 2 + 1];
   }
   out[((size_t)z * R + j) * D + d] = num / den;
+  if (lse != nullptr && d == 0) lse[(size_t)z * R + j] = mg + logf(den);
 }
 
 // qt[z][h n + j][f] = (sum_e q[z n + j][h hd + e] W_k[h hd + e][f]) / sqrt(hd): e in index order, one thread per output channel
@@ -269,20 +269,6 @@ template <int D, int RT> static void launch_pool(const float* x, const float* qt
 
 }  // namespace la
 
-static bool ex_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-static bool extract_sizes_ok(const char* who, int D, int n) {
-  if (D != 64 && D != 128 && D != 256) {
-    la_set_error("%s: D=%d must be 64, 128 or 256", who, D);
-    return false;
-  }
-  if (n < 1 || n > 16) {
-    la_set_error("%s: n=%d queries per pair must be 1..16", who, n);
-    return false;
-  }
-  return true;
-}
-
 // row tiles of 16 folded queries, in chunks of two per workgroup (one when a single tile holds them all)
 static void extract_tiles(int R, int* rt, int* nchunk, int* RP) {
   const int ntile = (R + 15) / 16;
@@ -304,14 +290,15 @@ extern "C" int la_extract_pool_plan(int M, int hw, int D, int R, int* split_rows
   return 0;
 }
 
-extern "C" int la_extract_pool(const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n, float* scratch,
-                               float* out, void* stream) {
-  LA_CHECK_ARG(x && qt && scratch && out, "la_extract_pool: null pointer");
-  if (!extract_sizes_ok("la_extract_pool", D, n)) return -1;
+// la_extract_pool and la_extract_pool_lse: the same two launches; lse == nullptr: the merge writes no statistics
+static int extract_pool_impl(const char* who, const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n,
+                             float* scratch, float* out, float* lse, void* stream) {
+  LA_CHECK_ARG(x && qt && scratch && out, "%s: null pointer", who);
+  if (!extract_sizes_ok(who, D, n)) return -1;
   LA_CHECK_ARG(B >= 1 && C >= 1 && M >= 1 && hw >= 1 && (long long)B * C <= 65535 && (long long)M * hw <= (1ll << 30) &&
                    (long long)B * M * C * hw <= (1ll << 31) - 1,
-               "la_extract_pool: bad sizes B=%d M=%d C=%d hw=%d (B C 1..65535, M hw up to 2^30, B M C hw below 2^31)", B, M, C, hw);
-  LA_CHECK_ARG(ex_al16(x) && ex_al16(qt) && ex_al16(scratch), "la_extract_pool: 16-byte aligned x / qt / scratch");
+               "%s: bad sizes B=%d M=%d C=%d hw=%d (B C 1..65535, M hw up to 2^30, B M C hw below 2^31)", who, B, M, C, hw);
+  LA_CHECK_ARG(ex_al16(x) && ex_al16(qt) && ex_al16(scratch), "%s: 16-byte aligned x / qt / scratch", who);
   const int R = la::EX_HEADS * n, BC = B * C;
   int rt, nchunk, RP;
   extract_tiles(R, &rt, &nchunk, &RP);
@@ -334,10 +321,21 @@ extern "C" int la_extract_pool(const float* x, const float* qt, int qt_broadcast
   else
     LA_EX_LAUNCH(256);
 #undef LA_EX_LAUNCH
-  LA_CHECK_LAUNCH("la_extract_pool");
-  hipLaunchKernelGGL(la::extract_merge_kernel, dim3(R, BC), dim3(D), 0, st, pacc, pms, nsplit, RP, D, R, out);
-  LA_CHECK_LAUNCH("la_extract_pool (merge)");
+  LA_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(la::extract_merge_kernel, dim3(R, BC), dim3(D), 0, st, pacc, pms, nsplit, RP, D, R, out, lse);
+  LA_CHECK_LAUNCH(who);
   return 0;
+}
+
+extern "C" int la_extract_pool(const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n, float* scratch,
+                               float* out, void* stream) {
+  return extract_pool_impl("la_extract_pool", x, qt, qt_broadcast, B, M, C, hw, D, n, scratch, out, nullptr, stream);
+}
+
+extern "C" int la_extract_pool_lse(const float* x, const float* qt, int qt_broadcast, int B, int M, int C, int hw, int D, int n, float* scratch,
+                                   float* out, float* lse, void* stream) {
+  LA_CHECK_ARG(lse != nullptr, "la_extract_pool_lse: null pointer");
+  return extract_pool_impl("la_extract_pool_lse", x, qt, qt_broadcast, B, M, C, hw, D, n, scratch, out, lse, stream);
 }
 
 extern "C" int la_extract_fold(const float* q, const float* Wk, int BC, int n, int D, float* qt, void* stream) {

@@ -154,6 +154,7 @@ class Lam(nn.Module):
         self.norm_fold = True            # A/B switch: False keeps the LayerNorm kernels where the engine would fold them into the GEMMs (LamEngine.norm_fold)
         self.attn_fp8 = False            # opt-in: fp8 (e4m3) QK^T in the HF encoder's attention (BASELINE configs[4]); outside the 1e-3 tolerance
         self.selected_rows: Optional[torch.Tensor] = None   # fix the RandomMatrixEncoder rows (parity / reproducibility)
+        self.extraction_keep: Optional[torch.Tensor] = None # fix the training-time query dropout of embedding_extraction (bool [n]; parity)
 
     # -- engine management --------------------------------------------------------------------------
     def _device(self) -> torch.device:

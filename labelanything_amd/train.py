@@ -12,7 +12,9 @@ directions, torch.autograd records the graph and moves data.  The image encoder 
 Parameters that the forward never touches (``prompt_encoder.transformer.final_attn_token_to_image``, ``norm_final_attn``: dead in
 the reference too, which therefore needs ``find_unused_parameters``) keep the zeros of the flat gradient buffer.  With
 ``prompt_encoder="TokenPool"`` the example embeddings are that transformer's output tokens and both are live.  With
-``fusion_transformer="OneWayTransformer"`` the mask decoder's ``norm3`` tensors are dead in the same way.
+``fusion_transformer="OneWayTransformer"`` the mask decoder's ``norm3`` tensors are dead in the same way, and so are the ``norm3`` tensors
+of the two ``embedding_extraction="cross_attention"`` layers.  That option trains with ``LamTrainer(..., embedding_dropout=p)``: the
+reference's train-mode query dropout (prompt_encoder.py:301-307) is ``draw_extraction_keep`` on the host.
 """
 from __future__ import annotations
 
@@ -102,6 +104,16 @@ class _AddPerGroup(Function):
             L.colmean(g.contiguous(), groups, rep, d, dy, g.new_empty(groups, L.COLMEAN_SPLIT, d))
             dy = dy * float(rep)
         return g, dy, None, None
+
+
+def draw_extraction_keep(n: int, p: float) -> Tensor:
+    """The reference's train-mode dropout of the n learned extraction queries (EmbeddingTransformer.forward, prompt_encoder.py:301-305) on
+    the host generator: ``torch.rand(n) > p``, and if nothing survives one index from ``torch.randint(0, n, (1,))`` -> bool [n].  The same
+    draws in the same order, so that a seeded run keeps the queries the reference keeps."""
+    keep = torch.rand(n) > p
+    if not bool(keep.any()):
+        keep[int(torch.randint(0, n, (1,)).item())] = True
+    return keep
 
 
 class DecoderGraph:
@@ -240,8 +252,29 @@ class DecoderGraph:
                                self.w[pe_ + ".pe_layer.positional_encoding_gaussian_matrix"])
         return sp, ns
 
+    def extract_embeddings(self, stream: Tensor, b: int, m: int, c: int, hw: int) -> Tensor:
+        """embedding_extraction = "cross_attention" (EmbeddingTransformer.forward, prompt_encoder.py:289-298): the n learned queries of
+        every (b, c) pair through two OneWayAttentionBlocks (transformer.py:140-154; query_pe zero, ReLU, norm3 never applied, no key
+        masked) over the pair's M hw rows of ``stream`` [B M C hw, D] -> (B, n, C, D).  Between q_proj and out_proj a layer is
+        fold -> pool -> unfold (csrc/extract.hip); layer 0's queries are the same for every pair, so they are projected and folded once and
+        pooled in the broadcast form, whose backward sums dqt over the pairs.  Both layers read the stream: autograd adds their dx."""
+        ex = "prompt_encoder.embedding_extraction"
+        d, n = self.cfg.embed_dim, int(self.cfg.embeddings_per_example)
+        bc = b * c
+        e = self.w[ex + ".embeddings.weight"]                                     # (n, D); "(b c) n d" rows from layer 0's residual on
+        for l in range(2):
+            lp = f"{ex}.layers.{l}"
+            ca = lp + ".cross_attn_image_to_token"
+            qt = A.extract_fold(self.lin(ca + ".q_proj", e), self.w[ca + ".k_proj.weight"], self.w[ca + ".k_proj.bias"], 1 if l == 0 else bc, n)
+            pooled = A.extract_pool(stream, qt[0] if l == 0 else qt, b, m, c, hw, n)
+            o = A.extract_unfold(pooled, self.w[ca + ".v_proj.weight"], self.w[ca + ".v_proj.bias"], bc, n)
+            e = self.ln(lp + ".norm1", A.add_rows(self.lin(ca + ".out_proj", o), e), 1e-5)
+            h = self.lin(lp + ".mlp.lin2", A.relu(self.lin(lp + ".mlp.lin1", e)))
+            e = self.ln(lp + ".norm2", A.add_rows(e, h), 1e-5)
+        return e.view(b, c, n, d).permute(0, 2, 1, 3).contiguous()
+
     def prompt_encoder(self, support: Tensor, b: int, m: int, g: int, points, boxes, masks, flag_examples: Tensor,
-                       selected_rows: Optional[Tensor]) -> Dict[str, Tensor]:
+                       selected_rows: Optional[Tensor], extraction_keep: Optional[Tensor] = None) -> Dict[str, Tensor]:
         cfg = self.cfg
         pe_ = "prompt_encoder"
         d, hw = cfg.embed_dim, g * g
@@ -278,6 +311,16 @@ class DecoderGraph:
             src = _AddPerGroup.apply(src, ce.repeat(b * m, 1), p, hw)
         pos = self.dense_pe(g)
         _, keys = self.two_way(pe_ + ".transformer", src, pos, sp, p, ns, hw, want_tokens=False)
+        if cfg.embedding_extraction == "cross_attention":
+            # prompt_encoder.py:299-313: a query of class c is valid when any support shows the class and, in train mode, when the
+            # dropout kept it; there is no class mean.  Dropped queries still enter the mask decoder's transformer as tokens: the flags
+            # only leave them out of the per-class maximum (la_classify_max)
+            emb = self.extract_embeddings(keys, b, m, c, hw)
+            n = emb.shape[1]
+            flags = (flag_examples.reshape(b, m, c) != 0).any(dim=1, keepdim=True).expand(b, n, c)
+            if extraction_keep is not None:
+                flags = flags & extraction_keep.to(flags.device).view(1, n, 1)
+            return {"class_examples_embeddings": emb, "class_examples_src": keys, "flag_examples": flags.to(torch.uint8).contiguous()}
         k = cfg.pool_side
         if k > 1:
             # embeddings_per_example > 1 (prompt_encoder.py:726-731): the M k k region means are examples of their own from here on
@@ -397,8 +440,9 @@ class DecoderGraph:
         query = ev[:, 0].reshape(b * hw, d)
         support = ev[:, 1:].reshape(b * (n - 1) * hw, d)
         points, boxes, masks = Lam._prompts_of(inp)
-        pe = self.prompt_encoder(support, b, n - 1, g, points, boxes, masks, inp["flag_examples"], inp.get("selected_rows"))
-        seg = self.mask_decoder(query.contiguous(), b, g, pe["class_embeddings"], pe["class_examples_embeddings"], pe["flag_examples"])
+        pe = self.prompt_encoder(support, b, n - 1, g, points, boxes, masks, inp["flag_examples"], inp.get("selected_rows"),
+                                 inp.get("extraction_keep"))
+        seg = self.mask_decoder(query.contiguous(), b, g, pe.get("class_embeddings"), pe["class_examples_embeddings"], pe["flag_examples"])
         fg = inp.get("flag_gts")
         if cfg.segment_example_logits:       # classes without a valid example: -inf at full resolution too (LamEngine.example_valid)
             valid = (pe["flag_examples"] != 0).any(dim=1)
@@ -414,7 +458,7 @@ class LamTrainer:
 
     def __init__(self, lam: Lam, lr: float = 5e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  num_warmup_steps: int = 0, loss=None, train_encoder: bool = False,
-                 backbone_lr: Optional[float] = None, encoder_buckets: int = 4):
+                 backbone_lr: Optional[float] = None, encoder_buckets: int = 4, embedding_dropout: Optional[float] = None):
         """backbone_lr: learning rate of the ``image_encoder.*`` tensors (the reference's ``backbone_lr`` parameter group,
         models/lam.py:340-346; needs train_encoder=True - with a frozen backbone the reference raises as well).
         train_encoder=False: ``get_learnable_params({'freeze_backbone': True})`` - the image encoder is frozen (and absent from
@@ -426,17 +470,31 @@ class LamTrainer:
         (train_encoder.py: ``HfEncoderGraph`` / ``SamEncoderGraph``).
         loss: ``FocalLossDevice`` (default: focal, weight 1, class weighting) or a ``loss.LabelAnythingLoss``; the latter is moved to the
         model's device and its parameters (prompt_contrastive's t_prime / bias) train with the decoder's learning rate and weight
-        decay, as ``WrapperModule.get_learnable_params`` appends them to the optimizer (experiment/utils.py:290-295)."""
+        decay, as ``WrapperModule.get_learnable_params`` appends them to the optimizer (experiment/utils.py:290-295).
+        embedding_dropout: for a model with ``embedding_extraction``, and required there: the probability with which train mode drops
+        each learned query from the per-class maximum (``draw_extraction_keep``, once per ``forward_backward``; the reference's constant
+        is 0.2, prompt_encoder.py:287; 0.0 keeps every query).  ``lam.extraction_keep`` (bool [n]) pins the mask instead of drawing it."""
         if float(getattr(lam.cfg, "dropout", 0.0) or 0.0) != 0.0:
             # the reference trains with nn.Dropout(p) inside MLPBlock / AttentionMLPBlock when it is set (models/common.py:25-32,68-75,
             # build_lam.py:128); the training graph here has no dropout node, so training such a model would silently be a different model
             raise NotImplementedError(f"dropout={lam.cfg.dropout} is not built into the training graph (every canonical parameters/*.yaml "
                                       f"leaves it at 0); build the model with dropout=0.0 to train it here")
-        if lam.cfg.embedding_extraction is not None:
-            # no reference recipe trains it here, in train mode the reference drops learned queries with host-side random draws
-            # (prompt_encoder.py:301-307), and la_extract_pool has no backward
-            raise NotImplementedError(f"embedding_extraction={lam.cfg.embedding_extraction!r} is an inference configuration here: its "
-                                      f"training graph (the backward of la_extract_pool, the reference's embedding dropout) is not built")
+        if lam.cfg.embedding_extraction is None:
+            if embedding_dropout is not None:
+                raise ValueError("embedding_dropout is the query dropout of embedding_extraction: this model has no extraction")
+        else:
+            if embedding_dropout is None:
+                # in train mode the reference drops learned queries with host-side random draws (prompt_encoder.py:301-307): training is
+                # a different function from inference, so the caller says so
+                raise NotImplementedError(f"embedding_extraction={lam.cfg.embedding_extraction!r} trains with the reference's query dropout: "
+                                          f"pass embedding_dropout (the reference's constant is 0.2; 0.0 keeps every query)")
+            if not 0.0 <= float(embedding_dropout) < 1.0:
+                raise ValueError(f"embedding_dropout={embedding_dropout} must lie in [0, 1)")
+            if isinstance(loss, LabelAnythingLoss) and len(loss.prompt_components):
+                # the contrastive term pairs the examples of a class across supports; here the "examples" are learned queries, and nobody
+                # has checked what the reference's pairing means for them
+                raise NotImplementedError("the prompt_contrastive loss component is not built for embedding_extraction (its pairing of "
+                                          "learned queries is unchecked); train it without that component")
         if lam.cfg.pool_side > 1 and isinstance(loss, LabelAnythingLoss) and len(loss.prompt_components):
             # the contrastive term pairs the examples of a class across supports; with k x k region embeddings per support the reference's
             # pairing treats the bins of ONE support as independent positives, which nobody has checked here
@@ -446,6 +504,7 @@ class LamTrainer:
         if lam._device().type != "cuda":
             raise RuntimeError("LamTrainer needs the model on an MI355X (there is no CPU path)")
         self.lam = lam
+        self.embedding_dropout = None if embedding_dropout is None else float(embedding_dropout)
         self.train_encoder = bool(train_encoder)
         if self.train_encoder and lam.cfg.encoder_spec is None:
             raise ValueError("train_encoder=True needs a model with an image encoder")
@@ -465,6 +524,8 @@ class LamTrainer:
             dead = ()
         if lam.cfg.one_way:         # norm3 of a OneWayAttentionBlock is a parameter its forward never applies (transformer.py:138,140-154)
             dead = dead + tuple(f"mask_decoder.transformer.layers.{l}.norm3." for l in range(2))
+        if lam.cfg.embedding_extraction is not None:        # the extraction's two layers are OneWayAttentionBlocks too
+            dead = dead + tuple(f"prompt_encoder.embedding_extraction.layers.{l}.norm3." for l in range(2))
         if isinstance(loss, LabelAnythingLoss):
             loss.to(lam._device())
             loss_named = [("loss." + k, p) for k, p in loss.named_parameters()]
@@ -566,6 +627,14 @@ class LamTrainer:
                 inp, _ = lam._prepare(batch, with_post=False, eng=self.engine)
                 if "flag_gts" in batch:
                     inp["flag_gts"] = batch["flag_gts"].to(lam._device())
+                keep = None
+                if self.embedding_dropout is not None:      # one draw per forward, as in the reference; a pinned mask wins
+                    nq = int(lam.cfg.embeddings_per_example)
+                    keep = lam.extraction_keep if lam.extraction_keep is not None else draw_extraction_keep(nq, self.embedding_dropout)
+                    keep = torch.as_tensor(keep, dtype=torch.bool).reshape(-1).cpu()
+                    if keep.numel() != nq or not bool(keep.any()):
+                        raise ValueError(f"extraction_keep must be a bool mask over the {nq} learned queries with at least one kept")
+                    inp["extraction_keep"] = keep.to(lam._device())
                 eng = self.engine
                 through_encoder = False
                 if "embeddings" in inp:
@@ -602,8 +671,12 @@ class LamTrainer:
                 for i in range(len(self.reducer.bounds)):
                     if not self.reducer.launched(i):
                         self.reducer.launch(i)
-        return {"loss": loss.detach(), "loss_components": components, "logits": out["logits"].detach(),
-                "class_examples_embeddings": out["class_examples_embeddings"].detach()}
+        res = {"loss": loss.detach(), "loss_components": components, "logits": out["logits"].detach(),
+               "class_examples_embeddings": out["class_examples_embeddings"].detach()}
+        if keep is not None:
+            res["extraction_keep"] = keep
+            res["flag_examples"] = out["flag_examples"]
+        return res
 
     def zero_grad(self) -> None:
         self.opt.zero_grad()

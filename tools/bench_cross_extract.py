@@ -15,6 +15,19 @@ episodes / s of ``Lam.forward`` (HIP graph replay) from cached embeddings for th
 embeddings_per_example = 4 model of tools/bench_multi_embedding.py, 1-way 5-shot.  One JSON line per measurement goes to --out.
 
     python tools/bench_cross_extract.py [--iters 50] [--repeats 7]
+
+--train measures the training side instead, on the recipe shape (480 px, 30 x 30 grid, D = 256, 4 queries, 768-channel embeddings, 2-way
+5-shot: M = 5, C = 3 with the background), --train-batch episodes per step:
+
+  pool / pool_lse / pool_bwd   la_extract_pool, la_extract_pool_lse and la_extract_pool_bwd per layer (per-pair queries), with the bytes
+                               la_extract_pool_bwd moves - the stream read once, dx written once, the dqt partials (R / 64 of the stream)
+                               written and read back - against the 8 TB/s HBM roof, and its 10 R D FLOP per stream row against the MFMA roof;
+  module                       the two-layer extraction module forward + backward: the training graph's nodes (DecoderGraph.extract_embeddings)
+                               beside the restatement of tests/cross_extract_ref.py in stock PyTorch eager fp32 on the same GPU, in its
+                               folded and its literal form - the comparison target, since the option had no training path before;
+  step                         LamTrainer.step of the whole model (embedding_dropout = 0.2) from precomputed embeddings.
+
+    python tools/bench_cross_extract.py --train [--out profiles/cross_extract_train_bench.jsonl]
 """
 import argparse
 import dataclasses
@@ -108,16 +121,128 @@ def bench_forward(iters, repeats, batch_size):
     return out
 
 
+def bench_train_kernels(b, m, c, iters, repeats):
+    hw, r = G * G, HEADS * N
+    bc = b * c
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(b * m * c, hw, D, generator=g).cuda()
+    qt = (torch.randn(bc, r, D, generator=g) * (4.3 / math.sqrt(D))).cuda()
+    dout = torch.randn(bc, r, D, generator=g).cuda()
+    out, lse = torch.empty(bc, r, D, device="cuda"), torch.empty(bc, r, device="cuda")
+    dx, dqt = torch.empty_like(x), torch.empty_like(qt)
+    scratch = torch.empty(bc * L.extract_pool_plan(m, hw, D, r)[2], device="cuda")
+    rows, nt, per = L.extract_pool_bwd_plan(m, hw, D, r)
+    scratch_b = torch.empty(bc * per, device="cuda")
+    t = alternate({"pool": lambda: L.extract_pool(x, qt, b, m, c, hw, D, N, scratch, out),
+                   "pool_lse": lambda: L.extract_pool_lse(x, qt, b, m, c, hw, D, N, scratch, out, lse),
+                   "pool_bwd": lambda: L.extract_pool_bwd(x, qt, out, lse, dout, b, m, c, hw, D, N, scratch_b, dx, dqt)}, iters, repeats)
+    nrows = b * m * c * hw
+    med = statistics.median(t["pool_bwd"]) * 1e-6
+    moved = nrows * 4 * D * 2 + 2 * bc * nt * r * D * 4                     # x in, dx out, the dqt partials out and in
+    return {"what": "extract_pool_bwd", "shape": dict(b=b, m=m, c=c, g=G, d=D, n=N, rows_per_pair=m * hw, tile_rows=rows, tiles_per_pair=nt,
+                                                      workgroups=nt * bc),
+            "pool": stats(t["pool"]), "pool_lse": stats(t["pool_lse"]), "pool_bwd": stats(t["pool_bwd"]),
+            "bwd_over_fwd": round(statistics.median(t["pool_bwd"]) / statistics.median(t["pool"]), 3),
+            "bwd_bytes_moved": moved, "bwd_GBps": round(moved / med / 1e9, 1), "bwd_fraction_of_hbm_roof": round(moved / med / HBM_BPS, 4),
+            "bwd_TFLOPs": round(nrows * 10 * r * D / med / 1e12, 2),
+            "bwd_fraction_of_fp32_mfma_roof": round(nrows * 10 * r * D / med / MFMA_F32_FLOPS, 4)}
+
+
+def bench_train_model(batch_size, iters, repeats):
+    from labelanything_amd.config import LamConfig
+    from labelanything_amd.episodes import make_episode
+    from labelanything_amd.models import Lam
+    from labelanything_amd.train import DecoderGraph, LamTrainer
+    from tests import cross_extract_ref as R
+    from tests.helpers import make_gt
+    cfg = LamConfig(encoder=None, use_vit=False, image_size=480, image_embed_dim=768, embed_dim=256, spatial_convs=3,
+                    class_attention=False, example_attention=False, example_class_attention=False, custom_preprocess=False,
+                    segment_example_logits=True, embeddings_per_example=N, embedding_extraction="cross_attention")
+    lam = Lam(cfg, seed=3).cuda()
+    batch = make_episode(batch=batch_size, n_ways=2, k_shots=5, image_size=480, seed=5, prompts=("mask",), embeddings_channels=768, grid=G)
+    b, m, c = batch["flag_examples"].shape
+    gt = make_gt(batch, c, seed=17)
+    # the module alone, forward + backward, on a stream of the step's shape
+    ex = R.PRE + "."
+    names = [k for k, _ in lam.named_parameters() if k.startswith(ex)]
+    params = dict(lam.named_parameters())
+    for k in names:
+        params[k].requires_grad_(True)
+    hw = G * G
+    x = torch.randn(b * m * c * hw, D, generator=torch.Generator().manual_seed(17)).cuda().requires_grad_(True)
+    wout = torch.randn(b, N, c, D, generator=torch.Generator().manual_seed(18)).cuda()
+    graph = DecoderGraph(lam)
+    w = {k: params[k] for k in names}
+
+    def clear():
+        x.grad = None
+        for k in names:
+            params[k].grad = None
+
+    def ours():
+        clear()
+        (graph.extract_embeddings(x, b, m, c, hw) * wout).sum().backward()
+
+    def eager(form):
+        def run():
+            clear()
+            (R.extract(x.view(b * m * c, hw, D), b, m, c, w, form) * wout).sum().backward()
+        return run
+
+    ours()
+    mine = x.grad.clone()
+    eager("folded")()
+    agree = float((mine - x.grad).abs().max() / x.grad.abs().max())
+    t = alternate({"ours": ours, "eager_folded": eager("folded"), "eager_literal": eager("literal")}, max(1, iters // 5), repeats)
+    clear()
+    for k in names:
+        params[k].requires_grad_(False)
+    rec = [{"what": "extraction_module_forward_backward", "shape": dict(b=b, m=m, c=c, g=G, d=D, n=N), "dx_vs_eager_rel_diff": agree,
+            "ours": stats(t["ours"]), "eager_folded": stats(t["eager_folded"]), "eager_literal": stats(t["eager_literal"]),
+            "eager_folded_over_ours": round(statistics.median(t["eager_folded"]) / statistics.median(t["ours"]), 3),
+            "eager_literal_over_ours": round(statistics.median(t["eager_literal"]) / statistics.median(t["ours"]), 3)}]
+    tr = LamTrainer(lam, embedding_dropout=0.2)
+    dev_batch = {k: (v.cuda() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+    for _ in range(3):
+        tr.step(dev_batch, gt)
+    torch.cuda.synchronize()
+    us = [window(lambda: tr.step(dev_batch, gt), max(1, iters // 10)) for _ in range(repeats)]
+    rec.append({"what": "training_step", "model": "x4: embedding_extraction=cross_attention, 4 queries, embedding_dropout 0.2",
+                "episodes_per_step": batch_size, "n_ways": 2, "k_shots": 5, "image_size": 480, "step": stats(us),
+                "episodes_per_s_median": round(batch_size / (statistics.median(us) * 1e-6), 2)})
+    return rec, (b, m, c)
+
+
+def main_train(a):
+    lines = [{"what": "box", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "iters": a.iters, "repeats": a.repeats}]
+    recs, (b, m, c) = bench_train_model(a.train_batch, a.iters, a.repeats)
+    lines.append(bench_train_kernels(b, m, c, a.iters, a.repeats))
+    lines += recs
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "cross_extract_train_bench.jsonl")
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as fh:
+        for rec in lines:
+            print(json.dumps(rec), flush=True)
+            fh.write(json.dumps(rec) + "\n")
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "cross_extract_bench.jsonl")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--forward-batch", type=int, default=8)
     ap.add_argument("--forward-iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cross_extract_bench.jsonl"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--train", action="store_true", help="measure the training side (la_extract_pool_bwd, the module, the whole step)")
+    ap.add_argument("--train-batch", type=int, default=2, help="episodes per training step")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_cross_extract needs an MI355X: there is nothing to measure on the CPU")
+    if a.train:
+        return main_train(a)
     lines = [{"what": "box", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "iters": a.iters, "repeats": a.repeats}]
     for s in SHAPES:
         lines.append(bench_shape(s, a.iters, a.repeats))
