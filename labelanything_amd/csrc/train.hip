@@ -1234,6 +1234,8 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const TS* __restrict__
   const int c0 = blockIdx.y * 64;
   const int tid = threadIdx.x;
   float sa = 0.f, sb = 0.f;
+  // 16-byte source loads: 16-bit rows whose every start is 16-byte aligned (the base address AND the row stride; c0 + cb is a multiple of 16)
+  const bool vec = sizeof(TS) == 2 && (ld % 8) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
   for (int rt = 0; rt < rtiles; ++rt) {
     const int r0 = (blockIdx.x * rtiles + rt) * 64;
     if (r0 >= Rp) break;
@@ -1241,7 +1243,7 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const TS* __restrict__
       const int r = tid >> 2, cb = (tid & 3) * 16;
       const int rr = r0 + r;
       TD v[16];
-      if (rr < R && c0 + cb + 15 < Cn && (ld % 8) == 0 && sizeof(TS) == 2) {
+      if (vec && rr < R && c0 + cb + 15 < Cn) {
         const uint4 a = *reinterpret_cast<const uint4*>(src + (size_t)rr * ld + c0 + cb);
         const uint4 b2 = *reinterpret_cast<const uint4*>(src + (size_t)rr * ld + c0 + cb + 8);
         *reinterpret_cast<uint4*>(&v[0]) = a;

@@ -18,7 +18,6 @@ LIB_NAMES = {"L", "_lib"}                 # the names the GPU test modules bind 
 # entry point -> the test that exercises it through the product's own Python layer (optimizer, loss, image / annotation preparation,
 # an autograd node) and neither calls the wrapper itself nor names the symbol in its docstring
 EXEMPT = {
-    "la_adamw_step": "test_optim_gpu.py::test_flat_adamw_tracks_torch_adamw_with_warmup",
     "la_bilinear_rows_bwd_set": "test_ops_gpu.py::test_bilinear_on_nhwc_rows_forward_and_backward",
     "la_error_count": "test_substitution_gpu.py::test_sampler_multi_tile_against_host",
     "la_error_points": "test_substitution_gpu.py::test_sampler_reproduces_the_reference_draws",
