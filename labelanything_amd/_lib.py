@@ -413,6 +413,9 @@ def gemm_fused_act_ok(m: int, n: int, k: int) -> bool:
 def layernorm(x: torch.Tensor, gamma, beta, eps: float, *, x2=None, gelu=False, out32=None, out16=None,
               out16_pe=None, pe=None, pe_mod=0, window=0, H=0, W=0, dt=LA_F16) -> None:
     rows, e = x.shape[0], x.shape[1]
+    if x2 is not None and (x2.shape[1] != e or x2.stride(1) != 1 or x2.stride(0) != x.stride(0)):
+        # the kernel walks x and x2 with ONE row stride: a contiguous x2 beside a column slice x would be read at the wrong rows
+        raise RuntimeError(f"layernorm: x2 must have the row stride of x ({x.stride(0)}), got {x2.stride(0)}")
     if window < 0:
         # padded-map forms (LA_MAP_CONV3X3 operand layout): -1 writes the 16-bit output into the interior of [B, H + 2, W + 2] maps, -2 reads
         # the input rows from that layout; ``rows`` counts the UN-padded pixels either way
