@@ -812,6 +812,16 @@ int la_extract_fold_bwd(const float* dqt, const float* q, const float* Wk, int B
 int la_extract_unfold_bwd(const float* dov, const float* pooled, const float* Wv, int BC, int n, int D, float* dpooled, float* dWv, float* dbv,
                           void* stream);
 
+/* ---- rotary position embedding of the DINOv3 ViT (transformers DINOv3ViTAttention / apply_rotary_pos_emb) ----
+ * la_rope_qk: rotates, IN PLACE, the q and k columns of the packed 16-bit q | k | v buffer qkv [rows, ld] (ld >= 3 ea, ea = heads * hdp,
+ * head h of q at column h * hdp, of k at ea + h * hdp).  rows = whole images of `tokens` rows; the first `prefix` rows of an image (CLS and
+ * register tokens) are not rotated, patch row prefix + i takes row i of the tables.  Within a head only the real hd columns are rotated:
+ * with x1 = x[:hd / 2], x2 = x[hd / 2:]   x <- x * cos + (-x2 | x1) * sin, in fp32, rounded once to the storage type.  cosw, sinw: fp32
+ * [tokens - prefix, hd].  Prefix rows, the columns hd .. hdp of every head, the v block and anything beyond 3 ea are neither read nor
+ * written.  hd % 16 == 0, hdp % 8 == 0, ld % 8 == 0, qkv and the tables 16-byte aligned (16-byte vector loads and stores only). */
+int la_rope_qk(void* qkv, long rows, int ld, int tokens, int prefix, int heads, int hd, int hdp, const float* cosw, const float* sinw, int dt,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

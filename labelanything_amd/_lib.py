@@ -157,6 +157,7 @@ SIGNATURES = dict(line.split() for line in """
     la_extract_pool_bwd                     ppipppiiiiiippps
     la_extract_fold_bwd                     pppiiippps
     la_extract_unfold_bwd                   pppiiippps
+    la_rope_qk                              pliiiiiippis
 """.strip().splitlines())
 EXPORTS = list(SIGNATURES)                  # (tests check the .so exports all of them)
 _CTYPE = {"p": C.c_void_p, "h": C.c_void_p, "s": C.c_void_p, "i": C.c_int, "l": C.c_long, "q": C.c_longlong, "f": C.c_float}
@@ -1183,3 +1184,18 @@ def extract_unfold_bwd(do, pooled, wv, bc: int, n: int, d: int, dpooled, dwv, db
     _numel("extract_unfold_bwd", do=(do, bc * n * (d // 2)), pooled=(pooled, bc * EXTRACT_HEADS * n * d), wv=(wv, (d // 2) * d),
            dpooled=(dpooled, bc * EXTRACT_HEADS * n * d), dwv=(dwv, (d // 2) * d), dbv=(dbv, d // 2))
     _call(lib().la_extract_unfold_bwd, do, pooled, wv, bc, n, d, dpooled, dwv, dbv)
+
+
+# ---- rotary position embedding (DINOv3 ViT) -----------------------------------------------------------------
+def rope_qk(qkv, tokens: int, prefix: int, heads: int, hd: int, hdp: int, cos, sin) -> None:
+    """Rotate, in place, the q and k columns of the packed 16-bit q | k | v buffer qkv [rows, >= 3 heads hdp] (row stride = ld): the rows
+    of every image of ``tokens`` rows from ``prefix`` on, the first hd of the hdp columns of every head, by the fp32 tables cos, sin
+    [tokens - prefix, hd].  Everything else keeps its bits."""
+    _f32c(cos, sin)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("rope_qk: qkv must be a 16-bit [rows, ld] matrix with unit column stride")
+    if tuple(cos.shape) != (tokens - prefix, hd) or tuple(sin.shape) != (tokens - prefix, hd):
+        raise ValueError(f"rope_qk: cos and sin must be [tokens - prefix, hd] = [{tokens - prefix}, {hd}]")
+    if qkv.shape[1] < 3 * heads * hdp:
+        raise ValueError(f"rope_qk: qkv has {qkv.shape[1]} columns, q | k | v of {heads} heads of {hdp} need {3 * heads * hdp}")
+    _call(lib().la_rope_qk, qkv, qkv.shape[0], qkv.stride(0), tokens, prefix, heads, hd, hdp, cos, sin, dt_of(qkv))

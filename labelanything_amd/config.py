@@ -18,7 +18,8 @@ class EncoderSpec:
 
     kind "sam": ViTDet backbone with 14x14 windowed + global rel-pos attention
     (models/image_encoder.py).  kind "hf": plain pre-LN ViT with CLS token as in
-    transformers.ViTModel (models/build_encoder.py:83-100).
+    transformers.ViTModel (models/build_encoder.py:83-100).  kind "dinov3": transformers.DINOv3ViTModel - no position table, 2-D rotary
+    embeddings on q and k of the patch tokens in every block, CLS + register tokens in front, LayerScale on both branches.
     """
 
     kind: str
@@ -31,6 +32,13 @@ class EncoderSpec:
     global_idx: Tuple[int, ...] = ()
     window: int = 14
     out_chans: int = 256            # SAM neck output channels
+    # kind "dinov3" (DINOv3ViTConfig: num_register_tokens, rope_theta, layerscale_value, key_bias, layer_norm_eps); every other kind keeps
+    # the defaults and never reads them
+    prefix_tokens: int = 1          # rows in front of the patch tokens: 1 CLS + the register tokens
+    rope_theta: float = 100.0
+    layer_scale: bool = False       # LayerScale on the attention and the MLP branch
+    key_bias: bool = True           # k_proj carries a bias
+    ln_eps: float = 1e-12           # of every LayerNorm of the stack (kind "dinov3" only: the other kinds' eps is fixed by their block names)
 
     @property
     def head_dim(self) -> int:
@@ -40,6 +48,8 @@ class EncoderSpec:
     def pos_grid(self) -> int:
         return self.img_size // self.patch
 
+
+_DINOV3 = dict(prefix_tokens=5, rope_theta=100.0, layer_scale=True, key_bias=False, ln_eps=1e-5)
 
 ENCODER_SPECS: Dict[str, EncoderSpec] = {
     # models/build_encoder.py:9-28 (SAM ViT-B/L/H), _build_vit :43-80
@@ -53,7 +63,33 @@ ENCODER_SPECS: Dict[str, EncoderSpec] = {
     "vit_dino_b8": EncoderSpec("hf", 768, 12, 12, 3072, patch=8, img_size=224),
     # google/vit-base-patch16-224-in21k (models/build_encoder.py:108-112): the plain HF ViT-B geometry
     "vit_b_imagenet_i21k": EncoderSpec("hf", 768, 12, 12, 3072, img_size=224),
+    # facebook/dinov3-vit{s,b,l}16-pretrain-* (parameters/trainval/coco/dinov3.yaml trains on ViT-B/16 embeddings at 480 px)
+    "vit_s_dinov3": EncoderSpec("dinov3", 384, 12, 6, 1536, img_size=224, **_DINOV3),
+    "vit_b_dinov3": EncoderSpec("dinov3", 768, 12, 12, 3072, img_size=224, **_DINOV3),
+    "vit_l_dinov3": EncoderSpec("dinov3", 1024, 24, 16, 4096, img_size=224, **_DINOV3),
 }
+
+
+def dinov3_spec_from_hf_config(hf: dict) -> EncoderSpec:
+    """EncoderSpec of a HuggingFace ``config.json`` with model_type "dinov3_vit".  What the device path does not build is refused here:
+    the gated MLP of the S+ / H+ sizes, another activation than GELU, and projections whose bias layout differs from the published one."""
+    if hf.get("model_type") != "dinov3_vit":
+        raise ValueError(f"not a DINOv3 ViT config: model_type={hf.get('model_type')!r}")
+    if hf.get("use_gated_mlp", False):
+        raise NotImplementedError("DINOv3 ViT with use_gated_mlp=True (the S+ and H+ sizes: SwiGLU MLP) is not built; the plain-MLP sizes "
+                                  "ViT-S/16, ViT-B/16 and ViT-L/16 are")
+    if hf.get("hidden_act", "gelu") != "gelu":
+        raise NotImplementedError(f"DINOv3 ViT with hidden_act={hf['hidden_act']!r} is not built: only 'gelu'")
+    for name, want in (("query_bias", True), ("value_bias", True), ("proj_bias", True), ("mlp_bias", True)):
+        if bool(hf.get(name, want)) != want:
+            raise NotImplementedError(f"DINOv3 ViT with {name}={hf[name]!r} is not built: only {want}")
+    dim, heads = int(hf["hidden_size"]), int(hf["num_attention_heads"])
+    if dim % heads or (dim // heads) % 16:
+        raise NotImplementedError(f"DINOv3 ViT head width {dim}/{heads}: la_rope_qk rotates head widths that are multiples of 16")
+    return EncoderSpec("dinov3", dim, int(hf["num_hidden_layers"]), heads, int(hf["intermediate_size"]), patch=int(hf.get("patch_size", 16)),
+                       img_size=int(hf.get("image_size", 224)), prefix_tokens=1 + int(hf.get("num_register_tokens", 0)),
+                       rope_theta=float(hf.get("rope_theta", 100.0)), layer_scale=True, key_bias=bool(hf.get("key_bias", False)),
+                       ln_eps=float(hf.get("layer_norm_eps", 1e-5)))
 
 
 def register_encoder(name: str, spec: EncoderSpec) -> None:

@@ -13,6 +13,7 @@ PyTorch is used for device memory, views/copies and the host-side prompt bookkee
 from __future__ import annotations
 
 
+import dataclasses
 import math
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -102,6 +103,10 @@ SAM_BLOCK = BlockNames("image_encoder.blocks.{}", "norm1", ("attn.qkv",), "attn.
 HF_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "layernorm_before",
                       ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.dense",
                       "layernorm_after", "intermediate.dense", "output.dense", 1e-12)
+# DINOv3 ViT (transformers DINOv3ViTLayer).  ``o_ls`` / ``down_ls`` are not checkpoint tensors: LamEngine._fold_layer_scale derives them from
+# o_proj / down_proj and the block's LayerScale vectors; eps comes from the spec (dinov3_block_names).
+DINOV3_BLOCK = BlockNames("image_encoder.layer.{}", "norm1", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "attention.o_ls",
+                          "norm2", "mlp.up_proj", "mlp.down_ls", 1e-5)
 
 
 @dataclass(frozen=True)
@@ -136,6 +141,19 @@ class AttnGeo:
     @property
     def parted(self) -> bool:     # qkv and the attention output are in window order
         return self.ws > 0 and self.form != "rows"
+
+
+def rope_table(g: int, hd: int, theta: float) -> Tuple[Tensor, Tensor]:
+    """(cos, sin), fp32 [g * g, hd] on the host: the rotary table of a g x g patch grid (transformers DINOv3ViTRopePositionEmbedding in
+    eval mode, operation for operation).  Patch centres (i + 0.5) / g mapped to [-1, 1], row-major (y, x); inv_freq =
+    theta^(-arange(0, 1, 4 / hd)); angles 2 pi coord (x) inv_freq flattened (y block, then x block) to hd / 2 and tiled twice."""
+    if hd % 4:
+        raise ValueError(f"rope_table: head width {hd} must be a multiple of 4")
+    c = torch.arange(0.5, g, dtype=torch.float32) / g
+    coords = 2.0 * torch.stack(torch.meshgrid(c, c, indexing="ij"), dim=-1).flatten(0, 1) - 1.0          # [g g, 2] = (y, x)
+    inv_freq = 1 / theta ** torch.arange(0, 1, 4 / hd, dtype=torch.float32)                                # [hd / 4]
+    angles = (2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]).flatten(1, 2).tile(2)           # [g g, hd]
+    return torch.cos(angles).contiguous(), torch.sin(angles).contiguous()
 
 
 _BICUBIC: Dict[tuple, Tensor] = {}
@@ -214,6 +232,7 @@ class LamEngine:
         # attention without V^T copies / window buffers (la_attn_fwd_rows) wherever its forms cover the block: plain attention, the 64 x 64
         # rel-pos grid, 16-slot windows; False keeps the V^T epilogue + window scatter path (A/B, and what the other geometries still use)
         self.attn_rows = True
+        self.last_block_path: Optional[str] = None      # "plain" | "fold": the block driver dinov3_encoder took last (tests assert it)
         self.win_fused_cs = True           # folded SAM stack: the window blocks' token means of the attention output from the attention epilogue's column sums
                                            # (on the matrix pipe since round 6; as the global blocks always did) instead of a la_colmean16 pass (A/B: False)
         self.conv_implicit = True          # the necks' 3 x 3 convolution as an implicit GEMM on zero-bordered plane-pair maps (A/B: False = im2col + GEMM)
@@ -241,6 +260,7 @@ class LamEngine:
         self._pe_cache: Dict[int, Tensor] = {}
         self._pe_tables: Dict[tuple, Tensor] = {}
         self._hfpos_cache: Dict[int, Tensor] = {}
+        self._rope_cache: Dict[int, Tuple[Tensor, Tensor]] = {}
         self._pack()
 
     # ------------------------------------------------------------------------------------------------
@@ -552,6 +572,13 @@ class LamEngine:
             p[pre + ".patch.w"] = self._patch_weight(pw)
             for i in range(spec.depth):
                 self._pack_block(HF_BLOCK.prefix.format(i), HF_BLOCK)
+        elif spec is not None and spec.kind == "dinov3":
+            pre, nm = "image_encoder", self.dinov3_block_names
+            p[pre + ".patch.w"] = self._patch_weight(w[pre + ".embeddings.patch_embeddings.weight"].flatten(1))
+            p[pre + ".prefix"] = torch.cat([w[pre + ".embeddings.cls_token"][0], w[pre + ".embeddings.register_tokens"][0]]).contiguous()
+            for i in range(spec.depth):
+                self._fold_layer_scale(nm.prefix.format(i))
+                self._pack_block(nm.prefix.format(i), nm)
         if self.scope == "encoder":
             return
         if cfg.lam_neck:
@@ -587,6 +614,25 @@ class LamEngine:
         if cfg.spatial_convs:
             for i in range(cfg.spatial_convs):
                 p[f"{md}.sc{i}.w"] = self._hd(w[f"{md}.spatial_convs.{3 * i}.weight"].permute(0, 2, 3, 1).flatten(1))
+
+    @property
+    def dinov3_block_names(self) -> BlockNames:
+        return dataclasses.replace(DINOV3_BLOCK, eps=self.cfg.encoder_spec.ln_eps)
+
+    def _fold_layer_scale(self, bp: str) -> None:
+        """DINOv3ViTLayer: x += lambda1 * o_proj(attn), x += lambda2 * down_proj(mlp).  The LayerScale vectors are folded, in fp32 and
+        before the 16-bit packing, into the rows and the bias of the two projections (``attention.o_ls``, ``mlp.down_ls``), so that the
+        residual epilogues of the block drivers stay what they are; a k_proj without a bias gets a zero one."""
+        w = self.w32
+        for src, dst, ls in (("attention.o_proj", "attention.o_ls", "layer_scale1"), ("mlp.down_proj", "mlp.down_ls", "layer_scale2")):
+            if self.cfg.encoder_spec.layer_scale:
+                lam = w[f"{bp}.{ls}.lambda1"]
+                w[f"{bp}.{dst}.weight"] = (lam[:, None] * w[f"{bp}.{src}.weight"]).contiguous()
+                w[f"{bp}.{dst}.bias"] = (lam * w[f"{bp}.{src}.bias"]).contiguous()
+            else:
+                w[f"{bp}.{dst}.weight"], w[f"{bp}.{dst}.bias"] = w[f"{bp}.{src}.weight"], w[f"{bp}.{src}.bias"]
+        if not self.cfg.encoder_spec.key_bias:
+            w[bp + ".attention.k_proj.bias"] = torch.zeros_like(w[bp + ".attention.q_proj.bias"])
 
     def _pack_extraction(self, ex: str) -> None:
         """EmbeddingTransformer (prompt_encoder.py:280-298).  The k / v projections stay fp32 matrices: la_extract_fold / la_extract_unfold
@@ -829,6 +875,8 @@ class LamEngine:
             xin, wkw = self.buf("enc.xwin", (at.arows, e), zero=True), dict(window=at.ws, H=at.g, W=at.g)
         self.ln(res, f"{bp}.{nm.norm1}", nm.eps, rvec, rpg, out16=xin, **wkw, **ckw)
         qkv, vt = self._qkv(bp, i, at, xin)
+        if self.cfg.encoder_spec.kind == "dinov3":
+            self._rope(at, qkv)
         ao, o_chunks = self._attention(bp, at, qkv, vt, opart)
         if rvec is not None:
             self.mean_fix(bp, at, e, xpart, opart, o_chunks, ao, rvec)
@@ -870,6 +918,8 @@ class LamEngine:
         if vm or not have_mr:
             L.norm_finalize(None if have_mr else part, rows, e, nm.eps, mr, x16=hi if vm else None, rpg=rpg, cs_part=xpart)
         qkv, _ = self._qkv(bp, i, at, hi, mr)
+        if self.cfg.encoder_spec.kind == "dinov3":
+            self._rope(at, qkv)
         ao, o_chunks = self._attention(bp, at, qkv, None, opart)
         dr = self._fold_mean(bp, at, e, xpart, opart, o_chunks, ao)
         L.gemm(ao, p[bp + ".proj.w"], bias=w[f"{bp}.{nm.proj}.bias"], out16=hi, aux16=lo, nstat_out=part, rvec=dr,
@@ -1022,6 +1072,66 @@ class LamEngine:
         out16.view(bn, hw, e).copy_(fin16.view(bn, t, e)[:, 1:])
         return out32, out16, e
 
+    # ---- DINOv3 ViT encoder (transformers DINOv3ViTModel maths; parameters/trainval/coco/dinov3.yaml trains on its embeddings) --------------
+    def _rope(self, at: AttnGeo, qkv: Tensor) -> None:
+        """Rotate q and k of the patch rows of one block's q | k | v buffer in place (la_rope_qk), between ``_qkv`` and ``_attention``."""
+        spec: EncoderSpec = self.cfg.encoder_spec
+        if at.parted:
+            raise NotImplementedError("la_rope_qk walks image-order rows; window-partitioned attention has no rotary form")
+        hw = at.rpg - spec.prefix_tokens
+        g = math.isqrt(hw)
+        tab = self._rope_cache.get(g)
+        if tab is None:
+            tab = self._rope_cache[g] = tuple(t.to(self.dev) for t in rope_table(g, spec.head_dim, spec.rope_theta))
+        L.rope_qk(qkv, at.rpg, spec.prefix_tokens, at.heads, spec.head_dim, at.hdp, tab[0], tab[1])
+
+    def dinov3_encoder(self, images: Tensor):
+        """hf_encoder without a position table and with ``prefix_tokens`` rows (CLS, registers) in front of every image's patches; the
+        blocks differ by la_rope_qk and by the LayerScale folded into o_proj / down_proj when the weights are packed.  Square inputs."""
+        spec: EncoderSpec = self.cfg.encoder_spec
+        self._check_encoder_input(images)
+        pre, nm, npre = "image_encoder", self.dinov3_block_names, spec.prefix_tokens
+        bn, _, s, s2 = images.shape
+        if s != s2:
+            raise NotImplementedError(f"the DINOv3 encoder is built for square inputs, got {s} x {s2}")
+        e, g = spec.dim, s // spec.patch
+        hw = g * g
+        t = hw + npre
+        rows = bn * t
+        w, p = self.w32, self.p
+        images = images.contiguous()
+        a, akw = self.patches("dino.patchA", images, bn * hw, spec.patch)
+        res = self.f32("dino.res", (rows, e))
+        res.view(bn, t, e)[:, :npre].copy_(p[pre + ".prefix"])       # CLS and register rows (weights only; plain copy)
+        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".embeddings.patch_embeddings.bias"], out32=res, map=L.MAP_GROUP,
+               p=(hw, t, npre, 0, 0), **akw)
+        x16 = self.buf("dino.x16", (rows, e))
+        at = self._attn_geo("dino", bn, t)
+        rvec = None
+        self.last_block_path = "fold" if self.norm_fold and at.form == "rows" and t >= 128 else "plain"
+        if self.last_block_path == "fold":
+            xs = self.buf("dino.xs", (rows, 2 * e), torch.float16)
+            part, mr = self._fold_bufs("dino", rows, e)
+            L.add_rowvec_split(res, None, t, xs)
+            L.norm_stats(res, nm.eps, x16, mr)
+            for i in range(spec.depth):
+                self._block_fold(i, nm, at, xs, part, mr, i == 0)
+            res = self._planes_to_f32(xs, "dino.res")
+        else:
+            if self.mean_planes:
+                rvec = self.f32("dino.rvec", (bn, e), zero=True)
+                rvec.zero_()
+            for i in range(spec.depth):
+                self._block_plain(i, nm, at, res, x16, rvec)
+        fin = self.f32("dino.final", (rows, e))
+        fin16 = self.buf("dino.final16", (rows, e))
+        self.ln(res, pre + ".norm", nm.eps, rvec, t, out32=fin, out16=fin16)
+        out32 = self.f32("dino.out32", (bn * hw, e))
+        out16 = self.buf("dino.out16", (bn * hw, e))
+        out32.view(bn, hw, e).copy_(fin.view(bn, t, e)[:, npre:])      # drop the prefix rows (plain strided copy)
+        out16.view(bn, hw, e).copy_(fin16.view(bn, t, e)[:, npre:])
+        return out32, out16, e
+
     def encode_images(self, images: Tensor):
         """(Bn,3,S,S) fp32 -> (emb32 [Bn*hw, C] NHWC fp32, emb16 or None, C, g)."""
         spec = self.cfg.encoder_spec
@@ -1030,6 +1140,8 @@ class LamEngine:
 
         if spec.kind == "sam":
             out32, out16, c = self.sam_encoder(images)
+        elif spec.kind == "dinov3":
+            out32, out16, c = self.dinov3_encoder(images)
         else:
             out32, out16, c = self.hf_encoder(images)
         return out32, out16, c, images.shape[-1] // spec.patch

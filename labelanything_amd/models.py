@@ -480,9 +480,12 @@ class Lam(nn.Module):
 
 
 def _hf5_to_hf4(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Accept transformers-5.x ViT key names for the HF encoder and map them to the 4.x layout."""
+    """Accept transformers-5.x ViT key names for the HF encoder and map them to the 4.x layout.  DINOv3 ViT: the
+    ``model.layer.N.`` spelling that transformers 5.x prints becomes the ``layer.N.`` of the published checkpoints."""
     out = {}
     for k, v in sd.items():
+        if k.startswith("image_encoder.model.layer."):
+            k = "image_encoder.layer." + k[len("image_encoder.model.layer."):]
         if k.startswith("image_encoder.") and (".layers." in k and "encoder.layer." not in k):
             k = (k.replace("image_encoder.encoder.layers.", "image_encoder.encoder.layer.")
                   .replace("image_encoder.layers.", "image_encoder.encoder.layer.")
@@ -636,10 +639,10 @@ class ImageEncoder(nn.Module):
         spec = ENCODER_SPECS[encoder]
         side = image_size or (spec.img_size if spec.kind == "sam" else 480)
         kw = dict(encoder=encoder, image_size=side, vit_patch_size=vit_patch_size or spec.patch)
-        if spec.kind == "hf":
+        if spec.kind != "sam":
             kw.update(image_embed_dim=spec.dim)
         self.lam = Lam(LamConfig(**kw), seed=seed, compute_dtype=compute_dtype)
-        self.project_last_hidden = bool(project_last_hidden) or spec.kind == "hf"
+        self.project_last_hidden = bool(project_last_hidden) or spec.kind != "sam"
         self.kind = spec.kind
 
     def forward(self, x, return_last_block_state: bool = False):
@@ -694,8 +697,9 @@ def _build_hf_encoder(name: str, project_last_hidden=False, pretrained: Optional
     if pretrained is not None:
         wpath = os.path.join(pretrained, "model.safetensors")
         sd = _load_any(wpath if os.path.exists(wpath) else os.path.join(pretrained, "pytorch_model.bin"))
+        keep_mask_token = ENCODER_SPECS[name].kind == "dinov3"      # (a parameter of DINOv3ViTEmbeddings; MAE's belongs to its decoder)
         sd = {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items()
-              if not k.startswith("decoder.") and "mask_token" not in k}
+              if not k.startswith("decoder.") and (keep_mask_token or "mask_token" not in k)}
         enc.load_state_dict(sd)
     return enc
 

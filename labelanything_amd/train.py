@@ -501,6 +501,10 @@ class LamTrainer:
             raise NotImplementedError(f"the prompt_contrastive loss component is not built for embeddings_per_example="
                                       f"{lam.cfg.embeddings_per_example} (more than one embedding per example); train it without that "
                                       f"component")
+        if train_encoder and lam.cfg.encoder_spec is not None and lam.cfg.encoder_spec.kind == "dinov3":
+            raise NotImplementedError("train_encoder=True with a 'dinov3' encoder is not built: the backward of la_rope_qk (the inverse "
+                                      "rotation) and the gradients of LayerScale and the register tokens do not exist; train on "
+                                      "precomputed embeddings (use_vit=False) or keep the encoder frozen")
         if lam._device().type != "cuda":
             raise RuntimeError("LamTrainer needs the model on an MI355X (there is no CPU path)")
         self.lam = lam

@@ -125,6 +125,31 @@ def encoder_shapes(spec: EncoderSpec, sam_neck: bool = True, pre: str = "image_e
             s[lp + ".output.dense.weight"] = (e, spec.mlp)
             s[lp + ".output.dense.bias"] = (e,)
         _ln_shapes(s, pre + ".layernorm", e)
+    elif spec.kind == "dinov3":
+        # transformers.DINOv3ViTModel with the ``layer.N.`` spelling of the published checkpoints, in its registration order; mask_token
+        # (masked-image pretraining) is held, saved and loaded, never read
+        s[pre + ".embeddings.cls_token"] = (1, 1, e)
+        s[pre + ".embeddings.mask_token"] = (1, 1, e)
+        s[pre + ".embeddings.register_tokens"] = (1, spec.prefix_tokens - 1, e)
+        s[pre + ".embeddings.patch_embeddings.weight"] = (e, 3, spec.patch, spec.patch)
+        s[pre + ".embeddings.patch_embeddings.bias"] = (e,)
+        for i in range(spec.depth):
+            lp = f"{pre}.layer.{i}"
+            _ln_shapes(s, lp + ".norm1", e)
+            s[lp + ".attention.k_proj.weight"] = (e, e)
+            if spec.key_bias:
+                s[lp + ".attention.k_proj.bias"] = (e,)
+            for n in ("v_proj", "q_proj", "o_proj"):
+                s[f"{lp}.attention.{n}.weight"] = (e, e)
+                s[f"{lp}.attention.{n}.bias"] = (e,)
+            s[lp + ".layer_scale1.lambda1"] = (e,)
+            _ln_shapes(s, lp + ".norm2", e)
+            s[lp + ".mlp.up_proj.weight"] = (spec.mlp, e)
+            s[lp + ".mlp.up_proj.bias"] = (spec.mlp,)
+            s[lp + ".mlp.down_proj.weight"] = (e, spec.mlp)
+            s[lp + ".mlp.down_proj.bias"] = (e,)
+            s[lp + ".layer_scale2.lambda1"] = (e,)
+        _ln_shapes(s, pre + ".norm", e)
     else:
         raise ValueError(spec.kind)
     return s
@@ -241,7 +266,10 @@ def init_state_dict(cfg: LamConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
     gen = torch.Generator().manual_seed(seed)
     out: Dict[str, torch.Tensor] = {}
     for name, shape in model_shapes(cfg).items():
-        if _is_norm(name):
+        if name.endswith(".lambda1"):
+            # LayerScale: uniform on [0.05, 1.5] and not the checkpoints' initial 1.0, so that folding it into a projection is never a no-op
+            t = 0.05 + 1.45 * torch.rand(shape, generator=gen)
+        elif _is_norm(name):
             if name.endswith(".weight"):
                 t = 1.0 + 0.1 * torch.randn(shape, generator=gen)
             else:
@@ -253,7 +281,7 @@ def init_state_dict(cfg: LamConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
         elif "rel_pos" in name:
             t = 0.1 * torch.randn(shape, generator=gen)
         elif name.endswith("pos_embed") or "position_embeddings" in name or "cls_token" in name \
-                or "pos_embedding" in name:
+                or "pos_embedding" in name or "register_tokens" in name or "mask_token" in name:
             t = 0.02 * torch.randn(shape, generator=gen)
         elif (len(shape) == 2 and shape[0] == 1) or name.endswith("embedding_extraction.embeddings.weight"):
             t = torch.randn(shape, generator=gen)    # nn.Embedding rows: N(0, 1) per entry
