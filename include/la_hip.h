@@ -198,6 +198,12 @@ int la_layernorm(const float* x, const float* x2, int ldx, int rows, int E, cons
  * (image_encoder.py:399-410, Conv2d k=s=patch). */
 int la_im2col_patch(const float* img, int Bn, int S, int patch, void* out16, int dt, void* stream);
 
+/* The same gather for patch sides that are no multiple of 8 (transformers Dinov2PatchEmbeddings, patch 14): rows [Bn*g*g, Kp] with
+ * k = c*p*p + ky*p + kx for k < K = 3*p*p and exact zeros in the columns K .. Kp, written on every call.  patch even and >= 2,
+ * S % patch == 0, Kp % 64 == 0, Kp >= K, Kp >= 128.  dt as for la_im2col_patch; LA_F16X2: fp16 rows [hi (Kp) | lo (Kp)] of length 2 Kp.
+ * img 8-byte, out 16-byte aligned.  Multiply by a weight whose columns K .. Kp are zero. */
+int la_im2col_patch_pad(const float* img, int Bn, int S, int patch, int Kp, void* out, int dt, void* stream);
+
 /* 3x3 / pad 1 im2col on an NHWC 16-bit map [B,H,W,C] -> [B*H*W, 9*C], k = (ky*3+kx)*C + c  (C % 8 == 0)
  * (neck conv image_encoder.py:100-106, spatial convs mask_decoder.py:236-255).  dt = LA_F16X2: pixel rows are fp16 plane pairs
  * [hi (C) | lo (C)] and the output rows [9 taps of hi | 9 taps of lo] (18 C columns). */

@@ -5,7 +5,7 @@ The baseline few-shot models (dcama, fptrans, panet, ...), SAM itself and the mu
 from labelanything_amd.models import (  # noqa: F401
     ENCODERS, ImageEncoder, LabelAnything, Lam, build_encoder, build_lam, build_lam_dino_b8, build_lam_no_vit, build_lam_vit_b,
     build_lam_vit_b_imagenet_i21k, build_lam_vit_h, build_lam_vit_l, build_lam_vit_mae_b, build_vit_b, build_vit_b_imagenet_i21k,
-    build_vit_b_mae, build_vit_dino_b8, build_vit_h, build_vit_l,
+    build_vit_b_dinov2, build_vit_b_mae, build_vit_dino_b8, build_vit_h, build_vit_l,
 )
 
 # registry name -> builder; the names are the contract (experiment configs and the embeddings CLI index the dict by them)
@@ -14,4 +14,4 @@ model_registry = dict(
     lam_h=build_lam_vit_h, lam_l=build_lam_vit_l, lam_b=build_lam_vit_b,
     lam_mae_b=build_lam_vit_mae_b, lam_dino_b8=build_lam_dino_b8, lam_b_imagenet_i21k=build_lam_vit_b_imagenet_i21k,
 )
-model_registry.update(ENCODERS)        # encoder-only entries: vit_h, vit_l, vit_b, vit_b_mae, vit_dino_b8
+model_registry.update(ENCODERS)        # encoder-only entries: vit_h, vit_l, vit_b, vit_b_mae, vit_dino_b8, vit_b_dinov2

@@ -17,7 +17,7 @@ import torch
 from PIL import Image
 from safetensors.torch import load_file, save_file
 
-from labelanything_amd.config import ENCODER_SPECS, EncoderSpec, LamConfig, dinov3_spec_from_hf_config, register_encoder
+from labelanything_amd.config import ENCODER_SPECS, EncoderSpec, LamConfig, dinov2_spec_from_hf_config, dinov3_spec_from_hf_config, register_encoder
 from labelanything_amd.image_prep import DevicePreprocessor
 from labelanything_amd.models import Lam, _hf5_to_hf4
 
@@ -131,12 +131,17 @@ def preprocess_images_to_embeddings_huggingface(model_name, directory, batch_siz
     """Plain HF ViT encoders (preprocess.py:209-246).  ``model_name`` is a LOCAL HuggingFace model directory
     (config.json + model.safetensors | pytorch_model.bin); there is no network in this build.  A directory whose config.json says
     model_type "dinov3_vit" runs the DINOv3 encoder (rotary embeddings, register tokens, LayerScale) with the ImageNet mean and std its
-    image processor uses; its gated-MLP sizes are refused (config.dinov3_spec_from_hf_config)."""
+    image processor uses; its gated-MLP sizes are refused (config.dinov3_spec_from_hf_config).  model_type "dinov2" runs the DINOv2 encoder
+    (14 x 14 patches, LayerScale) the same way; the SwiGLU giant size and model_type "dinov2_with_registers" are refused from config.json
+    alone (config.dinov2_spec_from_hf_config)."""
     with open(os.path.join(model_name, "config.json")) as fh:
         hc = json.load(fh)
     dinov3 = hc.get("model_type") == "dinov3_vit"
+    dino = dinov3 or hc.get("model_type") == "dinov2"       # own a mask_token; ImageNet statistics whatever --mean_std says
     if dinov3:
         spec = dinov3_spec_from_hf_config(hc)
+    elif hc.get("model_type") in ("dinov2", "dinov2_with_registers"):
+        spec = dinov2_spec_from_hf_config(hc)
     else:
         spec = EncoderSpec("hf", dim=hc["hidden_size"], depth=hc["num_hidden_layers"], heads=hc["num_attention_heads"],
                            mlp=hc["intermediate_size"], patch=hc.get("patch_size", 16), img_size=hc.get("image_size", 224))
@@ -148,12 +153,12 @@ def preprocess_images_to_embeddings_huggingface(model_name, directory, batch_siz
     sd = load_file(wpath) if os.path.exists(wpath) else torch.load(os.path.join(model_name, "pytorch_model.bin"), map_location="cpu")
     sd = {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items() if not k.startswith("decoder.")}
     enc = _hf5_to_hf4({"image_encoder." + k: v for k, v in sd.items()})
-    if not dinov3:         # (MAE's mask_token belongs to its decoder; DINOv3ViTEmbeddings owns one, loaded and never read)
+    if not dino:           # (MAE's mask_token belongs to its decoder; the DINO embeddings own one, loaded and never read)
         enc = {k: v for k, v in enc.items() if "mask_token" not in k}
     missing, unexpected = torch.nn.Module.load_state_dict(lam, enc, strict=False)
     missing = [k for k in missing if k.startswith("image_encoder.")]
     if missing or unexpected:
         raise RuntimeError(f"weights do not match the ViT config: missing {missing[:5]}, unexpected {unexpected[:5]}")
     lam = lam.to(device)
-    mean, std = IMAGENET_DEFAULT if dinov3 else get_mean_std(mean_std)
+    mean, std = IMAGENET_DEFAULT if dino else get_mean_std(mean_std)
     return _run(lam, directory, outfolder, None, batch_size, image_resolution, custom_preprocess, mean, std, square=True)

@@ -158,6 +158,7 @@ SIGNATURES = dict(line.split() for line in """
     la_extract_fold_bwd                     pppiiippps
     la_extract_unfold_bwd                   pppiiippps
     la_rope_qk                              pliiiiiippis
+    la_im2col_patch_pad                     piiiipis
 """.strip().splitlines())
 EXPORTS = list(SIGNATURES)                  # (tests check the .so exports all of them)
 _CTYPE = {"p": C.c_void_p, "h": C.c_void_p, "s": C.c_void_p, "i": C.c_int, "l": C.c_long, "q": C.c_longlong, "f": C.c_float}
@@ -437,6 +438,26 @@ def im2col_patch(img: torch.Tensor, patch: int, out16: torch.Tensor, split: bool
     if split and out16.dtype != torch.float16:
         raise RuntimeError("im2col_patch(split=True) writes fp16 plane pairs")
     _call(lib().la_im2col_patch, img, bn, s, patch, out16, dt)
+
+
+def im2col_patch_pad(img: torch.Tensor, patch: int, kp: int, out: torch.Tensor, split: bool = False) -> None:
+    """im2col_patch for even patch sides that are no multiple of 8: out [Bn g g, kp] (split: fp16 [Bn g g, 2 kp] = [hi | lo]), the columns
+    3 patch^2 .. kp zero.  Everything the library would refuse is refused here, before it is entered."""
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3] or img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError("im2col_patch_pad: img must be a contiguous fp32 [Bn, 3, S, S] tensor")
+    bn, _, s, _ = img.shape
+    k = 3 * patch * patch
+    if patch < 2 or patch % 2 or s % patch:
+        raise ValueError(f"im2col_patch_pad: patch={patch} must be even, >= 2 and divide the image side {s}")
+    if kp % 64 or kp < k or kp < 128:
+        raise ValueError(f"im2col_patch_pad: kp={kp} must be a multiple of 64, >= 128 and >= 3 patch^2 = {k}")
+    rows = bn * (s // patch) ** 2
+    if split and out.dtype != torch.float16:
+        raise ValueError("im2col_patch_pad(split=True) writes fp16 plane pairs")
+    if out.dtype not in _DT or tuple(out.shape) != (rows, 2 * kp if split else kp) or not out.is_contiguous():
+        raise ValueError(f"im2col_patch_pad: out must be a contiguous fp16 / bf16 / fp32 [{rows}, {2 * kp if split else kp}] matrix, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    _call(lib().la_im2col_patch_pad, img, bn, s, patch, kp, out, LA_F16X2 if split else dt_of(out))
 
 
 def im2col_3x3(x16: torch.Tensor, b: int, h: int, w: int, c: int, out16: torch.Tensor, split: bool = False) -> None:

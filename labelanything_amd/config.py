@@ -19,7 +19,9 @@ class EncoderSpec:
     kind "sam": ViTDet backbone with 14x14 windowed + global rel-pos attention
     (models/image_encoder.py).  kind "hf": plain pre-LN ViT with CLS token as in
     transformers.ViTModel (models/build_encoder.py:83-100).  kind "dinov3": transformers.DINOv3ViTModel - no position table, 2-D rotary
-    embeddings on q and k of the patch tokens in every block, CLS + register tokens in front, LayerScale on both branches.
+    embeddings on q and k of the patch tokens in every block, CLS + register tokens in front, LayerScale on both branches.  kind "dinov2":
+    transformers.Dinov2Model - the "hf" stack (CLS token, position table resampled bicubically) with 14 x 14 patches, LayerScale on both
+    branches, its own key names and the LayerNorm eps of its config.
     """
 
     kind: str
@@ -32,13 +34,13 @@ class EncoderSpec:
     global_idx: Tuple[int, ...] = ()
     window: int = 14
     out_chans: int = 256            # SAM neck output channels
-    # kind "dinov3" (DINOv3ViTConfig: num_register_tokens, rope_theta, layerscale_value, key_bias, layer_norm_eps); every other kind keeps
+    # kinds "dinov3", "dinov2" (DINOv3ViTConfig: num_register_tokens, rope_theta, layerscale_value, key_bias, layer_norm_eps); every other kind keeps
     # the defaults and never reads them
     prefix_tokens: int = 1          # rows in front of the patch tokens: 1 CLS + the register tokens
     rope_theta: float = 100.0
     layer_scale: bool = False       # LayerScale on the attention and the MLP branch
     key_bias: bool = True           # k_proj carries a bias
-    ln_eps: float = 1e-12           # of every LayerNorm of the stack (kind "dinov3" only: the other kinds' eps is fixed by their block names)
+    ln_eps: float = 1e-12           # of every LayerNorm of the stack (kinds "dinov3", "dinov2": the other kinds' eps is fixed by their block names)
 
     @property
     def head_dim(self) -> int:
@@ -50,6 +52,7 @@ class EncoderSpec:
 
 
 _DINOV3 = dict(prefix_tokens=5, rope_theta=100.0, layer_scale=True, key_bias=False, ln_eps=1e-5)
+_DINOV2 = dict(patch=14, img_size=518, layer_scale=True, ln_eps=1e-6)
 
 ENCODER_SPECS: Dict[str, EncoderSpec] = {
     # models/build_encoder.py:9-28 (SAM ViT-B/L/H), _build_vit :43-80
@@ -67,6 +70,10 @@ ENCODER_SPECS: Dict[str, EncoderSpec] = {
     "vit_s_dinov3": EncoderSpec("dinov3", 384, 12, 6, 1536, img_size=224, **_DINOV3),
     "vit_b_dinov3": EncoderSpec("dinov3", 768, 12, 12, 3072, img_size=224, **_DINOV3),
     "vit_l_dinov3": EncoderSpec("dinov3", 1024, 24, 16, 4096, img_size=224, **_DINOV3),
+    # facebook/dinov2-{small,base,large} (parameters/trainval/coco/dinov2.yaml trains on ViT-B/14 embeddings at 224 px); position table 37 x 37
+    "vit_s_dinov2": EncoderSpec("dinov2", 384, 12, 6, 1536, **_DINOV2),
+    "vit_b_dinov2": EncoderSpec("dinov2", 768, 12, 12, 3072, **_DINOV2),
+    "vit_l_dinov2": EncoderSpec("dinov2", 1024, 24, 16, 4096, **_DINOV2),
 }
 
 
@@ -90,6 +97,29 @@ def dinov3_spec_from_hf_config(hf: dict) -> EncoderSpec:
                        img_size=int(hf.get("image_size", 224)), prefix_tokens=1 + int(hf.get("num_register_tokens", 0)),
                        rope_theta=float(hf.get("rope_theta", 100.0)), layer_scale=True, key_bias=bool(hf.get("key_bias", False)),
                        ln_eps=float(hf.get("layer_norm_eps", 1e-5)))
+
+
+def dinov2_spec_from_hf_config(hf: dict) -> EncoderSpec:
+    """EncoderSpec of a HuggingFace ``config.json`` with model_type "dinov2" (Dinov2Config has no intermediate_size: the MLP is
+    hidden_size * mlp_ratio wide).  Refused here, by name: the register variant, the SwiGLU MLP of the giant size, another activation than
+    GELU, q / k / v without biases, and heads wider than the attention kernels' 128 columns."""
+    if hf.get("model_type") == "dinov2_with_registers":
+        raise NotImplementedError("model_type 'dinov2_with_registers': the register variant of DINOv2 is not built; the plain 'dinov2' "
+                                  "checkpoints (small, base, large) are")
+    if hf.get("model_type") != "dinov2":
+        raise ValueError(f"not a DINOv2 config: model_type={hf.get('model_type')!r}")
+    if hf.get("use_swiglu_ffn", False):
+        raise NotImplementedError("DINOv2 with use_swiglu_ffn=True (the giant size: SwiGLU MLP) is not built; the plain-MLP sizes "
+                                  "small, base and large are")
+    if hf.get("hidden_act", "gelu") != "gelu":
+        raise NotImplementedError(f"DINOv2 with hidden_act={hf['hidden_act']!r} is not built: only 'gelu'")
+    if not hf.get("qkv_bias", True):
+        raise NotImplementedError("DINOv2 with qkv_bias=False is not built: only q / k / v projections with biases")
+    dim, heads = int(hf["hidden_size"]), int(hf["num_attention_heads"])
+    if dim % heads or dim // heads > 128:
+        raise NotImplementedError(f"DINOv2 head width {dim}/{heads}: the attention kernels take heads of at most 128 columns")
+    return EncoderSpec("dinov2", dim, int(hf["num_hidden_layers"]), heads, int(dim * hf.get("mlp_ratio", 4)), patch=int(hf.get("patch_size", 14)),
+                       img_size=int(hf.get("image_size", 518)), layer_scale=True, ln_eps=float(hf.get("layer_norm_eps", 1e-6)))
 
 
 def register_encoder(name: str, spec: EncoderSpec) -> None:

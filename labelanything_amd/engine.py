@@ -107,6 +107,19 @@ HF_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "layernorm_before",
 # o_proj / down_proj and the block's LayerScale vectors; eps comes from the spec (dinov3_block_names).
 DINOV3_BLOCK = BlockNames("image_encoder.layer.{}", "norm1", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "attention.o_ls",
                           "norm2", "mlp.up_proj", "mlp.down_ls", 1e-5)
+# DINOv2 (transformers Dinov2Layer): the HF block with its own LayerNorm / MLP names; ``output.ls`` / ``fc2_ls`` are derived like DINOv3's.
+DINOV2_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "norm1",
+                          ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.ls",
+                          "norm2", "mlp.fc1", "mlp.fc2_ls", 1e-6)
+# the checkpoint's projections the LayerScale vectors are folded into: (source of BlockNames.proj, source of BlockNames.lin2)
+LAYER_SCALE_SRC = {"dinov3": ("attention.o_proj", "mlp.down_proj"), "dinov2": ("attention.output.dense", "mlp.fc2")}
+
+
+def patch_kp(patch: int) -> int:
+    """Columns of the patch-embedding operand: K = 3 p p when the patch side is a multiple of 8 (la_im2col_patch), else K rounded up to
+    the multiple of 64 (at least 128) that la_im2col_patch_pad pads with zeros and every K % 64 == 0 path of la_gemm takes."""
+    k = 3 * patch * patch
+    return k if patch % 8 == 0 else max(128, -(-k // 64) * 64)
 
 
 @dataclass(frozen=True)
@@ -232,7 +245,7 @@ class LamEngine:
         # attention without V^T copies / window buffers (la_attn_fwd_rows) wherever its forms cover the block: plain attention, the 64 x 64
         # rel-pos grid, 16-slot windows; False keeps the V^T epilogue + window scatter path (A/B, and what the other geometries still use)
         self.attn_rows = True
-        self.last_block_path: Optional[str] = None      # "plain" | "fold": the block driver dinov3_encoder took last (tests assert it)
+        self.last_block_path: Optional[str] = None      # "plain" | "fold": the block driver hf_encoder / dinov3_encoder took last (tests assert it)
         self.win_fused_cs = True           # folded SAM stack: the window blocks' token means of the attention output from the attention epilogue's column sums
                                            # (on the matrix pipe since round 6; as the global blocks always did) instead of a la_colmean16 pass (A/B: False)
         self.conv_implicit = True          # the necks' 3 x 3 convolution as an implicit GEMM on zero-bordered plane-pair maps (A/B: False = im2col + GEMM)
@@ -412,7 +425,11 @@ class LamEngine:
     def _patch_weight(self, pw: Tensor) -> Tensor:
         """Patch-embed weight [dim, 3 p p]: plain 16-bit; or, in the split-precision group "patch", fp16 plane triples
         [W_hi | W_hi | W_lo] against [A_hi | A_lo] patches (three fp16 MFMA products, ~21 mantissa bits; 2.8x the rate of
-        the exact-fp32 MFMA it replaces) - fp32 for bf16 operands, whose planes would carry 16 bits only."""
+        the exact-fp32 MFMA it replaces) - fp32 for bf16 operands, whose planes would carry 16 bits only.  A patch side that is no multiple
+        of 8 (DINOv2's 14: K = 588) gets zero columns up to ``patch_kp`` first, in fp32, which la_im2col_patch_pad's zero columns meet."""
+        kp = patch_kp(math.isqrt(pw.shape[1] // 3))
+        if kp != pw.shape[1]:
+            pw = F.pad(pw, (0, kp - pw.shape[1]))
         if "patch" not in self.precise:
             return self._h(pw)
         self.patch_split = self.dt == torch.float16 and pw.shape[1] % 64 == 0
@@ -420,17 +437,24 @@ class LamEngine:
 
     def patches(self, name: str, images: Tensor, rows: int, patch: int):
         """im2col of the patch embedding in the operand form _patch_weight chose; returns (A, extra la_gemm keywords)."""
-        k = 3 * patch * patch
+        k = patch_kp(patch)
+
+        def gather(a: Tensor, split: bool = False) -> None:
+            if patch % 8:
+                L.im2col_patch_pad(images, patch, k, a, split=split)
+            else:
+                L.im2col_patch(images, patch, a, split=split)
+
         if "patch" not in self.precise:
             a = self.buf(name, (rows, k))
-            L.im2col_patch(images, patch, a)
+            gather(a)
             return a, {}
         if self.patch_split:
             a = self.buf(name, (rows, 2 * k), torch.float16)
-            L.im2col_patch(images, patch, a, split=True)
+            gather(a, split=True)
             return a, {"a_kmod": 2 * k}
         a = self.buf(name, (rows, k), torch.float32)
-        L.im2col_patch(images, patch, a)
+        gather(a)
         return a, {}
 
     def gemm_w(self, a: Tensor, key: str, **kw) -> None:
@@ -566,18 +590,20 @@ class LamEngine:
                         tab = F.interpolate(tab.t().unsqueeze(0), size=2 * size - 1, mode="linear")[0].t()
                     p[f"{bp}.tab{ax}"] = self._h(F.pad(tab, (0, hdp - hd)))
             self._pack_conv_neck(pre + ".neck")
-        elif spec is not None and spec.kind == "hf":
-            pre = "image_encoder"
+        elif spec is not None and spec.kind in ("hf", "dinov2"):
+            pre, nm = "image_encoder", self.hf_block_names
             pw = w[pre + ".embeddings.patch_embeddings.projection.weight"].flatten(1)
             p[pre + ".patch.w"] = self._patch_weight(pw)
             for i in range(spec.depth):
-                self._pack_block(HF_BLOCK.prefix.format(i), HF_BLOCK)
+                if spec.kind == "dinov2":
+                    self._fold_layer_scale(nm.prefix.format(i), nm)
+                self._pack_block(nm.prefix.format(i), nm)
         elif spec is not None and spec.kind == "dinov3":
             pre, nm = "image_encoder", self.dinov3_block_names
             p[pre + ".patch.w"] = self._patch_weight(w[pre + ".embeddings.patch_embeddings.weight"].flatten(1))
             p[pre + ".prefix"] = torch.cat([w[pre + ".embeddings.cls_token"][0], w[pre + ".embeddings.register_tokens"][0]]).contiguous()
             for i in range(spec.depth):
-                self._fold_layer_scale(nm.prefix.format(i))
+                self._fold_layer_scale(nm.prefix.format(i), nm)
                 self._pack_block(nm.prefix.format(i), nm)
         if self.scope == "encoder":
             return
@@ -619,12 +645,20 @@ class LamEngine:
     def dinov3_block_names(self) -> BlockNames:
         return dataclasses.replace(DINOV3_BLOCK, eps=self.cfg.encoder_spec.ln_eps)
 
-    def _fold_layer_scale(self, bp: str) -> None:
-        """DINOv3ViTLayer: x += lambda1 * o_proj(attn), x += lambda2 * down_proj(mlp).  The LayerScale vectors are folded, in fp32 and
-        before the 16-bit packing, into the rows and the bias of the two projections (``attention.o_ls``, ``mlp.down_ls``), so that the
-        residual epilogues of the block drivers stay what they are; a k_proj without a bias gets a zero one."""
+    @property
+    def hf_block_names(self) -> BlockNames:
+        """Block names of the stack ``hf_encoder`` drives: transformers ViTModel's, or Dinov2Model's with the eps of its config."""
+        spec = self.cfg.encoder_spec
+        return HF_BLOCK if spec.kind == "hf" else dataclasses.replace(DINOV2_BLOCK, eps=spec.ln_eps)
+
+    def _fold_layer_scale(self, bp: str, nm: BlockNames) -> None:
+        """DINOv3ViTLayer / Dinov2Layer: x += lambda1 * o_proj(attn), x += lambda2 * down_proj(mlp).  The LayerScale vectors are folded, in
+        fp32 and before the 16-bit packing, into the rows and the bias of the kind's two projections (LAYER_SCALE_SRC), under the derived
+        names ``nm.proj`` / ``nm.lin2``, so that the residual epilogues of the block drivers stay what they are; a key projection without
+        a bias gets a zero one."""
         w = self.w32
-        for src, dst, ls in (("attention.o_proj", "attention.o_ls", "layer_scale1"), ("mlp.down_proj", "mlp.down_ls", "layer_scale2")):
+        osrc, dsrc = LAYER_SCALE_SRC[self.cfg.encoder_spec.kind]
+        for src, dst, ls in ((osrc, nm.proj, "layer_scale1"), (dsrc, nm.lin2, "layer_scale2")):
             if self.cfg.encoder_spec.layer_scale:
                 lam = w[f"{bp}.{ls}.lambda1"]
                 w[f"{bp}.{dst}.weight"] = (lam[:, None] * w[f"{bp}.{src}.weight"]).contiguous()
@@ -632,7 +666,7 @@ class LamEngine:
             else:
                 w[f"{bp}.{dst}.weight"], w[f"{bp}.{dst}.bias"] = w[f"{bp}.{src}.weight"], w[f"{bp}.{src}.bias"]
         if not self.cfg.encoder_spec.key_bias:
-            w[bp + ".attention.k_proj.bias"] = torch.zeros_like(w[bp + ".attention.q_proj.bias"])
+            w[f"{bp}.{nm.qkv[1]}.bias"] = torch.zeros_like(w[f"{bp}.{nm.qkv[0]}.bias"])
 
     def _pack_extraction(self, ex: str) -> None:
         """EmbeddingTransformer (prompt_encoder.py:280-298).  The k / v projections stay fp32 matrices: la_extract_fold / la_extract_unfold
@@ -1008,7 +1042,8 @@ class LamEngine:
             out = (res, last16, e)
         return (out, res) if want_last_block else out
 
-    # ---- HuggingFace plain ViT encoder (transformers ViTModel maths; build_encoder.py:83-100) -------------------------------------------
+    # ---- HuggingFace plain ViT encoder (transformers ViTModel maths; build_encoder.py:83-100) and DINOv2 (Dinov2Model maths: the same
+    # embeddings, position resample and final ``layernorm``; block names, LayerNorm eps and folded LayerScale from ``hf_block_names``) ----
     def _hf_pos(self, g: int) -> Tensor:
         t = self._hfpos_cache.get(g)
         if t is None:
@@ -1029,8 +1064,10 @@ class LamEngine:
     def hf_encoder(self, images: Tensor):
         spec: EncoderSpec = self.cfg.encoder_spec
         self._check_encoder_input(images)
-        pre, nm = "image_encoder", HF_BLOCK
-        bn, _, s, _ = images.shape
+        pre, nm = "image_encoder", self.hf_block_names
+        bn, _, s, s2 = images.shape
+        if spec.kind == "dinov2" and s != s2:
+            raise NotImplementedError(f"the DINOv2 encoder is built for square inputs, got {s} x {s2}")
         e, g = spec.dim, s // spec.patch
         hw = g * g
         t = hw + 1
@@ -1047,7 +1084,8 @@ class LamEngine:
         x16 = self.buf("hf.x16", (rows, e))
         at = self._attn_geo("hf", bn, t)
         rvec = None
-        if self.norm_fold and at.form == "rows" and t >= 128:       # (per-image groups of the producer epilogue: >= 128 rows)
+        self.last_block_path = "fold" if self.norm_fold and at.form == "rows" and t >= 128 else "plain"
+        if self.last_block_path == "fold":                          # (per-image groups of the producer epilogue: >= 128 rows)
             # The stream enters through a row map (CLS gap), so its planes and first statistics come from one pass each; the final
             # ``layernorm`` is the LayerNorm kernel on hi + lo.
             xs = self.buf("hf.xs", (rows, 2 * e), torch.float16)
@@ -1142,8 +1180,10 @@ class LamEngine:
             out32, out16, c = self.sam_encoder(images)
         elif spec.kind == "dinov3":
             out32, out16, c = self.dinov3_encoder(images)
-        else:
+        elif spec.kind in ("hf", "dinov2"):
             out32, out16, c = self.hf_encoder(images)
+        else:
+            raise ValueError(f"no encoder driver for kind {spec.kind!r}")
         return out32, out16, c, images.shape[-1] // spec.patch
 
     def lam_neck(self, emb32: Tensor, emb16: Optional[Tensor], bn: int, g: int) -> Tensor:

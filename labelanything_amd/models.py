@@ -697,7 +697,8 @@ def _build_hf_encoder(name: str, project_last_hidden=False, pretrained: Optional
     if pretrained is not None:
         wpath = os.path.join(pretrained, "model.safetensors")
         sd = _load_any(wpath if os.path.exists(wpath) else os.path.join(pretrained, "pytorch_model.bin"))
-        keep_mask_token = ENCODER_SPECS[name].kind == "dinov3"      # (a parameter of DINOv3ViTEmbeddings; MAE's belongs to its decoder)
+        # (a parameter of DINOv3ViTEmbeddings and of Dinov2Embeddings; MAE's belongs to its decoder)
+        keep_mask_token = {"dinov3": True, "dinov2": True, "hf": False}[ENCODER_SPECS[name].kind]
         sd = {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items()
               if not k.startswith("decoder.") and (keep_mask_token or "mask_token" not in k)}
         enc.load_state_dict(sd)
@@ -716,13 +717,20 @@ def build_vit_dino_b8(**kw) -> ImageEncoder:
     return _build_hf_encoder("vit_dino_b8", **kw)
 
 
+def build_vit_b_dinov2(**kw) -> ImageEncoder:
+    """facebook/dinov2-base (ViT-B/14) at the 224 px of parameters/trainval/coco/dinov2.yaml unless ``image_size`` says otherwise."""
+    kw.setdefault("image_size", 224)
+    return _build_hf_encoder("vit_b_dinov2", **kw)
+
+
 def build_encoder(name: str, **kw) -> ImageEncoder:
     """models/build_encoder.py:138-141; geometries added with ``config.register_encoder`` build through the same two paths."""
     if name in ENCODERS:
         return ENCODERS[name](**kw)
     if name not in ENCODER_SPECS:
         raise KeyError(f"unknown encoder {name!r}; available: {sorted(ENCODER_SPECS)}")
-    return (_build_sam_encoder if ENCODER_SPECS[name].kind == "sam" else _build_hf_encoder)(name, **kw)
+    return {"sam": _build_sam_encoder, "hf": _build_hf_encoder, "dinov3": _build_hf_encoder,
+            "dinov2": _build_hf_encoder}[ENCODER_SPECS[name].kind](name, **kw)
 
 
 # models/build_encoder.py:143-151, on-path entries (resnet50 / swin_b feed the out-of-scope pyramid variants)
@@ -732,6 +740,7 @@ ENCODERS: Dict[str, Any] = {
     "vit_b": build_vit_b,
     "vit_b_mae": build_vit_b_mae,
     "vit_dino_b8": build_vit_dino_b8,
+    "vit_b_dinov2": build_vit_b_dinov2,
 }
 
 

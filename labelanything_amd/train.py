@@ -505,6 +505,10 @@ class LamTrainer:
             raise NotImplementedError("train_encoder=True with a 'dinov3' encoder is not built: the backward of la_rope_qk (the inverse "
                                       "rotation) and the gradients of LayerScale and the register tokens do not exist; train on "
                                       "precomputed embeddings (use_vit=False) or keep the encoder frozen")
+        if train_encoder and lam.cfg.encoder_spec is not None and lam.cfg.encoder_spec.kind == "dinov2":
+            raise NotImplementedError("train_encoder=True with a 'dinov2' encoder is not built: the gradients of LayerScale and of the "
+                                      "padded patch embedding (la_im2col_patch_pad's operand) do not exist; train on precomputed "
+                                      "embeddings (use_vit=False) or keep the encoder frozen")
         if lam._device().type != "cuda":
             raise RuntimeError("LamTrainer needs the model on an MI355X (there is no CPU path)")
         self.lam = lam
@@ -584,7 +588,7 @@ class LamTrainer:
         self.enc_graph = None
         if self.train_encoder:
             from .train_encoder import HfEncoderGraph, SamEncoderGraph
-            graph_cls = SamEncoderGraph if lam.cfg.encoder_spec.kind == "sam" else HfEncoderGraph
+            graph_cls = {"sam": SamEncoderGraph, "hf": HfEncoderGraph}[lam.cfg.encoder_spec.kind]     # (the other kinds are refused above)
             self.enc_graph = graph_cls(lam, {k: gv for k, gv in zip(self.names, self.opt.grad_views) if k.startswith("image_encoder.")},
                                        precise=self.train_precise)
             self._anchor = torch.zeros(1, device=lam._device(), requires_grad=True)

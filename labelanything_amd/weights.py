@@ -150,6 +150,29 @@ def encoder_shapes(spec: EncoderSpec, sam_neck: bool = True, pre: str = "image_e
             s[lp + ".mlp.down_proj.bias"] = (e,)
             s[lp + ".layer_scale2.lambda1"] = (e,)
         _ln_shapes(s, pre + ".norm", e)
+    elif spec.kind == "dinov2":
+        # transformers.Dinov2Model in its registration order and spelling; mask_token (masked-image pretraining) is held, never read
+        s[pre + ".embeddings.cls_token"] = (1, 1, e)
+        s[pre + ".embeddings.mask_token"] = (1, e)
+        s[pre + ".embeddings.position_embeddings"] = (1, 1 + spec.pos_grid ** 2, e)
+        s[pre + ".embeddings.patch_embeddings.projection.weight"] = (e, 3, spec.patch, spec.patch)
+        s[pre + ".embeddings.patch_embeddings.projection.bias"] = (e,)
+        for i in range(spec.depth):
+            lp = f"{pre}.encoder.layer.{i}"
+            _ln_shapes(s, lp + ".norm1", e)
+            for n in ("query", "key", "value"):
+                s[f"{lp}.attention.attention.{n}.weight"] = (e, e)
+                s[f"{lp}.attention.attention.{n}.bias"] = (e,)
+            s[lp + ".attention.output.dense.weight"] = (e, e)
+            s[lp + ".attention.output.dense.bias"] = (e,)
+            s[lp + ".layer_scale1.lambda1"] = (e,)
+            _ln_shapes(s, lp + ".norm2", e)
+            s[lp + ".mlp.fc1.weight"] = (spec.mlp, e)
+            s[lp + ".mlp.fc1.bias"] = (spec.mlp,)
+            s[lp + ".mlp.fc2.weight"] = (e, spec.mlp)
+            s[lp + ".mlp.fc2.bias"] = (e,)
+            s[lp + ".layer_scale2.lambda1"] = (e,)
+        _ln_shapes(s, pre + ".layernorm", e)
     else:
         raise ValueError(spec.kind)
     return s
