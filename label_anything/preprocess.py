@@ -17,9 +17,9 @@ import torch
 from PIL import Image
 from safetensors.torch import load_file, save_file
 
-from labelanything_amd.config import ENCODER_SPECS, EncoderSpec, LamConfig, dinov2_spec_from_hf_config, dinov3_spec_from_hf_config, register_encoder
+from labelanything_amd.config import ENCODER_SPECS, LamConfig, encoder_kind, register_encoder, spec_from_hf_config
 from labelanything_amd.image_prep import DevicePreprocessor
-from labelanything_amd.models import Lam, _hf5_to_hf4
+from labelanything_amd.models import Lam, _hf5_to_hf4, clean_hf_state_dict
 
 IMAGENET_DEFAULT = ([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])      # data/utils.py "default"
 IMAGENET_STANDARD = ([0.5, 0.5, 0.5], [0.5, 0.5, 0.5])                 # data/utils.py "standard"
@@ -133,32 +133,22 @@ def preprocess_images_to_embeddings_huggingface(model_name, directory, batch_siz
     model_type "dinov3_vit" runs the DINOv3 encoder (rotary embeddings, register tokens, LayerScale) with the ImageNet mean and std its
     image processor uses; its gated-MLP sizes are refused (config.dinov3_spec_from_hf_config).  model_type "dinov2" runs the DINOv2 encoder
     (14 x 14 patches, LayerScale) the same way; the SwiGLU giant size and model_type "dinov2_with_registers" are refused from config.json
-    alone (config.dinov2_spec_from_hf_config)."""
+    alone (config.dinov2_spec_from_hf_config).  config.spec_from_hf_config dispatches on the model_type."""
     with open(os.path.join(model_name, "config.json")) as fh:
         hc = json.load(fh)
-    dinov3 = hc.get("model_type") == "dinov3_vit"
-    dino = dinov3 or hc.get("model_type") == "dinov2"       # own a mask_token; ImageNet statistics whatever --mean_std says
-    if dinov3:
-        spec = dinov3_spec_from_hf_config(hc)
-    elif hc.get("model_type") in ("dinov2", "dinov2_with_registers"):
-        spec = dinov2_spec_from_hf_config(hc)
-    else:
-        spec = EncoderSpec("hf", dim=hc["hidden_size"], depth=hc["num_hidden_layers"], heads=hc["num_attention_heads"],
-                           mlp=hc["intermediate_size"], patch=hc.get("patch_size", 16), img_size=hc.get("image_size", 224))
+    spec = spec_from_hf_config(hc)
+    kind = encoder_kind(spec.kind)
     name = "hf:" + os.path.abspath(model_name)
     register_encoder(name, spec)
     lam = Lam(LamConfig(encoder=name, image_size=image_resolution, image_embed_dim=spec.dim, vit_patch_size=spec.patch),
               compute_dtype=compute_dtype)
     wpath = os.path.join(model_name, "model.safetensors")
     sd = load_file(wpath) if os.path.exists(wpath) else torch.load(os.path.join(model_name, "pytorch_model.bin"), map_location="cpu")
-    sd = {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items() if not k.startswith("decoder.")}
-    enc = _hf5_to_hf4({"image_encoder." + k: v for k, v in sd.items()})
-    if not dino:           # (MAE's mask_token belongs to its decoder; the DINO embeddings own one, loaded and never read)
-        enc = {k: v for k, v in enc.items() if "mask_token" not in k}
+    enc = _hf5_to_hf4({"image_encoder." + k: v for k, v in clean_hf_state_dict(sd, spec.kind).items()})
     missing, unexpected = torch.nn.Module.load_state_dict(lam, enc, strict=False)
     missing = [k for k in missing if k.startswith("image_encoder.")]
     if missing or unexpected:
         raise RuntimeError(f"weights do not match the ViT config: missing {missing[:5]}, unexpected {unexpected[:5]}")
     lam = lam.to(device)
-    mean, std = IMAGENET_DEFAULT if dino else get_mean_std(mean_std)
+    mean, std = IMAGENET_DEFAULT if kind.imagenet_stats else get_mean_std(mean_std)
     return _run(lam, directory, outfolder, None, batch_size, image_resolution, custom_preprocess, mean, std, square=True)

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
 import math
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
 
 @dataclass(frozen=True)
@@ -120,6 +120,97 @@ def dinov2_spec_from_hf_config(hf: dict) -> EncoderSpec:
         raise NotImplementedError(f"DINOv2 head width {dim}/{heads}: the attention kernels take heads of at most 128 columns")
     return EncoderSpec("dinov2", dim, int(hf["num_hidden_layers"]), heads, int(dim * hf.get("mlp_ratio", 4)), patch=int(hf.get("patch_size", 14)),
                        img_size=int(hf.get("image_size", 518)), layer_scale=True, ln_eps=float(hf.get("layer_norm_eps", 1e-6)))
+
+
+def vit_spec_from_hf_config(hf: dict) -> EncoderSpec:
+    """EncoderSpec of a HuggingFace ``config.json`` of the plain ViT family (ViTModel, ViTMAEModel): every model_type no other kind claims."""
+    return EncoderSpec("hf", dim=hf["hidden_size"], depth=hf["num_hidden_layers"], heads=hf["num_attention_heads"], mlp=hf["intermediate_size"],
+                       patch=hf.get("patch_size", 16), img_size=hf.get("image_size", 224))
+
+
+@dataclass(frozen=True)
+class BlockNames:
+    """Where one kind of encoder keeps the tensors of a transformer block: ``prefix.format(i)`` + "." + a name below + ".weight" / ".bias"."""
+    prefix: str
+    norm1: str
+    qkv: Tuple[str, ...]          # one fused q | k | v tensor, or q, k, v
+    proj: str
+    norm2: str
+    lin1: str
+    lin2: str
+    eps: float                    # of every LayerNorm of the stack
+
+
+SAM_BLOCK = BlockNames("image_encoder.blocks.{}", "norm1", ("attn.qkv",), "attn.proj", "norm2", "mlp.lin1", "mlp.lin2", 1e-6)
+HF_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "layernorm_before",
+                      ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.dense",
+                      "layernorm_after", "intermediate.dense", "output.dense", 1e-12)
+# DINOv3 ViT (transformers DINOv3ViTLayer).  ``o_ls`` / ``down_ls`` are not checkpoint tensors: LamEngine._fold_layer_scale derives them from
+# o_proj / down_proj and the block's LayerScale vectors; eps comes from the spec (EncoderKind.spec_eps).
+DINOV3_BLOCK = BlockNames("image_encoder.layer.{}", "norm1", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "attention.o_ls",
+                          "norm2", "mlp.up_proj", "mlp.down_ls", 1e-5)
+# DINOv2 (transformers Dinov2Layer): the HF block with its own LayerNorm / MLP names; ``output.ls`` / ``fc2_ls`` are derived like DINOv3's.
+DINOV2_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "norm1",
+                          ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.ls",
+                          "norm2", "mlp.fc1", "mlp.fc2_ls", 1e-6)
+
+
+@dataclass(frozen=True)
+class EncoderKind:
+    """Everything the code asks about ``EncoderSpec.kind``, as data.  Tensor names are relative to ``image_encoder.``."""
+    blocks: BlockNames
+    patch: str                                      # the patch embedding: + ".weight" / ".bias"
+    final_norm: Optional[str]                       # the LayerNorm behind the block stack (SAM: none, the neck follows)
+    builder: str                                    # the function of models.py that builds the encoder-only model
+    train_graph: str                                # the class of train_encoder.py that trains the stack, or ...
+    train_refusal: Optional[str] = None             # ... why LamTrainer(train_encoder=True) refuses the kind (then train_graph is "")
+    default_side: Optional[int] = 480               # input side of ImageEncoder when none is given; None: the spec's img_size
+    spec_eps: bool = False                          # LayerNorm eps from spec.ln_eps (else blocks.eps)
+    layer_scale: Optional[Tuple[str, str]] = None   # the checkpoint's projections LayerScale folds into: sources of blocks.proj, blocks.lin2
+    prefix: Tuple[str, ...] = ()                    # the tensors whose rows stand in front of every image's patch rows
+    pos_table: bool = False                         # embeddings.position_embeddings: added to every row, resampled to the input's grid
+    rope: bool = False                              # q and k of the patch rows are rotated in every block (la_rope_qk)
+    square: Optional[str] = None                    # the family's name where inputs must be square
+    mask_token: bool = False                        # the checkpoint's mask_token is a parameter of the encoder (else of a decoder: dropped)
+    imagenet_stats: bool = False                    # embeddings are made with the ImageNet mean / std whatever the caller asks for
+    model_types: Tuple[str, ...] = ()               # HuggingFace ``model_type`` values the kind claims (spec_from_hf refuses what is not built)
+    spec_from_hf: Optional[Callable[[dict], EncoderSpec]] = None
+
+
+_HF_PATCH, _CLS, _FROZEN = "embeddings.patch_embeddings.projection", "embeddings.cls_token", "embeddings (use_vit=False) or keep the encoder frozen"
+ENCODER_KINDS: Dict[str, EncoderKind] = {
+    "sam": EncoderKind(SAM_BLOCK, "patch_embed.proj", None, "_build_sam_encoder", "SamEncoderGraph", default_side=None),
+    "hf": EncoderKind(HF_BLOCK, _HF_PATCH, "layernorm", "_build_hf_encoder", "HfEncoderGraph", prefix=(_CLS,), pos_table=True,
+                      spec_from_hf=vit_spec_from_hf_config),
+    "dinov2": EncoderKind(DINOV2_BLOCK, _HF_PATCH, "layernorm", "_build_hf_encoder", "", spec_eps=True,
+                          layer_scale=("attention.output.dense", "mlp.fc2"), prefix=(_CLS,), pos_table=True, square="DINOv2", mask_token=True,
+                          imagenet_stats=True, model_types=("dinov2", "dinov2_with_registers"), spec_from_hf=dinov2_spec_from_hf_config,
+                          train_refusal="train_encoder=True with a 'dinov2' encoder is not built: the gradients of LayerScale and of the "
+                                        "padded patch embedding (la_im2col_patch_pad's operand) do not exist; train on precomputed " + _FROZEN),
+    "dinov3": EncoderKind(DINOV3_BLOCK, "embeddings.patch_embeddings", "norm", "_build_hf_encoder", "", spec_eps=True,
+                          layer_scale=("attention.o_proj", "mlp.down_proj"), prefix=(_CLS, "embeddings.register_tokens"), rope=True,
+                          square="DINOv3", mask_token=True, imagenet_stats=True, model_types=("dinov3_vit",),
+                          spec_from_hf=dinov3_spec_from_hf_config,
+                          train_refusal="train_encoder=True with a 'dinov3' encoder is not built: the backward of la_rope_qk (the inverse "
+                                        "rotation) and the gradients of LayerScale and the register tokens do not exist; train on "
+                                        "precomputed " + _FROZEN),
+}
+
+
+def encoder_kind(kind: str) -> EncoderKind:
+    """The one lookup of an encoder kind: everything that depends on ``EncoderSpec.kind`` reads the record it returns."""
+    try:
+        return ENCODER_KINDS[kind]
+    except KeyError:
+        raise ValueError(f"no encoder driver for kind {kind!r}; known kinds: {sorted(ENCODER_KINDS)}") from None
+
+
+def spec_from_hf_config(hf: dict) -> EncoderSpec:
+    """EncoderSpec of a HuggingFace ``config.json``: by the kind that claims its model_type, the plain ViT family otherwise."""
+    for rec in ENCODER_KINDS.values():
+        if hf.get("model_type") in rec.model_types:
+            return rec.spec_from_hf(hf)
+    return vit_spec_from_hf_config(hf)
 
 
 def register_encoder(name: str, spec: EncoderSpec) -> None:

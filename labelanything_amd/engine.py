@@ -22,7 +22,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .config import LamConfig, EncoderSpec
+from .config import LamConfig, EncoderSpec, EncoderKind, encoder_kind
+from .config import BlockNames, SAM_BLOCK, HF_BLOCK, DINOV2_BLOCK, DINOV3_BLOCK          # noqa: F401  (re-exported: train_encoder.py, tests)
 
 Tensor = torch.Tensor
 
@@ -84,35 +85,6 @@ PRECISE_WIDE = ("patch", "vmean", "projmean", "neck")
 PRECISE_WIDE_PLANES = ("patch", "v", "proj", "neck")          # round 2's default: second weight planes for V and proj
 PRECISE_DEFAULT = "auto"
 PRECISE_GROUPS = ("patch", "qkv", "v", "proj", "lin1", "lin2", "neck", "vmean", "projmean")
-
-
-@dataclass(frozen=True)
-class BlockNames:
-    """Where one kind of encoder keeps the tensors of a transformer block: ``prefix.format(i)`` + "." + a name below + ".weight" / ".bias"."""
-    prefix: str
-    norm1: str
-    qkv: Tuple[str, ...]          # one fused q | k | v tensor, or q, k, v
-    proj: str
-    norm2: str
-    lin1: str
-    lin2: str
-    eps: float                    # of every LayerNorm of the stack
-
-
-SAM_BLOCK = BlockNames("image_encoder.blocks.{}", "norm1", ("attn.qkv",), "attn.proj", "norm2", "mlp.lin1", "mlp.lin2", 1e-6)
-HF_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "layernorm_before",
-                      ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.dense",
-                      "layernorm_after", "intermediate.dense", "output.dense", 1e-12)
-# DINOv3 ViT (transformers DINOv3ViTLayer).  ``o_ls`` / ``down_ls`` are not checkpoint tensors: LamEngine._fold_layer_scale derives them from
-# o_proj / down_proj and the block's LayerScale vectors; eps comes from the spec (dinov3_block_names).
-DINOV3_BLOCK = BlockNames("image_encoder.layer.{}", "norm1", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "attention.o_ls",
-                          "norm2", "mlp.up_proj", "mlp.down_ls", 1e-5)
-# DINOv2 (transformers Dinov2Layer): the HF block with its own LayerNorm / MLP names; ``output.ls`` / ``fc2_ls`` are derived like DINOv3's.
-DINOV2_BLOCK = BlockNames("image_encoder.encoder.layer.{}", "norm1",
-                          ("attention.attention.query", "attention.attention.key", "attention.attention.value"), "attention.output.ls",
-                          "norm2", "mlp.fc1", "mlp.fc2_ls", 1e-6)
-# the checkpoint's projections the LayerScale vectors are folded into: (source of BlockNames.proj, source of BlockNames.lin2)
-LAYER_SCALE_SRC = {"dinov3": ("attention.o_proj", "mlp.down_proj"), "dinov2": ("attention.output.dense", "mlp.fc2")}
 
 
 def patch_kp(patch: int) -> int:
@@ -245,7 +217,7 @@ class LamEngine:
         # attention without V^T copies / window buffers (la_attn_fwd_rows) wherever its forms cover the block: plain attention, the 64 x 64
         # rel-pos grid, 16-slot windows; False keeps the V^T epilogue + window scatter path (A/B, and what the other geometries still use)
         self.attn_rows = True
-        self.last_block_path: Optional[str] = None      # "plain" | "fold": the block driver hf_encoder / dinov3_encoder took last (tests assert it)
+        self.last_block_path: Optional[str] = None      # "plain" | "fold": the block driver vit_encoder took last (tests assert it)
         self.win_fused_cs = True           # folded SAM stack: the window blocks' token means of the attention output from the attention epilogue's column sums
                                            # (on the matrix pipe since round 6; as the global blocks always did) instead of a la_colmean16 pass (A/B: False)
         self.conv_implicit = True          # the necks' 3 x 3 convolution as an implicit GEMM on zero-bordered plane-pair maps (A/B: False = im2col + GEMM)
@@ -590,20 +562,14 @@ class LamEngine:
                         tab = F.interpolate(tab.t().unsqueeze(0), size=2 * size - 1, mode="linear")[0].t()
                     p[f"{bp}.tab{ax}"] = self._h(F.pad(tab, (0, hdp - hd)))
             self._pack_conv_neck(pre + ".neck")
-        elif spec is not None and spec.kind in ("hf", "dinov2"):
-            pre, nm = "image_encoder", self.hf_block_names
-            pw = w[pre + ".embeddings.patch_embeddings.projection.weight"].flatten(1)
-            p[pre + ".patch.w"] = self._patch_weight(pw)
+        elif spec is not None:
+            pre, kind, nm = "image_encoder", self.kind, self.block_names
+            p[pre + ".patch.w"] = self._patch_weight(w[f"{pre}.{kind.patch}.weight"].flatten(1))
+            if not kind.pos_table:          # (with a table the prefix row depends on the input's grid: _hf_pos)
+                p[pre + ".prefix"] = torch.cat([w[f"{pre}.{n}"][0] for n in kind.prefix]).contiguous()
             for i in range(spec.depth):
-                if spec.kind == "dinov2":
+                if kind.layer_scale:
                     self._fold_layer_scale(nm.prefix.format(i), nm)
-                self._pack_block(nm.prefix.format(i), nm)
-        elif spec is not None and spec.kind == "dinov3":
-            pre, nm = "image_encoder", self.dinov3_block_names
-            p[pre + ".patch.w"] = self._patch_weight(w[pre + ".embeddings.patch_embeddings.weight"].flatten(1))
-            p[pre + ".prefix"] = torch.cat([w[pre + ".embeddings.cls_token"][0], w[pre + ".embeddings.register_tokens"][0]]).contiguous()
-            for i in range(spec.depth):
-                self._fold_layer_scale(nm.prefix.format(i), nm)
                 self._pack_block(nm.prefix.format(i), nm)
         if self.scope == "encoder":
             return
@@ -642,22 +608,22 @@ class LamEngine:
                 p[f"{md}.sc{i}.w"] = self._hd(w[f"{md}.spatial_convs.{3 * i}.weight"].permute(0, 2, 3, 1).flatten(1))
 
     @property
-    def dinov3_block_names(self) -> BlockNames:
-        return dataclasses.replace(DINOV3_BLOCK, eps=self.cfg.encoder_spec.ln_eps)
+    def kind(self) -> EncoderKind:
+        return encoder_kind(self.cfg.encoder_spec.kind)
 
     @property
-    def hf_block_names(self) -> BlockNames:
-        """Block names of the stack ``hf_encoder`` drives: transformers ViTModel's, or Dinov2Model's with the eps of its config."""
-        spec = self.cfg.encoder_spec
-        return HF_BLOCK if spec.kind == "hf" else dataclasses.replace(DINOV2_BLOCK, eps=spec.ln_eps)
+    def block_names(self) -> BlockNames:
+        """Block names of the encoder's stack, with the LayerNorm eps of the spec where the kind takes it from there."""
+        kind = self.kind
+        return dataclasses.replace(kind.blocks, eps=self.cfg.encoder_spec.ln_eps) if kind.spec_eps else kind.blocks
 
     def _fold_layer_scale(self, bp: str, nm: BlockNames) -> None:
         """DINOv3ViTLayer / Dinov2Layer: x += lambda1 * o_proj(attn), x += lambda2 * down_proj(mlp).  The LayerScale vectors are folded, in
-        fp32 and before the 16-bit packing, into the rows and the bias of the kind's two projections (LAYER_SCALE_SRC), under the derived
+        fp32 and before the 16-bit packing, into the rows and the bias of the kind's two projections (EncoderKind.layer_scale), under the derived
         names ``nm.proj`` / ``nm.lin2``, so that the residual epilogues of the block drivers stay what they are; a key projection without
         a bias gets a zero one."""
         w = self.w32
-        osrc, dsrc = LAYER_SCALE_SRC[self.cfg.encoder_spec.kind]
+        osrc, dsrc = self.kind.layer_scale
         for src, dst, ls in ((osrc, nm.proj, "layer_scale1"), (dsrc, nm.lin2, "layer_scale2")):
             if self.cfg.encoder_spec.layer_scale:
                 lam = w[f"{bp}.{ls}.lambda1"]
@@ -877,7 +843,7 @@ class LamEngine:
             L.attn_fwd_rows(qkv, ao, nb, heads, t, tpad, gg, ea, scale, mode, cspart=opart if fused_o else None, **tabs, **wkw)
         elif at.form == "fp8":
             fused_o = False
-            qk8 = self.arena.get("hf.qk8", (at.arows, 2 * ea), torch.uint8, False)
+            qk8 = self.arena.get(at.pfx + ".qk8", (at.arows, 2 * ea), torch.uint8, False)
             L.qk_fp8(qkv, ea, qk8)
             L.attn_fwd_fp8(qk8, vt, ao, nb, heads, t, tpad, ea, scale)
         else:
@@ -909,7 +875,7 @@ class LamEngine:
             xin, wkw = self.buf("enc.xwin", (at.arows, e), zero=True), dict(window=at.ws, H=at.g, W=at.g)
         self.ln(res, f"{bp}.{nm.norm1}", nm.eps, rvec, rpg, out16=xin, **wkw, **ckw)
         qkv, vt = self._qkv(bp, i, at, xin)
-        if self.cfg.encoder_spec.kind == "dinov3":
+        if self.kind.rope:
             self._rope(at, qkv)
         ao, o_chunks = self._attention(bp, at, qkv, vt, opart)
         if rvec is not None:
@@ -952,7 +918,7 @@ class LamEngine:
         if vm or not have_mr:
             L.norm_finalize(None if have_mr else part, rows, e, nm.eps, mr, x16=hi if vm else None, rpg=rpg, cs_part=xpart)
         qkv, _ = self._qkv(bp, i, at, hi, mr)
-        if self.cfg.encoder_spec.kind == "dinov3":
+        if self.kind.rope:
             self._rope(at, qkv)
         ao, o_chunks = self._attention(bp, at, qkv, None, opart)
         dr = self._fold_mean(bp, at, e, xpart, opart, o_chunks, ao)
@@ -1042,9 +1008,10 @@ class LamEngine:
             out = (res, last16, e)
         return (out, res) if want_last_block else out
 
-    # ---- HuggingFace plain ViT encoder (transformers ViTModel maths; build_encoder.py:83-100) and DINOv2 (Dinov2Model maths: the same
-    # embeddings, position resample and final ``layernorm``; block names, LayerNorm eps and folded LayerScale from ``hf_block_names``) ----
+    # ---- plain ViT encoders: HuggingFace ViT (transformers ViTModel maths; build_encoder.py:83-100), DINOv2 (Dinov2Model) and DINOv3
+    # (DINOv3ViTModel; parameters/trainval/coco/dinov3.yaml trains on its embeddings).  What differs between them is data: EncoderKind ----
     def _hf_pos(self, g: int) -> Tensor:
+        """The position table at a g x g grid, [1 + g * g, E]; leaves the prefix row cls_token + pos[0], [1, E], in ``_hfpos_cache[-g]``."""
         t = self._hfpos_cache.get(g)
         if t is None:
             spec = self.cfg.encoder_spec
@@ -1056,61 +1023,10 @@ class LamEngine:
                 L.gemm_tn(bt, pos[0, 1:].contiguous(), grid)                               # grid = B . pos  (exact-fp32 MFMA)
                 pos = torch.cat([pos[:, :1], grid.unsqueeze(0)], dim=1)
             t = pos[0].contiguous()
-            cls_row = (self.w32["image_encoder.embeddings.cls_token"][0, 0] + t[0]).contiguous()
             self._hfpos_cache[g] = t
-            self._hfpos_cache[-g] = cls_row
+            self._hfpos_cache[-g] = (self.w32["image_encoder.embeddings.cls_token"][0] + t[:1]).contiguous()
         return t
 
-    def hf_encoder(self, images: Tensor):
-        spec: EncoderSpec = self.cfg.encoder_spec
-        self._check_encoder_input(images)
-        pre, nm = "image_encoder", self.hf_block_names
-        bn, _, s, s2 = images.shape
-        if spec.kind == "dinov2" and s != s2:
-            raise NotImplementedError(f"the DINOv2 encoder is built for square inputs, got {s} x {s2}")
-        e, g = spec.dim, s // spec.patch
-        hw = g * g
-        t = hw + 1
-        rows = bn * t
-        w, p = self.w32, self.p
-        pos = self._hf_pos(g)
-        cls_row = self._hfpos_cache[-g]
-        images = images.contiguous()
-        a, akw = self.patches("hf.patchA", images, bn * hw, spec.patch)
-        res = self.f32("hf.res", (rows, e))
-        res.view(bn, t, e)[:, 0].copy_(cls_row)      # CLS row = cls_token + pos[0] (weights only; plain copy)
-        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".embeddings.patch_embeddings.projection.bias"], res=pos, res_mod=t,
-               out32=res, map=L.MAP_GROUP, p=(hw, t, 1, 0, 0), **akw)
-        x16 = self.buf("hf.x16", (rows, e))
-        at = self._attn_geo("hf", bn, t)
-        rvec = None
-        self.last_block_path = "fold" if self.norm_fold and at.form == "rows" and t >= 128 else "plain"
-        if self.last_block_path == "fold":                          # (per-image groups of the producer epilogue: >= 128 rows)
-            # The stream enters through a row map (CLS gap), so its planes and first statistics come from one pass each; the final
-            # ``layernorm`` is the LayerNorm kernel on hi + lo.
-            xs = self.buf("hf.xs", (rows, 2 * e), torch.float16)
-            part, mr = self._fold_bufs("hf", rows, e)
-            L.add_rowvec_split(res, None, t, xs)
-            L.norm_stats(res, nm.eps, x16, mr)
-            for i in range(spec.depth):
-                self._block_fold(i, nm, at, xs, part, mr, i == 0)
-            res = self._planes_to_f32(xs, "hf.res")
-        else:
-            if self.mean_planes:
-                rvec = self.f32("hf.rvec", (bn, e), zero=True)
-                rvec.zero_()
-            for i in range(spec.depth):
-                self._block_plain(i, nm, at, res, x16, rvec)
-        fin = self.f32("hf.final", (rows, e))
-        fin16 = self.buf("hf.final16", (rows, e))
-        self.ln(res, pre + ".layernorm", nm.eps, rvec, t, out32=fin, out16=fin16)
-        out32 = self.f32("hf.out32", (bn * hw, e))
-        out16 = self.buf("hf.out16", (bn * hw, e))
-        out32.view(bn, hw, e).copy_(fin.view(bn, t, e)[:, 1:])          # drop CLS (plain strided copy)
-        out16.view(bn, hw, e).copy_(fin16.view(bn, t, e)[:, 1:])
-        return out32, out16, e
-
-    # ---- DINOv3 ViT encoder (transformers DINOv3ViTModel maths; parameters/trainval/coco/dinov3.yaml trains on its embeddings) --------------
     def _rope(self, at: AttnGeo, qkv: Tensor) -> None:
         """Rotate q and k of the patch rows of one block's q | k | v buffer in place (la_rope_qk), between ``_qkv`` and ``_attention``."""
         spec: EncoderSpec = self.cfg.encoder_spec
@@ -1123,49 +1039,53 @@ class LamEngine:
             tab = self._rope_cache[g] = tuple(t.to(self.dev) for t in rope_table(g, spec.head_dim, spec.rope_theta))
         L.rope_qk(qkv, at.rpg, spec.prefix_tokens, at.heads, spec.head_dim, at.hdp, tab[0], tab[1])
 
-    def dinov3_encoder(self, images: Tensor):
-        """hf_encoder without a position table and with ``prefix_tokens`` rows (CLS, registers) in front of every image's patches; the
-        blocks differ by la_rope_qk and by the LayerScale folded into o_proj / down_proj when the weights are packed.  Square inputs."""
+    def vit_encoder(self, images: Tensor):
+        """``prefix_tokens`` constant rows (CLS, registers) in front of every image's patch rows, the position table where the kind has
+        one, the block stack (plain or folded; la_rope_qk and the folded LayerScale are the blocks' business), the final LayerNorm; the
+        prefix rows are dropped on the way out."""
         spec: EncoderSpec = self.cfg.encoder_spec
         self._check_encoder_input(images)
-        pre, nm, npre = "image_encoder", self.dinov3_block_names, spec.prefix_tokens
+        pre, kind, nm, npre = "image_encoder", self.kind, self.block_names, spec.prefix_tokens
         bn, _, s, s2 = images.shape
-        if s != s2:
-            raise NotImplementedError(f"the DINOv3 encoder is built for square inputs, got {s} x {s2}")
+        if kind.square and s != s2:
+            raise NotImplementedError(f"the {kind.square} encoder is built for square inputs, got {s} x {s2}")
         e, g = spec.dim, s // spec.patch
         hw = g * g
         t = hw + npre
         rows = bn * t
         w, p = self.w32, self.p
+        poskw = dict(res=self._hf_pos(g), res_mod=t) if kind.pos_table else {}
+        prefix = self._hfpos_cache[-g] if kind.pos_table else p[pre + ".prefix"]
         images = images.contiguous()
-        a, akw = self.patches("dino.patchA", images, bn * hw, spec.patch)
-        res = self.f32("dino.res", (rows, e))
-        res.view(bn, t, e)[:, :npre].copy_(p[pre + ".prefix"])       # CLS and register rows (weights only; plain copy)
-        L.gemm(a, p[pre + ".patch.w"], bias=w[pre + ".embeddings.patch_embeddings.bias"], out32=res, map=L.MAP_GROUP,
-               p=(hw, t, npre, 0, 0), **akw)
-        x16 = self.buf("dino.x16", (rows, e))
-        at = self._attn_geo("dino", bn, t)
+        a, akw = self.patches("vit.patchA", images, bn * hw, spec.patch)
+        res = self.f32("vit.res", (rows, e))
+        res.view(bn, t, e)[:, :npre].copy_(prefix)       # CLS (+ pos[0]) and register rows (weights only; plain copy)
+        L.gemm(a, p[pre + ".patch.w"], bias=w[f"{pre}.{kind.patch}.bias"], **poskw, out32=res, map=L.MAP_GROUP, p=(hw, t, npre, 0, 0), **akw)
+        x16 = self.buf("vit.x16", (rows, e))
+        at = self._attn_geo("vit", bn, t)
         rvec = None
         self.last_block_path = "fold" if self.norm_fold and at.form == "rows" and t >= 128 else "plain"
-        if self.last_block_path == "fold":
-            xs = self.buf("dino.xs", (rows, 2 * e), torch.float16)
-            part, mr = self._fold_bufs("dino", rows, e)
+        if self.last_block_path == "fold":                          # (per-image groups of the producer epilogue: >= 128 rows)
+            # The stream enters through a row map (prefix gap), so its planes and first statistics come from one pass each; the final
+            # LayerNorm is the LayerNorm kernel on hi + lo.
+            xs = self.buf("vit.xs", (rows, 2 * e), torch.float16)
+            part, mr = self._fold_bufs("vit", rows, e)
             L.add_rowvec_split(res, None, t, xs)
             L.norm_stats(res, nm.eps, x16, mr)
             for i in range(spec.depth):
                 self._block_fold(i, nm, at, xs, part, mr, i == 0)
-            res = self._planes_to_f32(xs, "dino.res")
+            res = self._planes_to_f32(xs, "vit.res")
         else:
             if self.mean_planes:
-                rvec = self.f32("dino.rvec", (bn, e), zero=True)
+                rvec = self.f32("vit.rvec", (bn, e), zero=True)
                 rvec.zero_()
             for i in range(spec.depth):
                 self._block_plain(i, nm, at, res, x16, rvec)
-        fin = self.f32("dino.final", (rows, e))
-        fin16 = self.buf("dino.final16", (rows, e))
-        self.ln(res, pre + ".norm", nm.eps, rvec, t, out32=fin, out16=fin16)
-        out32 = self.f32("dino.out32", (bn * hw, e))
-        out16 = self.buf("dino.out16", (bn * hw, e))
+        fin = self.f32("vit.final", (rows, e))
+        fin16 = self.buf("vit.final16", (rows, e))
+        self.ln(res, f"{pre}.{kind.final_norm}", nm.eps, rvec, t, out32=fin, out16=fin16)
+        out32 = self.f32("vit.out32", (bn * hw, e))
+        out16 = self.buf("vit.out16", (bn * hw, e))
         out32.view(bn, hw, e).copy_(fin.view(bn, t, e)[:, npre:])      # drop the prefix rows (plain strided copy)
         out16.view(bn, hw, e).copy_(fin16.view(bn, t, e)[:, npre:])
         return out32, out16, e
@@ -1176,14 +1096,8 @@ class LamEngine:
         if spec is None:
             raise ValueError("this model was built without an image encoder (use_vit=False)")
 
-        if spec.kind == "sam":
-            out32, out16, c = self.sam_encoder(images)
-        elif spec.kind == "dinov3":
-            out32, out16, c = self.dinov3_encoder(images)
-        elif spec.kind in ("hf", "dinov2"):
-            out32, out16, c = self.hf_encoder(images)
-        else:
-            raise ValueError(f"no encoder driver for kind {spec.kind!r}")
+        _ = self.kind          # raises for an unknown kind
+        out32, out16, c = self.sam_encoder(images) if spec.kind == "sam" else self.vit_encoder(images)
         return out32, out16, c, images.shape[-1] // spec.patch
 
     def lam_neck(self, emb32: Tensor, emb16: Optional[Tensor], bn: int, g: int) -> Tensor:

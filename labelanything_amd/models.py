@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from .config import (LamConfig, ENCODER_SPECS, check_classification, check_extraction, check_fusion_transformer, check_levels, check_prompt_encoder,
-                     config_from_kwargs,
+                     config_from_kwargs, encoder_kind,
                      resolve_examples)
 from .engine import LamEngine, PRECISE_DEFAULT, resolve_precise
 from .weights import model_shapes, init_state_dict
@@ -637,7 +637,7 @@ class ImageEncoder(nn.Module):
                  compute_dtype=torch.float16, vit_patch_size: Optional[int] = None):
         super().__init__()
         spec = ENCODER_SPECS[encoder]
-        side = image_size or (spec.img_size if spec.kind == "sam" else 480)
+        side = image_size or encoder_kind(spec.kind).default_side or spec.img_size
         kw = dict(encoder=encoder, image_size=side, vit_patch_size=vit_patch_size or spec.patch)
         if spec.kind != "sam":
             kw.update(image_embed_dim=spec.dim)
@@ -689,6 +689,15 @@ def build_vit_b(**kw) -> ImageEncoder:
     return _build_sam_encoder("vit_b", **kw)
 
 
+def clean_hf_state_dict(sd: Dict[str, torch.Tensor], kind: str) -> Dict[str, torch.Tensor]:
+    """A HuggingFace checkpoint's tensors under the encoder's own key names: the ``vit.`` prefix of a ViTMAEForPreTraining stripped, its
+    ``decoder.`` dropped, and ``mask_token`` kept only where it is a parameter of the encoder's embeddings (DINOv3ViTEmbeddings,
+    Dinov2Embeddings; MAE's belongs to its decoder).  ``_hf5_to_hf4`` then takes the keys, prefixed with ``image_encoder.``."""
+    keep_mask_token = encoder_kind(kind).mask_token
+    return {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items()
+            if not k.startswith("decoder.") and (keep_mask_token or "mask_token" not in k)}
+
+
 def _build_hf_encoder(name: str, project_last_hidden=False, pretrained: Optional[str] = None, **kw) -> ImageEncoder:
     """``ViTModelWrapper.from_pretrained(<hub id>)`` (models/build_encoder.py:103-118).  There is no hub access in this build:
     ``pretrained`` names a LOCAL HuggingFace model directory (model.safetensors | pytorch_model.bin); without it the encoder keeps its
@@ -697,10 +706,7 @@ def _build_hf_encoder(name: str, project_last_hidden=False, pretrained: Optional
     if pretrained is not None:
         wpath = os.path.join(pretrained, "model.safetensors")
         sd = _load_any(wpath if os.path.exists(wpath) else os.path.join(pretrained, "pytorch_model.bin"))
-        # (a parameter of DINOv3ViTEmbeddings and of Dinov2Embeddings; MAE's belongs to its decoder)
-        keep_mask_token = {"dinov3": True, "dinov2": True, "hf": False}[ENCODER_SPECS[name].kind]
-        sd = {(k[len("vit."):] if k.startswith("vit.") else k): v for k, v in sd.items()
-              if not k.startswith("decoder.") and (keep_mask_token or "mask_token" not in k)}
+        sd = clean_hf_state_dict(sd, ENCODER_SPECS[name].kind)
         enc.load_state_dict(sd)
     return enc
 
@@ -729,8 +735,7 @@ def build_encoder(name: str, **kw) -> ImageEncoder:
         return ENCODERS[name](**kw)
     if name not in ENCODER_SPECS:
         raise KeyError(f"unknown encoder {name!r}; available: {sorted(ENCODER_SPECS)}")
-    return {"sam": _build_sam_encoder, "hf": _build_hf_encoder, "dinov3": _build_hf_encoder,
-            "dinov2": _build_hf_encoder}[ENCODER_SPECS[name].kind](name, **kw)
+    return globals()[encoder_kind(ENCODER_SPECS[name].kind).builder](name, **kw)
 
 
 # models/build_encoder.py:143-151, on-path entries (resnet50 / swin_b feed the out-of-scope pyramid variants)

@@ -28,6 +28,7 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import autograd_ops as A
+from .config import encoder_kind
 from .loss import FocalLossDevice, LabelAnythingLoss
 from .models import Lam
 from .optim import FlatAdamW
@@ -501,14 +502,8 @@ class LamTrainer:
             raise NotImplementedError(f"the prompt_contrastive loss component is not built for embeddings_per_example="
                                       f"{lam.cfg.embeddings_per_example} (more than one embedding per example); train it without that "
                                       f"component")
-        if train_encoder and lam.cfg.encoder_spec is not None and lam.cfg.encoder_spec.kind == "dinov3":
-            raise NotImplementedError("train_encoder=True with a 'dinov3' encoder is not built: the backward of la_rope_qk (the inverse "
-                                      "rotation) and the gradients of LayerScale and the register tokens do not exist; train on "
-                                      "precomputed embeddings (use_vit=False) or keep the encoder frozen")
-        if train_encoder and lam.cfg.encoder_spec is not None and lam.cfg.encoder_spec.kind == "dinov2":
-            raise NotImplementedError("train_encoder=True with a 'dinov2' encoder is not built: the gradients of LayerScale and of the "
-                                      "padded patch embedding (la_im2col_patch_pad's operand) do not exist; train on precomputed "
-                                      "embeddings (use_vit=False) or keep the encoder frozen")
+        if train_encoder and lam.cfg.encoder_spec is not None and encoder_kind(lam.cfg.encoder_spec.kind).train_refusal:
+            raise NotImplementedError(encoder_kind(lam.cfg.encoder_spec.kind).train_refusal)
         if lam._device().type != "cuda":
             raise RuntimeError("LamTrainer needs the model on an MI355X (there is no CPU path)")
         self.lam = lam
@@ -587,8 +582,8 @@ class LamTrainer:
         self._seen_version = lam.weights_version      # out-of-band weight changes (load_state_dict, invalidate) re-derive both: _sync_version
         self.enc_graph = None
         if self.train_encoder:
-            from .train_encoder import HfEncoderGraph, SamEncoderGraph
-            graph_cls = {"sam": SamEncoderGraph, "hf": HfEncoderGraph}[lam.cfg.encoder_spec.kind]     # (the other kinds are refused above)
+            from . import train_encoder
+            graph_cls = getattr(train_encoder, encoder_kind(lam.cfg.encoder_spec.kind).train_graph)     # (a kind without one is refused above)
             self.enc_graph = graph_cls(lam, {k: gv for k, gv in zip(self.names, self.opt.grad_views) if k.startswith("image_encoder.")},
                                        precise=self.train_precise)
             self._anchor = torch.zeros(1, device=lam._device(), requires_grad=True)

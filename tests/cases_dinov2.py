@@ -5,9 +5,8 @@ tests/test_dinov2_model_gpu.py, so all three see the same weights and inputs.  I
 """
 from __future__ import annotations
 
-import torch
-
 from labelanything_amd.config import EncoderSpec, LamConfig, register_encoder
+from tests.cases_encoder import encoder_config, encoder_images     # noqa: F401  (the family's importers take them from here)
 
 _D2 = dict(patch=14, layer_scale=True, ln_eps=1e-6)
 # position table 5 x 5 (img_size 70): used as stored at 70 px, resampled bicubically at every other side
@@ -26,19 +25,6 @@ ENCODER_CASES = {
     "hd32": dict(encoder="dinov2_hd32", side=70, images=3, weight_seed=43, image_seed=143, path="plain"),
     "fold": dict(encoder="dinov2_fold", side=168, images=2, weight_seed=44, image_seed=144, path="fold"),
 }
-
-
-def encoder_config(case: dict) -> LamConfig:
-    """The encoder-only model of an encoder case (what ``ImageEncoder`` builds)."""
-    from labelanything_amd.config import ENCODER_SPECS
-    spec = ENCODER_SPECS[case["encoder"]]
-    return LamConfig(encoder=case["encoder"], image_size=case["side"], vit_patch_size=spec.patch, image_embed_dim=spec.dim)
-
-
-def encoder_images(case: dict) -> torch.Tensor:
-    """Seeded normal images [images, 3, side, side] (the value range of normalised pixels)."""
-    g = torch.Generator().manual_seed(case["image_seed"])
-    return torch.randn(case["images"], 3, case["side"], case["side"], generator=g)
 
 
 # The tiny encoder inside the full model at 112 px (8 x 8 grid, 65 tokens, position table resampled 5 -> 8): LAM neck 128 -> 64, mask

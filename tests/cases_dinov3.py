@@ -5,9 +5,8 @@ tests/test_dinov3_model_gpu.py, so all three see the same weights and inputs.  I
 """
 from __future__ import annotations
 
-import torch
-
 from labelanything_amd.config import EncoderSpec, LamConfig, register_encoder
+from tests.cases_encoder import encoder_config, encoder_images     # noqa: F401  (the family's importers take them from here)
 
 _D3 = dict(prefix_tokens=5, rope_theta=100.0, layer_scale=True, key_bias=False, ln_eps=1e-5)
 register_encoder("dinov3_tiny", EncoderSpec("dinov3", dim=128, depth=2, heads=2, mlp=512, img_size=64, **_D3))
@@ -24,19 +23,6 @@ ENCODER_CASES = {
     "hd32": dict(encoder="dinov3_hd32", side=64, images=3, weight_seed=32, image_seed=132, path="plain"),
     "fold": dict(encoder="dinov3_fold", side=192, images=2, weight_seed=33, image_seed=133, path="fold"),
 }
-
-
-def encoder_config(case: dict) -> LamConfig:
-    """The encoder-only model of an encoder case (what ``ImageEncoder`` builds)."""
-    from labelanything_amd.config import ENCODER_SPECS
-    spec = ENCODER_SPECS[case["encoder"]]
-    return LamConfig(encoder=case["encoder"], image_size=case["side"], vit_patch_size=spec.patch, image_embed_dim=spec.dim)
-
-
-def encoder_images(case: dict) -> torch.Tensor:
-    """Seeded normal images [images, 3, side, side] (the value range of normalised pixels)."""
-    g = torch.Generator().manual_seed(case["image_seed"])
-    return torch.randn(case["images"], 3, case["side"], case["side"], generator=g)
 
 
 # The tiny encoder inside the full model at 128 px (8 x 8 grid, 69 tokens): LAM neck 128 -> 64, mask prompts, 1-way 1-shot, two episodes.

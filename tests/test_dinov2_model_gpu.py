@@ -7,64 +7,37 @@ logits; argmax exact outside the 2e-3 margin band, whose share of the reference'
 re-asserted here from the json).  The 99.9th percentile of the element-wise relative error is printed beside every max-norm figure.
 
 Measured on one MI355X (max-norm): tiny 4.03e-4, resample 4.65e-4, hd32 3.68e-4, fold 3.92e-4 (plain driver 4.05e-4), model case logits
-2.95e-4 and low-res logits 2.96e-4 (profiles/r15_dinov2.md).
+2.95e-4 and low-res logits 2.96e-4 (profiles/r15_dinov2.md).  The fold case's last bits differ from process to process (3.92e-4 - 3.99e-4
+seen): its 16 x 16 position table is resampled by la_gemm_tn, which splits the 256 input positions over workgroups and accumulates with
+float atomics, once per engine; every other case gives the same bits in every process (profiles/encoder_kinds.md).
 """
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 from click.testing import CliRunner
-from PIL import Image
 from safetensors.torch import load_file, save_file
 
 from labelanything_amd.models import ImageEncoder
 from labelanything_amd.weights import init_state_dict
-from tests import model_checks as MC
+from tests import encoder_checks as EC
 from tests.cases_dinov2 import ENCODER_CASES, MARGIN, MAX_BAND_SHARE, MODEL_CASES, encoder_config, encoder_images
-from tests.helpers import load_golden, pct_rel_err, rel_err
+from tests.encoder_checks import TOL, tokens
+from tests.helpers import load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-3
-
-
-def tokens(enc, images):
-    return enc(images).flatten(2).transpose(1, 2)            # [images, E, g, g] -> [images, hw, E]
-
-
-def run_encoder(name, norm_fold=True):
-    """(patch tokens [images, hw, E] of the case on the device path, the fixture's, the block driver taken)."""
-    case = ENCODER_CASES[name]
-    gold, meta = load_golden(f"dinov2_{name}")
-    assert meta["weight_seed"] == case["weight_seed"] and meta["image_seed"] == case["image_seed"]
-    enc = ImageEncoder(case["encoder"], image_size=case["side"], seed=case["weight_seed"]).cuda()
-    enc.lam.norm_fold = norm_fold
-    out = tokens(enc, encoder_images(case))
-    torch.cuda.synchronize()
-    return out, gold["patch_tokens"], enc.lam.engine().last_block_path
 
 
 @pytest.mark.parametrize("name", list(ENCODER_CASES))
 def test_encoder_matches_the_transformers_fixture(name):
     """Every case on the driver the engine chooses for it, which is asserted."""
-    got, ref, path = run_encoder(name)
-    err, p999 = rel_err(got, ref), pct_rel_err(got, ref)
-    print(f"[dinov2 {name}] path {path}: encoder output max-norm {err:.3e} (bound {TOL:.0e}), 99.9th percentile element-wise {p999:.3e}")
-    assert path == ENCODER_CASES[name]["path"]
-    assert err <= TOL
+    EC.check_encoder_case("dinov2", ENCODER_CASES, name)
 
 
 def test_fold_case_on_the_plain_block_driver():
     """The ViT-B-wide case with the LayerNorm kernels (``norm_fold = False``) - against the fixture, and against the folded driver."""
-    got, ref, path = run_encoder("fold", norm_fold=False)
-    folded, _, fpath = run_encoder("fold")
-    err, p999, between = rel_err(got, ref), pct_rel_err(got, ref), rel_err(got, folded)
-    print(f"[dinov2 fold] path {path}: encoder output max-norm {err:.3e} (bound {TOL:.0e}), 99.9th percentile element-wise {p999:.3e}; "
-          f"against the folded driver {between:.3e}")
-    assert (path, fpath) == ("plain", "fold")
-    assert err <= TOL
+    EC.check_fold_case_on_the_plain_driver("dinov2", ENCODER_CASES)
 
 
 def test_layer_scale_position_table_and_the_tail_chunk_are_not_no_ops():
@@ -95,27 +68,7 @@ def test_layer_scale_position_table_and_the_tail_chunk_are_not_no_ops():
 
 
 def test_model_case_logits_argmax_and_graph_replay():
-    name = "model_tiny_1w1s"
-    lam, case, gold, meta = MC.load_model(MODEL_CASES, name, "dinov2_")
-    from labelanything_amd.episodes import make_episode
-    batch = make_episode(**case["episode"])
-    seg, _ = lam._forward(batch)
-    out = lam.forward_argmax(batch)
-    torch.cuda.synchronize()
-    errs = {"low_res_logits": rel_err(seg, gold["low_res_logits"]), "logits": rel_err(out["logits"], gold["logits"])}
-    p999 = pct_rel_err(out["logits"], gold["logits"])
-    print(f"[dinov2 {name}] " + ", ".join(f"{k} {v:.3e}" for k, v in errs.items()) + f" (bound {TOL:.0e}), 99.9th percentile "
-          f"element-wise {p999:.3e}, encoder path {lam.engine().last_block_path}")
-    assert all(v <= TOL for v in errs.values()), errs
-    MC.check_argmax(name, out, gold, MARGIN, band_share=(meta, MAX_BAND_SHARE))
-    MC.check_graph_replay(lam, case)
-
-
-def _images(d, sizes):
-    rng = np.random.default_rng(0)
-    os.makedirs(d, exist_ok=True)
-    for i, (h, w) in enumerate(sizes):
-        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(os.path.join(d, f"{i:012d}.png"))
+    EC.check_model_case("dinov2", MODEL_CASES, "model_tiny_1w1s", MARGIN, MAX_BAND_SHARE)
 
 
 def test_generate_embeddings_from_a_dinov2_directory(tmp_path):
@@ -139,7 +92,7 @@ def test_generate_embeddings_from_a_dinov2_directory(tmp_path):
                    "hidden_act": "gelu"}, fh)
     save_file(enc_sd, str(model_dir / "model.safetensors"))
     imgs, out = str(tmp_path / "imgs"), str(tmp_path / "emb")
-    _images(imgs, [(100, 70)])
+    EC.write_images(imgs, [(100, 70)])
     r = CliRunner().invoke(main, ["generate_embeddings", "--huggingface", "--model_name", str(model_dir), "--directory", imgs,
                                   "--outfolder", out, "--image_resolution", "84", "--mean_std", "standard"])
     assert r.exit_code == 0, r.output + str(r.exception)

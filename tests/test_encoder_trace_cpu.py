@@ -10,7 +10,11 @@ planes instead of token means (planes), no split precision, bf16, no SAM neck, w
 la_relpos_terms, padded windows); at 256 px 16 x 16 (in-kernel rel-pos, windows wider than the image); 20 x 20 windows at 640 px (the
 only windows beyond 16 slots); the reduced fixtures' sam_tiny; 80-wide heads padded to 128.  HF, 768 wide, depth 2: folded and
 LayerNorm-kernel stacks at 224 px, V^T attention, fp8 QK^T, 96 px (37 tokens: below the fold's group size), hf_tiny with a resampled
-position table, 32-wide heads padded to 64.
+position table, 32-wide heads padded to 64.  DINOv3 (five prefix rows from the weights, no position table, la_rope_qk on q and k,
+LayerScale folded into the packed weights), 768 wide, depth 2 at 192 px (149 tokens): the folded stack, the LayerNorm kernels, V^T
+attention; the reduced fixtures' dinov3_tiny and dinov3_hd32 (32-wide heads: the first 32 of every 64 columns rotated) at 64 px.  DINOv2
+(patch 14, LayerScale folded likewise), 768 wide, depth 2: at 168 px (145 tokens) the folded stack and the LayerNorm kernels on a
+resampled table, at 224 px the table as stored; dinov2_tiny at 70 px, and at 42 px (resampled table, la_im2col_patch_pad); dinov2_hd32.
 
 The TRAINING graphs (train_encoder.py) have a table of their own, EXPECTED_TRAIN: forward, then backward of an all-ones gradient, on two
 zero images, with the gradient slots laid out in one flat buffer as FlatAdamW does.  Each row is pinned twice: the full trace, and the
@@ -83,6 +87,17 @@ EXPECTED = {
     'hf 96 default': (25, '1d7d6f67575faf9947ee7181dcd185ae10c7a213318e089f8effe097c18b8ced'),
     'hf_tiny 240': (19, '90ac544736b1a2f491e33b0e29743b74c96d20e2773dd593e20d17fd5cd4f86a'),
     'hf hd32 160': (19, '0fc307c677c6ebd002ffed0a3518237d7dbfd690bae86ced86831027c31d717c'),
+    'dinov3 fold 192': (28, 'fc84d67db4cfd4e2837eb49ddb7eec9896628f77ddd6ea4200f7777c4ffd3ca9'),
+    'dinov3 fold 192 nofold': (26, '379a3b1c5463bceaa23a1b80857e55c78812a548540d86c0f08e6934f2df2de9'),
+    'dinov3 fold 192 nofold norows': (26, 'f8a95d20ae38456ac920f1c6e153452800ad6d675179a1be06a0d88069a870dd'),
+    'dinov3 tiny 64': (20, '38f53994fc563cee6bb5eb503a593e3704dbee700b12e0f0723d9997f8065ac7'),
+    'dinov3 hd32 64': (20, '3efba6e7bf4da9873f0df2c43440a8f37711cd6ab7b1b42a08c10fc8ef0738d4'),
+    'dinov2 fold 168': (27, 'd4a04decee65af08459534ec742a62ee4767d7cdc360d672add7db61812d9690'),
+    'dinov2 fold 168 nofold': (25, 'ea5676bb089e32ff404212d316d30aafd97e4acbbff6cbe1753c3a2da25b4ba7'),
+    'dinov2 fold 224': (26, 'abfc0b9a3ea23488dd80e701815e9b9969ab36a48d1c2379d5e6a027f8a5f526'),
+    'dinov2 tiny 70': (18, 'e3f31178de6259593162860c3f2ef1c471ba457155783c9f7c2eaeb496d185ed'),
+    'dinov2 tiny 42': (19, '0537fd8ccefb197b8f59dafb032ba05650514386d2f937210c0bcb8a83ac9d71'),
+    'dinov2 hd32 70': (18, 'f464a969d09050e7a1cefff8271ea968c6e3062d7eea8a2bd4361e07aa008bba'),
 }
 
 # name: (number of lines, sha256 of the full trace, sha256 of the shape trace) - python tools/encoder_trace.py --train-table

@@ -8,50 +8,34 @@
                included - written once) over its time; beside it ``la_im2col_patch`` (p = 16, K = 768) on the same images as the
                yardstick - at 518 px on their top-left 512 x 512 corner, the largest part a 16 px grid covers.
 
-The variants' windows alternate in ONE process, so that all see the same clocks and neighbours; every figure is the median of --repeats
-windows of --iters calls after a warm-up, with the min - max spread beside it.  One JSON line per measurement goes to --out.
+How the windows are taken and where the JSON lines go: tools/bench_encoder.py.
 
     python tools/bench_dinov2.py [--images 8] [--iters 10] [--repeats 7]
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch                                        # noqa: E402
 
-from tools.bench_multi_embedding import alternate, stats   # noqa: E402
+from tools.bench_encoder import alternate, batch, forwards, main, stats   # noqa: E402
 
 SIDES = (224, 518)
 
 
-def batch(images, side):
-    g = torch.Generator().manual_seed(11 + side)
-    return torch.randn(images, 3, side, side, generator=g).cuda()
-
-
 def encoders(images, iters, repeats):
-    from labelanything_amd.models import ImageEncoder
-    xs = {side: batch(images, side) for side in SIDES}
-    encs = {side: ImageEncoder("vit_b_dinov2", image_size=side, seed=3).cuda() for side in SIDES}
-    fns = {f"forward_{side}": (lambda e=encs[side], x=xs[side]: e(x)) for side in SIDES}
-    for fn in fns.values():
-        fn()
-    t = alternate(fns, iters, repeats)
-    return {"what": "vit_b_dinov2_forward", "images": images,
-            "block_path": {str(side): encs[side].lam.engine().last_block_path for side in SIDES},
-            "patch_split": {str(side): bool(encs[side].lam.engine().patch_split) for side in SIDES},
-            **{k: stats(v) for k, v in t.items()}}
+    encs, t = forwards({f"forward_{side}": ("vit_b_dinov2", batch(images, side, 11 + side)) for side in SIDES}, iters, repeats)
+    engines = {str(side): encs[f"forward_{side}"].lam.engine() for side in SIDES}
+    return {"what": "vit_b_dinov2_forward", "images": images, "block_path": {k: e.last_block_path for k, e in engines.items()},
+            "patch_split": {k: bool(e.patch_split) for k, e in engines.items()}, **{k: stats(v) for k, v in t.items()}}
 
 
 def gathers(images, iters, repeats, side):
     from labelanything_amd import _lib as L
     from labelanything_amd.engine import patch_kp
-    x14 = batch(images, side)
+    x14 = batch(images, side, 11 + side)
     s16 = side // 16 * 16
     x16 = x14[..., :s16, :s16].contiguous()
     kp, k16 = patch_kp(14), patch_kp(16)
@@ -74,31 +58,16 @@ def gathers(images, iters, repeats, side):
     return rec
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--images", type=int, default=8)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_dinov2_bench.jsonl"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_dinov2 needs an MI355X: there is nothing to measure on the CPU")
-    lines = [{"what": "box", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "iters": a.iters, "repeats": a.repeats}]
-    print(json.dumps(lines[0]), flush=True)
-    lines.append(encoders(a.images, a.iters, a.repeats))
-    print(json.dumps(lines[-1]), flush=True)
+def records(images, iters, repeats):
+    enc = encoders(images, iters, repeats)
+    yield enc
     for side in SIDES:
-        lines.append(gathers(a.images, a.iters, a.repeats, side))
-        print(json.dumps(lines[-1]), flush=True)
-        form = "f16x2" if lines[1]["patch_split"][str(side)] else "f16"
-        lines.append({"what": f"gather_share_of_forward_{side}", "form": form,
-                      "share": round(lines[-1][f"pad_p14_{form}"]["median_us"] / lines[1][f"forward_{side}"]["median_us"], 5)})
-        print(json.dumps(lines[-1]), flush=True)
-    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-    with open(a.out, "w") as fh:
-        for rec in lines:
-            fh.write(json.dumps(rec) + "\n")
+        gather = gathers(images, iters, repeats, side)
+        yield gather
+        form = "f16x2" if enc["patch_split"][str(side)] else "f16"
+        yield {"what": f"gather_share_of_forward_{side}", "form": form,
+               "share": round(gather[f"pad_p14_{form}"]["median_us"] / enc[f"forward_{side}"]["median_us"], 5)}
 
 
 if __name__ == "__main__":
-    main()
+    main("bench_dinov2", "r15_dinov2_bench.jsonl", records)

@@ -21,7 +21,8 @@ holds every tensor of the prompt encoder's result and of the output - which are 
   python tools/encoder_trace.py --train-table       the same for the training matrix: full and shape digest per row
   python tools/encoder_trace.py --decoder-table     the same for the decoder matrix
   python tools/encoder_trace.py --print NAME        one trace (a row of any of the three matrices)
-  python tools/encoder_trace.py --packed NAME       key, shape, dtype, sha256 of the bytes of every packed weight of NAME's engine
+  python tools/encoder_trace.py --packed NAME       key, shape, dtype, sha256 of the bytes of every packed weight of NAME's engine, then
+                                                    of its fp32 ``image_encoder.`` weights (the LayerScale products live there)
 """
 from __future__ import annotations
 
@@ -38,7 +39,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from labelanything_amd import _lib as L                                            # noqa: E402
-from labelanything_amd.config import EncoderSpec, LamConfig, register_encoder     # noqa: E402
+from labelanything_amd.config import EncoderSpec, LamConfig, encoder_kind, register_encoder     # noqa: E402
 
 # host arithmetic only: these keep working.  (The host predicates that ask the shared library - gemm_fused_act_ok, conv3x3_split_ok,
 # stream_mlp_ok, extract_pool_plan - are recorder stand-ins like the launchers: a row states their answers in ``returns``.)
@@ -105,6 +106,8 @@ def _wide(kind: str, depth: int, **kw) -> EncoderSpec:
 
 def _specs() -> None:
     import tests.cases          # noqa: F401  (registers sam_tiny, hf_tiny)
+    import tests.cases_dinov2   # noqa: F401  (dinov2_tiny, dinov2_hd32, dinov2_fold)
+    import tests.cases_dinov3   # noqa: F401  (dinov3_tiny, dinov3_hd32, dinov3_fold)
     for s in (1024, 448, 256):
         register_encoder(f"trace_sam_{s}", _wide("sam", 3, img_size=s, global_idx=(2,), window=14))
     register_encoder("trace_sam_640_w20", _wide("sam", 3, img_size=640, global_idx=(2,), window=20))
@@ -122,6 +125,15 @@ def _sam(size: int, enc=None, ctor=None, attrs=None, last=False, **cfg):
 
 def _hf(size: int, enc="trace_hf", attrs=None, dim=768):
     return dict(cfg=dict(encoder=enc, image_size=size, image_embed_dim=dim, embed_dim=64), ctor={}, attrs=attrs or {}, last=False)
+
+
+def _vit(enc: str, size: int, attrs=None):
+    """A row of an encoder whose patch size and width come from its spec (the DINO families)."""
+    from labelanything_amd.config import ENCODER_SPECS
+    _specs()
+    spec = ENCODER_SPECS[enc]
+    return dict(cfg=dict(encoder=enc, image_size=size, vit_patch_size=spec.patch, image_embed_dim=spec.dim, embed_dim=64), ctor={},
+                attrs=attrs or {}, last=False)
 
 
 def matrix() -> dict:
@@ -153,6 +165,17 @@ def matrix() -> dict:
         "hf 96 default": _hf(96),
         "hf_tiny 240": _hf(240, enc="hf_tiny", dim=128),
         "hf hd32 160": _hf(160, enc="trace_hf_hd32", dim=128),
+        "dinov3 fold 192": _vit("dinov3_fold", 192),
+        "dinov3 fold 192 nofold": _vit("dinov3_fold", 192, nofold),
+        "dinov3 fold 192 nofold norows": _vit("dinov3_fold", 192, {"norm_fold": False, "attn_rows": False}),
+        "dinov3 tiny 64": _vit("dinov3_tiny", 64),
+        "dinov3 hd32 64": _vit("dinov3_hd32", 64),
+        "dinov2 fold 168": _vit("dinov2_fold", 168),
+        "dinov2 fold 168 nofold": _vit("dinov2_fold", 168, nofold),
+        "dinov2 fold 224": _vit("dinov2_fold", 224),
+        "dinov2 tiny 70": _vit("dinov2_tiny", 70),
+        "dinov2 tiny 42": _vit("dinov2_tiny", 42),
+        "dinov2 hd32 70": _vit("dinov2_hd32", 70),
     }
 
 
@@ -229,7 +252,7 @@ def train_graph(row: dict):
     for k, p in (reversed(named) if row["reverse"] else named):
         views[k] = flat[off:off + p.numel()].view_as(p)
         off += p.numel()
-    cls = TE.SamEncoderGraph if cfg.encoder_spec.kind == "sam" else TE.HfEncoderGraph
+    cls = getattr(TE, encoder_kind(cfg.encoder_spec.kind).train_graph)
     # (numerics as LamTrainer chooses them: no token-mean corrections in the saved-activation forward)
     graph = cls(lam, views, precise=tuple(g for g in lam.precise if g not in ("vmean", "projmean")))
     for k, v in row["attrs"].items():
@@ -373,7 +396,8 @@ def main() -> None:
         print("\n".join(trace(rows[a.show]).lines))
     else:
         Recorder().patch(setattr)
-        for k, v in sorted(engine(rows[a.packed]).p.items()):
+        eng = engine(rows[a.packed])
+        for k, v in sorted(eng.p.items()) + sorted((k, v) for k, v in eng.w32.items() if k.startswith("image_encoder.")):
             for ent in _sha_entries(k, v):
                 print(*ent)
 

@@ -6,7 +6,8 @@ off-path dependencies with empty stub modules, then the reference
 here, so a generator may still put a stand-in of its own in place of a stub (tools/make_golden_metrics_iou.py does).
 
 For the generators that build a model it also holds the model (``build_reference``, ``reference_episode``), the reference's training
-step in fp32 and fp64 (``run_train``, ``write_train``), the fixture files (``write_fixture``) and the command line (``main``).
+step in fp32 and fp64 (``run_train``, ``write_train``), the fixture files (``write_fixture``) and the command line (``main``); for the
+generators of an encoder family (DINOv2, DINOv3) everything but the transformers model (``encoder_family_main``).
 Nothing of the reference travels: fixtures hold seeds and the reference's outputs only.
 """
 from __future__ import annotations
@@ -256,6 +257,99 @@ def write_fixture(stem, tensors, meta, rows=None):
         with open(os.path.join(GOLDEN, stem + ".json"), "w") as fh:
             json.dump({**meta, "torch": torch.__version__, "generated_by": by}, fh, indent=1, default=list)
     return os.path.getsize(path)
+
+
+# ---- encoder families (tools/make_golden_dinov2.py, tools/make_golden_dinov3.py): transformers' model of the family on the seeded weights.
+# A script gives ``hf_model(spec, side)`` - its transformers config and model, eval mode - and, where this transformers spells the keys
+# otherwise, ``spell(key, the model's keys)``; ``cases`` is the family's tests/cases_<family>.py. ----
+class PatchGrid(torch.nn.Module):
+    """The encoder as the reference's Lam calls one: images -> [B, E, g, g], the prefix rows (CLS, registers) dropped - what the
+    reference's ``ViTModelWrapper`` does for a plain ViT."""
+
+    def __init__(self, model, prefix):
+        super().__init__()
+        self.model, self.prefix = model, prefix
+
+    def forward(self, pixel_values):
+        hs = self.model(pixel_values).last_hidden_state[:, self.prefix:]
+        b, hw, e = hs.shape
+        g = pixel_values.shape[-1] // self.model.config.patch_size
+        return hs.reshape(b, g, g, e).permute(0, 3, 1, 2).contiguous()
+
+
+def band_share(logits, margin):
+    """Share of pixels whose top-two gap is within margin * max|finite logit| (the pixels the argmax test does not compare)."""
+    top2 = logits.float().topk(2, dim=1).values
+    scale = float(logits[torch.isfinite(logits)].abs().max())
+    return float(((top2[:, 0] - top2[:, 1]) <= margin * scale).double().mean())
+
+
+def load_encoder(model, sd, spell=None):
+    """Strict-load the ``image_encoder.`` tensors of a seeded state dict, in the key spelling of this transformers."""
+    pre, local = "image_encoder.", set(model.state_dict())
+    enc = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+    model.load_state_dict({(spell(k, local) if spell else k): v for k, v in enc.items()}, strict=True)
+
+
+def encoder_fixture(family, cases, hf_model, spell, name, case):
+    """<family>_<name>: ``patch_tokens`` = last_hidden_state without the prefix rows, [images, hw, E], on CPU / fp32; the json holds the
+    seeds, the geometry and the model's state-dict keys and shapes in its order."""
+    from labelanything_amd.weights import init_state_dict
+    cfg = cases.encoder_config(case)
+    spec = cfg.encoder_spec
+    model = hf_model(spec, case["side"])
+    load_encoder(model, init_state_dict(cfg, case["weight_seed"]), spell)
+    with torch.no_grad():
+        hs = model(cases.encoder_images(case)).last_hidden_state
+    t = (case["side"] // spec.patch) ** 2 + spec.prefix_tokens
+    assert tuple(hs.shape) == (case["images"], t, spec.dim) and bool(torch.isfinite(hs).all())
+    out = hs[:, spec.prefix_tokens:].contiguous()
+    meta = {"case": name, **{k: case[k] for k in ("encoder", "side", "images", "weight_seed", "image_seed", "path")}, "tokens": t,
+            "state_dict": [[k, list(v.shape)] for k, v in model.state_dict().items()], "scale": float(out.abs().max())}
+    size = write_fixture(f"{family}_{name}", {"patch_tokens": out}, meta)
+    print(f"[{name}] tokens {t} output {tuple(out.shape)} scale {meta['scale']:.3f} bytes {size}")
+
+
+def encoder_model_fixture(family, cases, hf_model, spell, name, case):
+    """<family>_<name>: the family's encoder behind ``PatchGrid`` inside the reference's ``_build_lam``, the seeded episode through
+    ``Lam.forward``: low_res_logits, logits, argmax; the json holds the share of the reference's pixels inside the margin band, which must
+    be at most ``cases.MAX_BAND_SHARE`` (otherwise pick another weight seed)."""
+    from label_anything.models.build_lam import _build_lam
+    from labelanything_amd.episodes import make_episode
+    from labelanything_amd.weights import init_state_dict
+    cfg = case["cfg"]
+    spec = cfg.encoder_spec
+    vit = PatchGrid(hf_model(spec, cfg.image_size), spec.prefix_tokens)
+    lam = _build_lam(build_vit=(lambda project_last_hidden=True: vit), use_vit=True, use_vit_sam_neck=cfg.use_vit_sam_neck,
+                     image_embed_dim=cfg.image_embed_dim, embed_dim=cfg.embed_dim, image_size=cfg.image_size, vit_patch_size=cfg.vit_patch_size,
+                     class_attention=cfg.class_attention, example_attention=cfg.example_attention,
+                     example_class_attention=cfg.example_class_attention, spatial_convs=cfg.spatial_convs,
+                     class_encoder=dict(cfg.class_encoder) if cfg.class_encoder else None, custom_preprocess=cfg.custom_preprocess)
+    lam.eval()
+    sd = init_state_dict(cfg, case["weight_seed"])
+    load_encoder(vit.model, sd, spell)
+    res = lam.load_state_dict({k: v for k, v in sd.items() if not k.startswith("image_encoder.")}, strict=False)
+    assert all(k.startswith("image_encoder.") for k in res.missing_keys) and not res.unexpected_keys, res
+    batch = make_episode(**case["episode"])
+    rows = fixed_rows(lam, case, batch["flag_examples"].shape[2])
+    with torch.no_grad():
+        seg_low, _ = lam._forward(batch)
+        ref = lam(batch)
+    share = band_share(ref["logits"], cases.MARGIN)
+    assert share <= cases.MAX_BAND_SHARE, f"{name}: {share:.3%} of the reference's pixels lie inside the margin band; pick another weight seed"
+    assert bool(torch.isfinite(seg_low).all())
+    meta = {"case": name, "weight_seed": case["weight_seed"], "episode": case["episode"], "margin": cases.MARGIN, "margin_band_share": share,
+            "low_res_scale": float(seg_low.abs().max())}
+    size = write_fixture(f"{family}_{name}", logit_tensors(seg_low, ref), meta, rows)
+    print(f"[{name}] bytes {size} band share {share:.4f} low-res scale {meta['low_res_scale']:.3f}")
+
+
+def encoder_family_main(family, cases, hf_model, spell=None):
+    """The command line of an encoder family's generator: its ENCODER_CASES, then its MODEL_CASES."""
+    def forward(name, case):
+        (encoder_fixture if name in cases.ENCODER_CASES else encoder_model_fixture)(family, cases, hf_model, spell, name, case)
+
+    main({**cases.ENCODER_CASES, **cases.MODEL_CASES}, forward)
 
 
 def main(cases, forward, trains=()):
