@@ -61,8 +61,12 @@ __global__ __launch_bounds__(256) void focal_fwd_bwd_kernel(const float* __restr
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, xp[(long)c * HW]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(xp[(long)c * HW] - mx);
-    const float lse = mx + logf(se);
-    const float ce = lse - xp[t * HW];
+    // shift-stable: mx + logf(se) - x_t would lose ulp(mx) of ce (and of sm below) to a common offset of the logits.  sm keeps the
+    // form exp(x - lse) with the maximum taken out first - sm_t == pt, and the rounding of lg is one factor common to a pixel's
+    // classes, as before - rather than exp(x - mx) / se: equally accurate, but that form doubled the spread that the rounding
+    // residue of zero-gradient biases (sum_c dx_c == 0) shows between a two-rank and a one-process step (profiles/loss_conditioning.md)
+    const float lg = logf(se);
+    const float ce = lg - (xp[t * HW] - mx);
     const float pt = expf(-ce);
     const float om = 1.0f - pt;
     const float wt = w[(int)t];
@@ -73,7 +77,7 @@ __global__ __launch_bounds__(256) void focal_fwd_bwd_kernel(const float* __restr
       const float g = powf(om, gamma) + (om > 0.f ? gamma * ce * pt * powf(om, gamma - 1.0f) : 0.f);
       const float k = inv_n * wt * g;
       for (int c = 0; c < C; ++c) {
-        const float sm = expf(xp[(long)c * HW] - lse);
+        const float sm = expf((xp[(long)c * HW] - mx) - lg);
         dp[(long)c * HW] = k * (sm - (c == (int)t ? 1.0f : 0.0f));
       }
     }

@@ -281,8 +281,7 @@ __global__ __launch_bounds__(256) void lo_fused_kernel(const float* __restrict__
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       if (focal && tc[v] >= 0) {
-        const float lse = mx[v] + logf(se[v]);
-        const float ce = lse - xt[v];
+        const float ce = logf(se[v]) - (xt[v] - mx[v]);      // shift-stable: mx + logf(se) - x_t loses ulp(mx) to a common offset
         const float pt = expf(-ce);
         const float om = 1.0f - pt;
         const float wt = s_w[tc[v]];

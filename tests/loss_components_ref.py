@@ -87,6 +87,26 @@ def prompt_contrastive(emb: torch.Tensor, flags: torch.Tensor, t_prime: torch.Te
     return total / b
 
 
+def prompt_contrastive_pairs(emb: torch.Tensor, flags: torch.Tensor, t_prime: torch.Tensor, bias: torch.Tensor, y: Optional[torch.Tensor] = None):
+    """The per-pair breakdown of ``prompt_contrastive``: -> {"positive", "negative"} the two parts of the loss (their sum is the loss:
+    the pairs with y = +1 and with y = -1), {"u"} = -y z of every counted pair (i < j, both flagged, any image) and {"y"} of those
+    pairs.  ``y`` [n, n] replaces the class rule (tests/loss_profiles.py: a wrong pair label must show)."""
+    b, m, c, d = emb.shape
+    e = F.normalize(emb.double().reshape(b, m * c, d), p=2, dim=-1, eps=1e-12)
+    z = e @ e.transpose(1, 2) * torch.exp(t_prime.double()) + bias.double()
+    if y is None:
+        cls = torch.arange(m * c, device=emb.device) % c
+        y = torch.where(cls[:, None] == cls[None, :], 1.0, -1.0).double()
+    y = y.double().to(emb.device)
+    u = -y * z
+    loss = F.softplus(u)
+    f = flags.reshape(b, m * c) != 0
+    pair = torch.triu(f[:, :, None] & f[:, None, :], diagonal=1)
+    valid = f.sum(1).clamp_min(1).double()                      # an image without a flag has no pair: its divisor is never used
+    per = loss * pair / valid[:, None, None] / b
+    return {"positive": (per * (y > 0)).sum(), "negative": (per * (y < 0)).sum(), "u": u[pair], "y": y.expand_as(u)[pair]}
+
+
 def objective(components: Dict[str, Dict], class_weighting, logits: torch.Tensor, target: torch.Tensor,
               emb: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None, t_prime: Optional[torch.Tensor] = None,
               bias: Optional[torch.Tensor] = None):

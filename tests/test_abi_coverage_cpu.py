@@ -21,7 +21,6 @@ EXEMPT = {
     "la_bilinear_rows_bwd_set": "test_ops_gpu.py::test_bilinear_on_nhwc_rows_forward_and_backward",
     "la_error_count": "test_substitution_gpu.py::test_sampler_multi_tile_against_host",
     "la_error_points": "test_substitution_gpu.py::test_sampler_reproduces_the_reference_draws",
-    "la_focal_loss": "test_loss_gpu.py::test_focal_loss_matches_autograd_oracle",
     "la_prompt_masks": "test_image_prep_gpu.py::test_prompt_masks_match_reference_apply_masks",
     "la_resample_u8": "test_image_prep_gpu.py::test_device_resample_is_bit_exact_with_pillow",
     "la_u8_to_chw_norm": "test_image_prep_gpu.py::test_device_preprocess_matches_reference_chain_bit_for_bit",

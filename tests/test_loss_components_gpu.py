@@ -12,6 +12,7 @@ from safetensors.torch import load_file
 from labelanything_amd import _lib as L
 from labelanything_amd.loss import LabelAnythingLoss
 from tests import loss_components_ref as R
+from tests import loss_profiles as P
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -106,6 +107,22 @@ def test_logits_components_alone_and_without_gradient():
         assert abs(float(res["value"]) - float(val)) <= 5e-6 * max(1.0, abs(float(val))), comps
         assert set(res["components"]) == set(comps)
         assert int(crit.bad_targets) == 0
+        # with a gradient: against the sum of the components' own fp64 gradients, per image and relative to the smallest of them
+        # (tests/loss_profiles.py); the tolerance is the fp32 restatement's error under the same measure times its margin
+        xg = logits.cuda().requires_grad_(True)
+        with_grad = LabelAnythingLoss(comps, class_weighting=False)(xg, target.cuda())
+        with_grad["value"].backward()
+        assert torch.equal(with_grad["value"].detach(), res["value"])
+        cw = R.class_weights(target, logits.shape[1], False)
+        gamma = float(comps.get("focal", {}).get("gamma", 2.0))
+        fns = {"focal": lambda v: R.focal(v, target, gamma, cw), "dice": lambda v: R.dice(v, target, cw), "fp": lambda v: R.false_positive(v, target)}
+        parts = [P._grad64(fns[k], logits)[1] * float(kw["weight"]) ** 2 for k, kw in comps.items()]
+        mask = sum({"focal": 1, "dice": 2, "fp": 4}[k] for k in comps)
+        weights = {k: float(comps.get(k, {}).get("weight", 0.0)) for k in ("focal", "dice", "fp")}
+        const = P.image_ratio(P.logits32(logits, target, mask, gamma, False, weights=weights)["grad"], parts)
+        fig = P.image_ratio(xg.grad, parts)
+        print(f"{sorted(comps)}: gradient {fig:.3g}, restatement {const:.3g}")
+        assert fig <= P.MARGIN * max(const, P.U), (comps, fig, const)
 
 
 def test_two_calls_are_bitwise_identical():

@@ -1,6 +1,9 @@
 """GPU: la_prompt_contrastive at the widths and row counts training runs with - D = 512 (the embed_dim of the configs that use the
 term), D > 256 and n > 256 (the kernel's second and later register slices and its strided flag count), and the limits n = 1024,
-D = 1024 - against the fp64 restatement (tests/loss_components_ref.py)."""
+D = 1024 - against the fp64 restatement (tests/loss_components_ref.py), the gradient row by row: one row lies below F.normalize's eps
+and has a gradient of order 1e10, so a bound relative to the largest gradient of the whole tensor would leave every other row
+unchecked.  The tolerance is that of tests/loss_profiles.py: the error of the fp32 restatement of the kernel on the same inputs,
+against fp64 under the same measure, times its margin."""
 import math
 
 import pytest
@@ -8,6 +11,7 @@ import torch
 
 from labelanything_amd.loss import LabelAnythingLoss
 from tests import loss_components_ref as R
+from tests import loss_profiles as P
 
 pytestmark = pytest.mark.gpu
 
@@ -36,10 +40,13 @@ def test_large_rows_and_widths_match_the_restatement(shape):
     ref.backward()
     assert abs(float(res["value"]) - float(ref)) <= 2e-6 * max(1.0, abs(float(ref))), (float(res["value"]), float(ref))
     assert torch.equal(res["components"]["prompt_contrastive"], res["value"])
-    for mine, theirs in ((e.grad, ed.grad), (pc.t_prime.grad, tp.grad), (pc.bias.grad, bs.grad)):
-        assert torch.isfinite(mine).all()
-        err = float((mine.double() - theirs).abs().max())
-        assert err <= 1e-5 * max(1.0, float(theirs.abs().max())), err
+    case = {"emb": emb, "flags": flags, "t_prime": torch.tensor([math.log(30.0)]), "bias": torch.tensor([-7.0])}
+    want = {"demb": ed.grad.cpu(), "loss": float(ref.detach()), "dt": float(tp.grad), "db": float(bs.grad)}
+    const = P.contrastive_figures(want, P.contrastive32(case))            # the fp32 restatement against fp64: no kernel in it
+    got = {"demb": e.grad, "loss": float(res["value"]), "dt": float(pc.t_prime.grad), "db": float(pc.bias.grad)}
+    for k, v in P.contrastive_figures(want, got).items():                 # d emb per row; the loss, d t' and d bias relatively
+        print(f"{shape} {k}: {v:.3g}, restatement {const[k]:.3g}")
+        assert v <= P.MARGIN * max(const[k], P.U), (k, v, const[k])
     rows = flags.reshape(b, m * c) == 0                     # unflagged rows get no gradient
     assert float(e.grad.reshape(b, m * c, d)[rows.cuda()].abs().max()) == 0.0 if bool(rows.any()) else True
 
