@@ -828,6 +828,30 @@ int la_extract_unfold_bwd(const float* dov, const float* pooled, const float* Wv
 int la_rope_qk(void* qkv, long rows, int ld, int tokens, int prefix, int heads, int hd, int hdp, const float* cosw, const float* sinw, int dt,
                void* stream);
 
+/* ---- cosine-similarity few-shot segmenter (models/similarity.py, SimilarityFewShotSegmenter.forward) ----
+ * la_sim_prepare (similarity.py:123-131 and 141-142): x fp32 NHWC rows [n, gin^2, D] -> out16 fp16 rows [n, cs^2, D]:
+ * F.interpolate(mode="bicubic", align_corners=False) to cs x cs (A = -0.75, source scale * (dst + 0.5) - 0.5 with scale = gin / cs in
+ * fp32, border taps clamped; the 16 taps applied separably), then F.normalize over D (x / max(|x|, 1e-12)), rounded once to fp16 - one
+ * pass.  gin == cs: the normalisation alone.  D % 64 == 0, 64 <= D <= 1024; x 16-byte aligned.
+ * la_sim_class_bits (similarity.py:149-153 and 167-170): masks fp32 [P, N, Hm, Wm] -> bits uint32 [P, cs^2]: F.interpolate(mode="nearest")
+ * to cs x cs by torch's source-index rule (min(floorf(dst * (float)in / out), in - 1)); bit n (1 <= n < N) = masks[p, n] != 0 at the
+ * source pixel, bit 0 = none of the bits 1 .. N - 1 (class 0 of the input is not read: the reference replaces it).  1 <= N <= 32.
+ * la_sim_max (similarity.py:157-186): q16 fp16 [B, Q, D], k16 fp16 [B, K, D], bits uint32 [B, K] ->
+ *   out[b, n, q] = max over the keys k with bit n of bits[b, k] set of <q16[b, q], k16[b, k]>, -inf for a class without a key;
+ * out fp32 [B, N, Q].  fp16 32x32x16 MFMA with fp32 accumulation, keys as rows and queries as columns, so that the running maximum is
+ * register-local; the [Q, K] scores exist in accumulator registers only.  Per 32-key tile a class that no key has costs nothing, a class
+ * that every key has takes the unmasked maximum, and only a tile with both kinds of key pays a select per score.  Eight classes are
+ * carried per pass over the keys (N > 8: further passes).  Large problems split the keys over workgroups: the partial maxima go to
+ * `work` with plain stores and a second launch takes their maximum, so there are no atomics and - the maximum being independent of the
+ * order - the result is the same bits for every split and every run.  la_sim_max_plan gives the split and the floats `work` must hold
+ * (0: none needed) for a device of `ncu` compute units (<= 0: the current device; la_sim_max always plans for the current device).
+ * D % 64 == 0, 64 <= D <= 1024, 1 <= N <= 32, q16 and k16 16-byte aligned; anything else is refused with a message. */
+int la_sim_prepare(const float* x, long n, int gin, int cs, int D, void* out16, void* stream);
+int la_sim_class_bits(const float* masks, int P, int N, int Hm, int Wm, int cs, unsigned* bits, void* stream);
+int la_sim_max_plan(int B, int Q, int K, int D, int N, int ncu, int* ksplit, long long* work_floats);
+int la_sim_max(const void* q16, const void* k16, const unsigned* bits, int B, int Q, int K, int D, int N, float* work, long long work_floats,
+               float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,10 @@ SIGNATURES = dict(line.split() for line in """
     la_extract_unfold_bwd                   pppiiippps
     la_rope_qk                              pliiiiiippis
     la_im2col_patch_pad                     piiiipis
+    la_sim_prepare                          pliiips
+    la_sim_class_bits                       piiiiips
+    la_sim_max_plan                         iiiiiihh
+    la_sim_max                              pppiiiiipqps
 """.strip().splitlines())
 EXPORTS = list(SIGNATURES)                  # (tests check the .so exports all of them)
 _CTYPE = {"p": C.c_void_p, "h": C.c_void_p, "s": C.c_void_p, "i": C.c_int, "l": C.c_long, "q": C.c_longlong, "f": C.c_float}
@@ -1220,3 +1224,77 @@ def rope_qk(qkv, tokens: int, prefix: int, heads: int, hd: int, hdp: int, cos, s
     if qkv.shape[1] < 3 * heads * hdp:
         raise ValueError(f"rope_qk: qkv has {qkv.shape[1]} columns, q | k | v of {heads} heads of {hdp} need {3 * heads * hdp}")
     _call(lib().la_rope_qk, qkv, qkv.shape[0], qkv.stride(0), tokens, prefix, heads, hd, hdp, cos, sin, dt_of(qkv))
+
+
+# ---- cosine-similarity few-shot segmenter (csrc/similarity.hip) ----------------------------------------------
+SIM_MAX_CLASSES = 32        # one class word per support pixel
+
+
+def _sim_width(who: str, d: int) -> None:
+    if d % 64 or not 64 <= d <= 1024:
+        raise ValueError(f"{who}: feature width D = {d} must be a multiple of 64 in [64, 1024]")
+
+
+def _sim_classes(who: str, n: int) -> None:
+    if not 1 <= n <= SIM_MAX_CLASSES:
+        raise ValueError(f"{who}: N = {n} classes, a class word holds 1 .. {SIM_MAX_CLASSES}")
+
+
+def sim_prepare(x, gin: int, cs: int, out16) -> None:
+    """x fp32 NHWC rows [n, gin^2, D] -> out16 fp16 [n, cs^2, D]: the bicubic resample to cs x cs (none if gin == cs), the L2
+    normalisation over D and the rounding, in one pass."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != gin * gin:
+        raise ValueError(f"sim_prepare: x must be a contiguous fp32 [n, gin^2 = {gin * gin}, D] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, _, d = x.shape
+    _sim_width("sim_prepare", d)
+    if out16.dtype != torch.float16 or not out16.is_contiguous() or tuple(out16.shape) != (n, cs * cs, d):
+        raise ValueError(f"sim_prepare: out16 must be a contiguous fp16 [{n}, {cs * cs}, {d}] tensor, got {out16.dtype} {tuple(out16.shape)}")
+    _call(lib().la_sim_prepare, x, n, gin, cs, d, out16)
+
+
+def sim_class_bits(masks, cs: int, bits) -> None:
+    """masks fp32 [P, N, Hm, Wm] -> bits int32 [P, cs^2] (the bit pattern of a uint32 class word): bit n = the nearest source pixel of
+    class n is non-zero, bit 0 = none of the classes 1 .. N - 1 has the pixel."""
+    if masks.dim() != 4 or masks.dtype != torch.float32 or not masks.is_contiguous():
+        raise ValueError("sim_class_bits: masks must be a contiguous fp32 [P, N, Hm, Wm] tensor")
+    p, n, hm, wm = masks.shape
+    _sim_classes("sim_class_bits", n)
+    if bits.dtype != torch.int32 or not bits.is_contiguous() or tuple(bits.shape) != (p, cs * cs):
+        raise ValueError(f"sim_class_bits: bits must be a contiguous int32 [{p}, {cs * cs}] tensor, got {bits.dtype} {tuple(bits.shape)}")
+    _call(lib().la_sim_class_bits, masks, p, n, hm, wm, cs, bits)
+
+
+def sim_max_plan(b: int, q: int, k: int, d: int, n: int, ncu: int = 0):
+    """(key split, floats of workspace) of ``sim_max`` on a device of ncu compute units (<= 0: the current device)."""
+    _sim_width("sim_max_plan", d)
+    _sim_classes("sim_max_plan", n)
+    ks, wf = C.c_int(0), C.c_longlong(0)
+    _call(lib().la_sim_max_plan, b, q, k, d, n, ncu, C.byref(ks), C.byref(wf))
+    return ks.value, wf.value
+
+
+def sim_max(q16, k16, bits, n: int, out, work=None) -> None:
+    """out[b, c, q] = max over the keys k whose class word bits[b, k] has bit c of <q16[b, q], k16[b, k]> (-inf: no such key).
+    q16 fp16 [B, Q, D], k16 fp16 [B, K, D], bits int32 [B, K], out fp32 [B, n, Q]; work: fp32, at least ``sim_max_plan(...)[1]`` floats
+    (allocated here if not given)."""
+    for t, name in ((q16, "q16"), (k16, "k16")):
+        if t.dim() != 3 or t.dtype != torch.float16 or not t.is_contiguous():
+            raise ValueError(f"sim_max: {name} must be a contiguous fp16 [B, rows, D] tensor, got {t.dtype} {tuple(t.shape)}")
+    b, q, d = q16.shape
+    k = k16.shape[1]
+    _sim_width("sim_max", d)
+    _sim_classes("sim_max", n)
+    if k16.shape[0] != b or k16.shape[2] != d:
+        raise ValueError(f"sim_max: k16 {tuple(k16.shape)} does not go with q16 {tuple(q16.shape)}")
+    if bits.dtype != torch.int32 or not bits.is_contiguous() or tuple(bits.shape) != (b, k):
+        raise ValueError(f"sim_max: bits must be a contiguous int32 [B, K] = [{b}, {k}] tensor, got {bits.dtype} {tuple(bits.shape)}")
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (b, n, q):
+        raise ValueError(f"sim_max: out must be a contiguous fp32 [{b}, {n}, {q}] tensor, got {out.dtype} {tuple(out.shape)}")
+    for t in (q16, k16, bits, out):
+        _dev(t)
+    need = sim_max_plan(b, q, k, d, n)[1]
+    if work is None:
+        work = torch.empty(max(need, 1), device=out.device, dtype=torch.float32)
+    elif work.dtype != torch.float32 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"sim_max: work must be contiguous fp32 with at least {need} elements")
+    _call(lib().la_sim_max, q16, k16, bits, b, q, k, d, n, work, work.numel(), out)
